@@ -8,13 +8,17 @@ One "step" = one pass of the hot path over one batch of synthetic input on every
 Multi-GPU: `value` at N > 1 is the STRONG split of the metric's ONE batch of `--batch` (8) songs over the ranks in
 contiguous slices - 8/4/2/1 songs per rank at 1/2/4/8 GPUs - through `ace355.dist.run_request` (exact-size RCCL broadcast of the
 request -> shard -> per-rank sampler + decode); the weak number (the reference's per-call cap of 8 songs on EVERY rank,
-handler/service_generate_request.py:12) is measured in the same run and reported beside it under `weak`.  `--scaling weak` makes the
+handler/service_generate_request.py:12) is measured in the same --full run and reported beside it under `weak`.  `--scaling weak` makes the
 weak number the headline instead.  `python bench.py --gpus N` with N > 1 outside torchrun re-executes itself under
 `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU over RCCL).
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job songs/s with inputs resident
-in HBM, plus `roofline` (dominant kernel = the bf16 MFMA GEMM, HIP-event timed) and `cpu_baseline`
-(the oracle/ restatement timed on this box's host cores on a bounded sample).
+Prints ONE JSON line on rank 0: value = whole-job songs/s with inputs resident in HBM, ms_per_step = host clock over the
+--steps timed passes.  A plain run does only that: set up, warm up, time, dump (--dump-outputs), print.  --full adds what
+takes passes or processes of its own: `roofline` (dominant kernel = the bf16 MFMA GEMM, HIP-event timed, one extra profiled
+pass; --no-roofline drops it), the board state and MFMA probe, `cpu_baseline` (the oracle/ restatement timed on the host's
+cores on a bounded sample; --no-cpu-baseline drops it) and, at N > 1, the other scaling mode beside the headline.
+--dump-outputs DIR writes what the last timed pass returned to its caller (the peak-normalised waveforms, or the latents
+with --no-vae) as DIR/<name>.npy in float32; above a size cap, the same fixed, seeded sample of each item's values.
 """
 from __future__ import annotations
 
@@ -53,13 +57,17 @@ def parse():
     ap.add_argument("--fp8", action="store_true",
                     help="BASELINE configs[4] precision: the four big projections on MXFP8 MFMA (not the headline metric, whose dtype is bf16)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
-                    help="strong (default, SURVEY 8e): --batch songs in total, split over the ranks, the weak number reported beside it; "
+                    help="strong (default, SURVEY 8e): --batch songs in total, split over the ranks, the weak number reported beside it with --full; "
                          "weak: --batch songs on EVERY rank")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / collective check WITHOUT a GPU: ranks over gloo on CPU tensors run broadcast -> (scatter) -> barrier "
                          "-> MAX-reduce and rank 0 prints a line marked dry_run (not a measurement; tests/test_dist_cpu.py drives it)")
     ap.add_argument("--lm-hints", action="store_true",
                     help="per-item LM hints [G,T,64] produced on rank 0 and SCATTERED to their owners each pass (think-mode conditioning)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: roofline + board state + MFMA probe, CPU baseline, the other scaling mode at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed pass's output (what the caller receives) as DIR/<name>.npy, float32, at most 64 MB in all")
     return ap.parse_args()
 
 
@@ -158,6 +166,23 @@ def vae_flops_per_frame(vcfg):
         f += rate * 3 * (2 * cout * cout * 8)      # 3 residual units: k7 + k1
     f += rate * 2 * vcfg.decoder_channels * vcfg.audio_channels * 7
     return f
+
+
+DUMP_BYTES = 32 << 20   # --dump-outputs, all ranks together (the option promises at most 64 MB)
+
+
+def dump_output(d, name, out, budget_bytes):
+    """`out` [B, ...] -> d/<name>.npy in float32: as it is when it fits `budget_bytes`, else as [B, n] with the same n positions of
+    every item, drawn by a fixed seed and sorted (the metric's 8 songs x 30 s of stereo are 92 MB)."""
+    import numpy as np
+    x = out.detach().float()
+    if x.numel() * 4 > budget_bytes:
+        x = x.reshape(x.shape[0], -1)
+        n = max(1, budget_bytes // (4 * x.shape[0]))
+        idx = torch.randperm(x.shape[1], generator=torch.Generator().manual_seed(0))[:n].sort().values
+        x = x[:, idx.to(x.device)]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, name + ".npy"), x.cpu().numpy())
 
 
 def library_source_sha() -> str:
@@ -490,17 +515,19 @@ def main():
         step_spread.update({"min": per[0], "median": per[len(per) // 2], "max": per[-1],
                             "what": "GPU time between the starts of consecutive passes on rank 0's stream (HIP events); the line's ms_per_step is the "
                                     "host clock over all passes, MAX over ranks"})
-        return G, s1 - s0, elapsed
+        return G, s1 - s0, elapsed, out
 
     step_spread = {}
     other = None
-    if world > 1:   # both modes in one run: the headline one last, so that the profiled pass below re-runs ITS per-rank shape
+    if args.full and world > 1:   # both modes in one run: the headline one last, so that the profiled pass below re-runs ITS per-rank shape
         o_mode = "weak" if args.scaling == "strong" else "strong"
         o_steps = max(2, args.steps // 4)   # (a side number: it must not double the run the driver times around the headline K steps)
-        oG, oB, o_el = measure(o_mode, o_steps, max(1, args.warmup // 2))
+        oG, oB, o_el, _ = measure(o_mode, o_steps, max(1, args.warmup // 2))
         other = {"scaling": o_mode, "value": oG * o_steps / o_el, "unit": "songs/s", "ms_per_step": 1000.0 * o_el / o_steps,
                  "global_batch": oG, "batch_rank0": oB, "steps": o_steps}
-    G, B, elapsed = measure(args.scaling, args.steps, args.warmup)
+    G, B, elapsed, out = measure(args.scaling, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, ("audio" if vae is not None else "latents") + (f"_rank{rank}" if world > 1 else ""), out, DUMP_BYTES // world)
 
     songs = G * args.steps
     value = songs / elapsed
@@ -530,7 +557,7 @@ def main():
         assert not collective
         return execute(dict(last_local))
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # dominant kernel = gemm_kernel: algorithmic FLOPs per launch / HIP-event launch time, one extra profiled pass
         dit.set_profile(True)
         if vae is not None:
@@ -609,7 +636,7 @@ def main():
         result["achieved_tflops_executed"] = executed / 1e12 / (elapsed / args.steps)
         result["null_branch_shortcut_tflop_saved"] = (alg - executed) / 1e12
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # board state while the DiT part of one more pass is in flight (rocm-smi, best effort): the same binary measures 493-549 ms per pass
         # across the boxes of the pool, and sclk / package power under load say which kind of box a line came from
         try:
@@ -629,7 +656,7 @@ def main():
         except Exception as e:  # no rocm-smi, no permission, ...: the line is complete without it
             result["gpu_state_under_load"] = {"error": str(e)[:120]}
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # what THIS board's matrix pipe does on a pure MFMA loop with random bf16 operands (no memory traffic), right after the passes:
         # the same binary measures 493-549 ms per pass over the boxes of the pool (DVFS under one power cap), and a line is only
         # comparable with another box's beside this number (nominal dense peak 2500; round 2's reference box: 1964)
@@ -644,7 +671,7 @@ def main():
         except Exception as e:
             result["box_probe"] = {"error": str(e)[:160]}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # reported at N=1 only
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:  # reported at N=1 only
         result["cpu_baseline"] = cpu_baseline(args, dcfg, vcfg, sd, vsd, enc.cpu(), null.cpu(), ctx_shared.cpu()[None], T, L)
 
     if rank == 0:

@@ -18,7 +18,7 @@ bash tools/profile_round.sh $TAG
 bash tools/mfma_busy_pass.sh $TAG
 # (after the PMC summaries exist in gpurun_out/: copy them where bench.py looks, so the line below carries its own traffic figure)
 cp $OUT/${TAG}_pmc_FETCH_SIZE.json $OUT/${TAG}_pmc_WRITE_SIZE.json $ROOT/profiles/ 2>/dev/null
-python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line.json
+python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line.json
 python -c "
 import json; d=json.load(open('$OUT/${TAG}_bench_line.json')); r=d['roofline']
 print('bench', round(d['value'],3), 'songs/s', round(d['ms_per_step'],1), 'ms; gemm frac', round(r['frac'],4), 'traffic', r.get('traffic'), 'cpu', d.get('cpu_baseline',{}).get('value'))"

@@ -26,7 +26,7 @@ for name, ls in rows.items():
 PY
 echo "# idle (before the bench)" > $OUT/${TAG}_smi_trace.txt
 rocm-smi --showclocks --showpower 2>/dev/null | grep -E "sclk|mclk|Power" >> $OUT/${TAG}_smi_trace.txt
-python bench.py --steps 40 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err &
+python bench.py --full --steps 40 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err &
 BP=$!
 sleep 12   # model build + warm-up
 echo "# under load (bench.py --steps 40, sampled every ~0.3 s)" >> $OUT/${TAG}_smi_trace.txt

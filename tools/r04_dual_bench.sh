@@ -17,7 +17,7 @@ for B in 4 2; do
   bash tools/ab_env.sh ACE355_DUAL=0 ACE355_DUAL=1 1 -- --steps 8 --warmup 2 --batch $B 2>&1 | tee -a $OUT/${TAG}_ab.txt
   ACE355_DUAL_SLOTS_MIN_ROWS=64 python bench.py --no-cpu-baseline --no-roofline --steps 8 --warmup 2 --batch $B 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('slots for every chain:', round(d['ms_per_step'],2), 'ms', round(d['value'],3))" | tee -a $OUT/${TAG}_ab.txt
 done
-python bench.py --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line.json
+python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line.json
 python -c "
 import json; d=json.load(open('$OUT/${TAG}_bench_line.json')); r=d['roofline']
 print(d['value'], d['ms_per_step'], {k: r[k] for k in ('achieved','frac','avg_launch_us','gemm_ms_per_pass','concurrent_chains','attn_tflops','attn_ms_per_pass','vae_conv_ms_per_pass')})"

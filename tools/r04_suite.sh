@@ -8,7 +8,7 @@ cd $ROOT
 timeout 3000 python -m pytest tests -m gpu -x -q -s 2>&1 | grep -v amdgpu.ids > $OUT/${TAG}_gpu_pytest.log
 tail -5 $OUT/${TAG}_gpu_pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -2 | tee -a $OUT/${TAG}_gpu_pytest.log
-python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line.json
+python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line.json
 python -c "import json; d=json.load(open('$OUT/${TAG}_bench_line.json')); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['config'].get('sampler_chains_per_gpu'))"
 for B in 1 2 4; do
   python bench.py --no-cpu-baseline --steps 10 --warmup 3 --batch $B 2>/dev/null | tail -1 > $OUT/${TAG}_b${B}_vae_line.json

@@ -9,6 +9,6 @@ for v in "A=0" "ACE355_GEMM_GROUPM=2" "ACE355_GEMM_GROUPM=8" "ACE355_GEMM_GROUPM
   env $v timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "gemm_sp_kernel" --output-format csv -d /tmp/prof_r -- python $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline > /tmp/prof_r.log 2>&1
   python $ROOT/tools/pmc_summary.py /tmp/prof_r /tmp/prof_r.json > /dev/null 2>&1
   F=$(python -c "import json; d=json.load(open('/tmp/prof_r.json')); print('%.1f MB x 2 (gfx950 correction) per launch over %d launches' % (d['gemm']['FETCH_SIZE']['per_launch']*1024/1e6, d['gemm']['FETCH_SIZE']['launches']))")
-  T=$(env $v python $ROOT/bench.py --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f ms per pass, GEMM %.4f' % (d['ms_per_step'], d['roofline']['frac']))")
+  T=$(env $v python $ROOT/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f ms per pass, GEMM %.4f' % (d['ms_per_step'], d['roofline']['frac']))")
   echo "$v: FETCH $F; $T"
 done
