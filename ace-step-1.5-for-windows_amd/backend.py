@@ -59,12 +59,41 @@ class NativeDitMixin:
             if quant == "fp8_weight_only":
                 dit.set_precision("fp8_weight_only")
             self.native_dit, self.use_native_dit = dit, True
+            self._native_adapter_key = None   # (a fresh handle carries the base weights)
             logger.info("[native-dit] decoder packed for gfx950 (%d layers, hidden %d)", cfg.num_hidden_layers, cfg.hidden_size)
             return True
         except Exception as exc:  # same policy as handler/mlx_dit_init.py:36-43
             logger.warning("[native-dit] init failed (%s: %s); PyTorch path stays active", type(exc).__name__, exc)
             self.use_native_dit, self.native_dit = False, None
             return False
+
+    def _native_adapter_terms(self):
+        """The LoRA terms the native DiT should carry now.  Default: the PEFT-wrapped ``self.model.decoder`` (the reference loads
+        adapters there after ``initialize_service``, H/lora/lifecycle.py:164-283), read by duck typing.  Hosts with a registry of their
+        own override this (``NativeHandler``)."""
+        from .lora import terms_from_decoder
+        return terms_from_decoder(self.model.decoder, getattr(self.native_dit, "cfg", None))
+
+    def _sync_native_adapters(self) -> None:
+        """Bring the native DiT's merged adapters in line with the host's: nothing at all while ``use_lora`` is off and nothing is
+        applied; a re-merge when the terms' fingerprint (names, scales, tensors, in-place versions) changed; the base back when
+        ``use_lora`` turned off.  ``UnsupportedAdapter`` (LoKr, DoRA, ...) propagates."""
+        applied = getattr(self, "_native_adapter_key", None)
+        if not getattr(self, "use_lora", False):
+            if applied is not None:
+                self.native_dit.clear_adapters()
+                self._native_adapter_key = None
+            return
+        from .lora import fingerprint
+        terms = list(self._native_adapter_terms())
+        key = fingerprint(terms) if terms else None
+        if key == applied:
+            return
+        if terms:
+            self.native_dit.set_adapters(terms)
+        else:
+            self.native_dit.clear_adapters()
+        self._native_adapter_key = key
 
     def _model_honours_timesteps(self) -> bool:
         """Whether the loaded checkpoint's own ``generate_audio`` reads an explicit ``timesteps=``: the sft and turbo models do
@@ -138,6 +167,7 @@ class NativeDitMixin:
         if ts_list is not None and not self._is_turbo() and not self._model_honours_timesteps():
             logger.info("[native-dit] base checkpoint: explicit timesteps are ignored, as its generate_audio does")
             ts_list = None
+        self._sync_native_adapters()   # (UnsupportedAdapter propagates: the seam's except runs the PyTorch path)
         if self._is_turbo():
             # turbo checkpoints (handler init_service_catalog.py:69-73 `is_turbo_model`): the model's own generate_audio has no
             # CFG / step count, only the shift -> 8-step table (turbo modeling file :1780-1995); same native loop
@@ -273,6 +303,12 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin):
         # data-parallel requests run in the library's launch-shape-independent mode (`shape_independent` below): a song's bits then do
         # not depend on how many ranks share the request.  False: the default (fastest) launch policy, batch-dependent low bits.
         self.dp_shape_independent = True
+        # LoRA registry (the reference's H/lora/lifecycle.py / controls.py state): adapter name -> its terms (PEFT scaling, device bf16)
+        self.lora_loaded = False
+        self.lora_scale = 1.0
+        self._lora_registry: Dict[str, list] = {}
+        self._active_loras: Dict[str, float] = {}
+        self._lora_active_adapter: Optional[str] = None
 
     def initialize_service(self, dit_config: DitConfig, decoder_state_dict: Dict[str, torch.Tensor],
                            null_condition_emb: torch.Tensor, vae_config: Optional[VaeConfig] = None,
@@ -306,6 +342,125 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin):
         except Exception as exc:
             logger.exception("initialize_service failed")
             return f"Error: {exc!s}", False
+
+    # ------------------------------------------------------------------ LoRA (H/lora/lifecycle.py, H/lora/controls.py)
+    def add_lora(self, lora_path: str, adapter_name: Optional[str] = None) -> str:
+        """Load the PEFT LoRA directory ``lora_path`` as ``adapter_name`` (default: the directory's name) and make it the active adapter
+        (lifecycle.py:164-286).  The native DiT merges it at the next request (``_sync_native_adapters``)."""
+        import os
+        from .lora import read_peft_adapter
+        if self.model is None:
+            return "❌ Model not initialized. Please initialize service first."
+        if self.quantization is not None:
+            return ("❌ LoRA loading is not supported on quantized models. "
+                    f"Current quantization: {self.quantization}. "
+                    "Please re-initialize the service with quantization disabled, then try loading the LoRA adapter again.")
+        if not lora_path or not lora_path.strip():
+            return "❌ Please provide a LoRA path."
+        lora_path = lora_path.strip()
+        if not os.path.exists(lora_path):
+            return f"❌ LoRA path not found: {lora_path}"
+        name = adapter_name.strip() if isinstance(adapter_name, str) and adapter_name.strip() else \
+            (os.path.basename(lora_path.rstrip(os.sep)) or "default")
+        if name in self._lora_registry:
+            return f"❌ Adapter name already in use: {name}. Use a different name or remove it first."
+        try:
+            terms = read_peft_adapter(lora_path, self.model.config)
+            dev = torch.device(self.device)
+            self._lora_registry[name] = [t._replace(A=t.A.to(dev, self.dtype), B=t.B.to(dev, self.dtype)) for t in terms]
+        except Exception as exc:
+            logger.exception("Failed to load LoRA adapter")
+            return f"❌ Failed to load LoRA: {exc!s}"
+        self.lora_loaded = True
+        self.use_lora = True
+        self._active_loras[name] = 1.0
+        self._lora_active_adapter = name
+        return f"✅ LoRA '{name}' loaded from {lora_path}"
+
+    def load_lora(self, lora_path: str) -> str:
+        """Single-adapter form of ``add_lora`` (lifecycle.py:289-295)."""
+        return self.add_lora(lora_path, adapter_name=None)
+
+    def remove_lora(self, adapter_name: str) -> str:
+        if not self._lora_registry:
+            return "⚠️ No LoRA adapter loaded."
+        if adapter_name not in self._lora_registry:
+            return f"❌ Unknown adapter: {adapter_name}. Loaded: {list(self._lora_registry.keys())}"
+        del self._lora_registry[adapter_name]
+        self._active_loras.pop(adapter_name, None)
+        if not self._lora_registry:
+            return self._lora_reset()
+        if self._lora_active_adapter == adapter_name:
+            self._lora_active_adapter = next(iter(self._lora_registry))
+        return f"✅ Adapter '{adapter_name}' removed. Active: {self._lora_active_adapter}"
+
+    def unload_lora(self) -> str:
+        if not self._lora_registry:
+            return "⚠️ No LoRA adapter loaded."
+        return self._lora_reset()
+
+    def _lora_reset(self) -> str:
+        self._lora_registry.clear()
+        self._active_loras.clear()
+        self._lora_active_adapter = None
+        self.lora_loaded = False
+        self.use_lora = False
+        self.lora_scale = 1.0
+        return "✅ LoRA unloaded, using base model"
+
+    def set_use_lora(self, use_lora: bool) -> str:
+        """controls.py:35-80."""
+        if use_lora and not self.lora_loaded:
+            return "❌ No LoRA adapter loaded. Please load a LoRA first."
+        self.use_lora = bool(use_lora)
+        return f"✅ LoRA {'enabled' if use_lora else 'disabled'}"
+
+    def set_lora_scale(self, adapter_name_or_scale, scale: Optional[float] = None) -> str:
+        """Scale of one adapter, clamped to [0, 1] (controls.py:83-113): ``set_lora_scale(0.5)`` for the active adapter or
+        ``set_lora_scale(name, 0.5)``."""
+        import math
+        if not self.lora_loaded:
+            return "⚠️ No LoRA loaded"
+        if scale is None:
+            value, name = adapter_name_or_scale, None
+        else:
+            value, name = scale, adapter_name_or_scale if isinstance(adapter_name_or_scale, str) else None
+        try:
+            value = float(value)
+        except (TypeError, ValueError):
+            return "❌ Invalid LoRA scale: please provide a numeric value between 0 and 1."
+        if not math.isfinite(value):
+            return "❌ Invalid LoRA scale: please provide a finite numeric value between 0 and 1."
+        value = max(0.0, min(1.0, value))
+        name = name or self._lora_active_adapter or next(iter(self._active_loras), None)
+        if not name:
+            return "❌ No adapter specified and no active adapter. Load a LoRA or pass adapter_name."
+        if name not in self._lora_registry:
+            return f"❌ Adapter '{name}' not in loaded adapters: {list(self._lora_registry.keys())}"
+        self._active_loras[name] = value
+        self.lora_scale = value
+        if not self.use_lora:
+            return f"✅ LoRA scale ({name}): {value:.2f} (LoRA disabled)"
+        return f"✅ LoRA scale ({name}): {value:.2f}"
+
+    def set_active_lora_adapter(self, adapter_name: str) -> str:
+        """Only the active adapter applies (PEFT's set_adapter; controls.py:193-205)."""
+        if adapter_name not in self._lora_registry:
+            return f"❌ Unknown adapter: {adapter_name}"
+        self._lora_active_adapter = adapter_name
+        return f"✅ Active LoRA adapter: {adapter_name}"
+
+    def get_lora_status(self) -> Dict[str, Any]:
+        return {"loaded": self.lora_loaded, "active": self.use_lora, "scale": self.lora_scale, "scales": dict(self._active_loras),
+                "active_adapter": self._lora_active_adapter, "adapters": list(self._lora_registry.keys())}
+
+    def _native_adapter_terms(self):
+        """The active adapter of this handler's registry, at its scale."""
+        name = self._lora_active_adapter
+        if not name or name not in self._lora_registry:
+            return []
+        s = float(self._active_loras.get(name, 1.0))
+        return [t._replace(scale=t.scale * s) for t in self._lora_registry[name]]
 
     # ------------------------------------------------------------------ service_generate
     def service_generate(self, encoder_hidden_states: torch.Tensor, context_latents: torch.Tensor,
@@ -356,6 +511,10 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin):
         low bits follow the slice size (~3e-3 relative L2, both at the reference's distance); the payload says which:
         ``extra_outputs["data_parallel"]["batch_dependent_bits"]``.  ``extra_outputs`` (pred_latents, src_latents, ...)
         describe the RETURNING rank's slice ``extra_outputs["song_range"]``, ``audios`` on rank 0 all G songs.  The per-call cap of 8 (handler/service_generate_request.py:12) then holds per rank."""
+        if data_parallel and self.use_lora and self._native_adapter_terms():
+            # adapters live in this process's registry only: they are not part of the broadcast request
+            return self._error_payload(RuntimeError("data_parallel: LoRA adapters are rank-local and not part of the broadcast request; "
+                                                    "disable or remove the adapter first"))
         if data_parallel:
             import torch.distributed as dist
             if dist.is_initialized() and dist.get_world_size() > 1:

@@ -287,12 +287,23 @@ int launch_peak_normalize(float* wav, int B, long per_item, float* scratch, hipS
 int launch_normalize_db(float* wav, int B, long per_item, float amp, float* peaks, hipStream_t s);
 int launch_interleave(const float* wav, int B, int C, long S, void* out, int as_pcm16, hipStream_t s);
 int launch_latent_check(const float* x, long n, int* flags_dev, hipStream_t s);
+int launch_zero_u64(unsigned long long* p, long n, hipStream_t s);
 
 // generic pack: dst bf16 / f32 from src (f32 or bf16) with an index mapping
 // PACK_ROWS_HEADPAIR: rows of a [heads*128, cols] projection land so that the rotate-half partners (d, d+64) of every head
 // are neighbours: dst row = head*128 + (d < 64 ? 2d : 2(d-64)+1).  q.k is invariant under a common permutation of the head
 // dims, and RoPE / head-norm become local to 2 / 128 adjacent columns (see headnorm_rope_kernel's `paired` form).
 enum PackMode { PACK_ROWS = 0, PACK_ROWS_IL32 = 1, PACK_CONV_IN = 2, PACK_CONVT_OUT = 3, PACK_ROWS_HEADPAIR = 4 };
+// Packed row of source row r for the three row modes (PACK_ROWS with its row offset dst_row0, PACK_ROWS_IL32 with p0 = 0 gate / 1 up,
+// PACK_ROWS_HEADPAIR): the one row map of pack_kernel, also read by the LoRA merge and read-back (lora.hip).
+__host__ __device__ __forceinline__ long pack_row(int mode, long r, long dst_row0, int p0) {
+    if (mode == PACK_ROWS_IL32) return dst_row0 + (r >> 5) * 64 + p0 * 32 + (r & 31);
+    if (mode == PACK_ROWS_HEADPAIR) {
+        const long d = r & 127;
+        return dst_row0 + (r - d) + (d < 64 ? 2 * d : 2 * (d - 64) + 1);
+    }
+    return dst_row0 + r;
+}
 int launch_pack(const void* src, int src_dtype, void* dst, int dst_is_bf16, int mode, long rows, long cols, long dst_ld,
                 long dst_row0, int p0, int p1, hipStream_t s);
 
@@ -329,5 +340,27 @@ struct ConvArgs {
 };
 int launch_conv(const ConvArgs& a, hipStream_t s);
 int launch_ncl_to_nlc(const float* z, bf16_t* out, int B, int C, int T, hipStream_t s);
+
+// LoRA merge (lora.hip, ace355_dit_set_adapters): one launch over the tiles of every target weight the call rewrites
+constexpr int LORA_TILE_ROWS = 64, LORA_TILE_COLS = 128;
+struct LoraTermDev {
+    const bf16_t* A;   // lora_A.weight [rank, cols]
+    const bf16_t* B;   // lora_B.weight [rows, rank]
+    int rank;
+    float scale;
+};
+struct LoraTargetDev {
+    bf16_t* dst;         // live packed buffer
+    const bf16_t* src;   // its pristine copy (same layout)
+    long ld;             // packed row pitch (= cols)
+    long row0;           // pack_row arguments of the target
+    int mode, p0;
+    int rows, cols;      // reference shape [out, in]; cols % 8 == 0
+    int tile0, tiles_n;  // first tile of this target in the launch, column tiles per row tile
+    int term0, nterms;   // terms [term0, term0 + nterms) of the term table; 0: copy the pristine rows back
+};
+int launch_lora_merge(const LoraTargetDev* targets_dev, int n_targets, int total_tiles, const LoraTermDev* terms_dev, hipStream_t s);
+int launch_lora_read(const bf16_t* w, long ld, int mode, long row0, int p0, long rows, long cols, void* dst, int dst_is_bf16,
+                     hipStream_t s);
 
 }  // namespace ace355

@@ -2,6 +2,7 @@
 // the decoder forward (AceStepDiTModel.forward, base.py:1303-1507) and the sampling loop
 // (generate_audio, base.py:1913-1981).  Host-side orchestration only; kernels live in gemm/attn/elementwise.hip.
 #include <math.h>
+#include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -41,6 +42,7 @@ struct CondSlot {
     bool valid = false;
     bool broadcast = false;       // all L keys identical (rows == 1): cross-attention output is a per-layer constant
     float* cross_const = nullptr; // [layers][D] = o_proj(v) of that constant, fp32
+    long gen_kv = 0, gen_o = 0;   // the LoRA weight generations (ace355_dit::Lora) the slot was built under
 };
 
 }  // namespace
@@ -169,6 +171,15 @@ struct ace355_dit {
     float* attn_part = nullptr;   // split-KV scratch lent to launch_attention (AttnArgs::part): small problems only
     long attn_part_floats = 0;
 
+    // LoRA adapters merged into the packed weights (ace355_dit_set_adapters, lora.hip)
+    struct Lora {
+        std::vector<std::pair<bf16_t*, bf16_t*>> pristine;   // live packed buffer -> its base copy (from the first merge that touches it)
+        std::set<std::string> applied;  // targets whose live rows hold a merge now
+        long gen_kv = 0, gen_o = 0;     // bumped by a call that rewrites a cross-attention k / v resp. o projection (condition slots)
+        void* tab = nullptr;            // device copy of the launch's target + term tables
+        size_t tab_bytes = 0;
+    } lora;
+
     // profiling
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> gemm_ev, attn_ev;
@@ -259,6 +270,54 @@ bool resolve(ace355_dit* h, const std::string& name, Dest* d) {
     if (name == "norm_out.weight") return rows(h->norm_out, 0, 1, D, D, 0);
     if (name == "scale_shift_table") return rows(h->sst_out, 0, 2, D, D, 0);
     return false;
+}
+
+// The ten LoRA target kinds of a layer (ace355_dit_set_adapters / ace355_dit_read_weight): the Linear projections of resolve(), by
+// their canonical reference key only
+bool lora_target(ace355_dit* h, const std::string& name, Dest* d) {
+    static const char* kinds[] = {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
+                                  "cross_attn.q_proj.weight", "cross_attn.k_proj.weight", "cross_attn.v_proj.weight", "cross_attn.o_proj.weight",
+                                  "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight"};
+    if (name.rfind("layers.", 0) != 0) return false;
+    const size_t dot = name.find('.', 7);
+    if (dot == std::string::npos || dot == 7 || dot - 7 > 2) return false;
+    const std::string li = name.substr(7, dot - 7), r = name.substr(dot + 1);
+    if (li.find_first_not_of("0123456789") != std::string::npos || std::to_string(atoi(li.c_str())) != li) return false;
+    bool kind = false;
+    for (const char* k : kinds) kind = kind || r == k;
+    return kind && resolve(h, name, d);
+}
+// elements of the packed projection buffer `buf` (one of a layer's seven)
+size_t packed_elems(const ace355_dit* h, const void* buf) {
+    const size_t D = h->D, F = h->F, QD = h->QD, KVD = h->KVD;
+    for (const LayerW& L : h->layers) {
+        if (buf == L.wqkv) return (QD + 2 * KVD) * D;
+        if (buf == L.wo || buf == L.wo_c) return D * QD;
+        if (buf == L.wq_c) return QD * D;
+        if (buf == L.wkv_c) return 2 * KVD * D;
+        if (buf == L.wgu) return 2 * F * D;
+        if (buf == L.wdown) return D * F;
+    }
+    return 0;
+}
+void lora_free_pristine(ace355_dit* h) {
+    for (auto& pr : h->lora.pristine) hipFree(pr.second);
+    h->lora.pristine.clear();
+}
+// A condition slot among `slots` whose cross K / V (or, broadcast, its cross-attention constant) was built before a set_adapters call
+// rewrote the weights they come from: ERR_STATE naming it
+int check_slot_generation(const ace355_dit* h, const int32_t* slots, int n) {
+    for (int i = 0; i < n; ++i) {
+        const int sl = slots[i];
+        if (sl < 0 || sl >= ACE355_MAX_SLOTS) continue;   // (range errors are reported where the slot is read)
+        const CondSlot& c = h->slots[sl];
+        if (c.valid && (c.gen_kv != h->lora.gen_kv || (c.broadcast && c.gen_o != h->lora.gen_o))) {
+            set_error("condition slot " + std::to_string(sl) + " is stale: it was built before ace355_dit_set_adapters changed the "
+                      "cross-attention weights; call ace355_dit_set_condition for it again");
+            return ACE355_ERR_STATE;
+        }
+    }
+    return 0;
 }
 
 struct EvScope {
@@ -574,7 +633,9 @@ int forward_core(ace355_dit* h, int N, int T, const int* slots, int temb_rows, h
     const bool fold = h->nf.on && temb_rows == 1 && M <= h->nf.cap_M;
     const auto& nf = h->nf;
     auto rowsq = [&](int li, int which) { return nf.rowsq + ((size_t)li * 3 + which) * M; };   // (M <= cap_M: this forward's rows)
-    if (fold) ACE_HIP(hipMemsetAsync(nf.rowsq, 0, (size_t)h->NL * 3 * M * sizeof(unsigned long long), s));
+    // (zeroed by a kernel, not hipMemsetAsync: inside a replayed sampler graph the memset node left the previous replay's sums in place for the
+    //  atomics to add to - a graph's first launch matched the eager path, every replay after it was off by 1e-2 relative L2)
+    if (fold && (rc = launch_zero_u64(nf.rowsq, (long)h->NL * 3 * M, s))) return rc;
     const float inv_d = 1.0f / (float)D;
     // (a sampler call computed the TimestepEmbedding and the folded norm vectors of EVERY step up front: this step's rows are used in
     //  place, and the loop has no per-step time_embed / mod_gs launches)
@@ -1083,6 +1144,8 @@ void ace355_dit_destroy(ace355_dit* h) {
     if (h->graph_in) hipEventDestroy(h->graph_in);
     if (h->graph_out) hipEventDestroy(h->graph_out);
     if (h->stage) hipFree(h->stage);
+    lora_free_pristine(h);
+    if (h->lora.tab) hipFree(h->lora.tab);
     if (h->rope_cos) hipFree(h->rope_cos);
     if (h->rope_sin) hipFree(h->rope_sin);
     if (h->enc_bf) hipFree(h->enc_bf);
@@ -1095,6 +1158,10 @@ void ace355_dit_destroy(ace355_dit* h) {
 int ace355_dit_load_tensor(ace355_dit* h, const char* name, const void* data, int dtype, int64_t numel, int is_device) {
     ACE_CHECK(h && name && data, "dit_load_tensor: null argument");
     ACE_CHECK(dtype == ACE355_DTYPE_F32 || dtype == ACE355_DTYPE_BF16, "dit_load_tensor: dtype");
+    if (!h->lora.applied.empty()) {
+        set_error("dit_load_tensor: LoRA adapters are applied; restore the base weights first (ace355_dit_set_adapters with no terms)");
+        return ACE355_ERR_STATE;
+    }
     Dest d;
     if (!resolve(h, name, &d)) {
         set_error(std::string("dit_load_tensor: unknown tensor name '") + name + "'");
@@ -1224,6 +1291,8 @@ int ace355_dit_set_condition(ace355_dit* h, int slot, const float* enc_dev, int 
     cs.broadcast = rows == 1;
     cs.L = L;
     cs.Lpad = Lpad;
+    cs.gen_kv = h->lora.gen_kv;
+    cs.gen_o = h->lora.gen_o;
     cs.valid = true;
     return ACE355_OK;
 }
@@ -1233,6 +1302,7 @@ int ace355_dit_forward(ace355_dit* h, const float* x_dev, const float* ctx_dev, 
     ACE_CHECK(h && x_dev && ctx_dev && t_host && t_r_host && slots_host && v_out_dev, "dit_forward: null argument");
     if (!h->finalized) { set_error("dit_forward: call ace355_dit_finalize first"); return ACE355_ERR_STATE; }
     ACE_CHECK(N > 0 && N <= ACE355_MAX_SEQS && T > 0, "dit_forward: N in [1,64], T > 0");
+    if (int rc0 = check_slot_generation(h, slots_host, N)) return rc0;
     hipStream_t s = (hipStream_t)stream;
     h->vt_key_N = h->vt_key_S = -1;   // (see ace355_dit_sample)
     h->cu_slots = 0;
@@ -1260,6 +1330,15 @@ int ace355_dit_sample(ace355_dit* h, const float* xt0_dev, const float* ctx_dev,
     const bool do_cfg = p->guidance_scale > 1.0f;
     const int copies = do_cfg ? 2 : 1, N = B * copies;
     ACE_CHECK(N <= ACE355_MAX_SEQS, "dit_sample: at most 64 sequences per call");
+    {   // every condition slot the call reads (a replayed graph reads them without passing forward_core's checks)
+        std::vector<int32_t> used;
+        for (int b = 0; b < B; ++b) {
+            used.push_back(p->cond_slots_host ? p->cond_slots_host[b] : p->cond_slot);
+            if (p->cover_switch_step < p->num_steps) used.push_back(p->non_cover_slots_host ? p->non_cover_slots_host[b] : p->non_cover_slot);
+        }
+        if (do_cfg) used.push_back(p->null_slot);
+        if (int rc0 = check_slot_generation(h, used.data(), (int)used.size())) return rc0;
+    }
     hipStream_t s = (hipStream_t)stream;
     RoctxRange r_sample("ace355.dit_sample");
     const int S = (T + 1) / 2;
@@ -1465,6 +1544,10 @@ int ace355_dit_set_precision(ace355_dit* h, int precision) {
     ACE_CHECK(precision == ACE355_PRECISION_BF16 || precision == ACE355_PRECISION_MXFP8 || precision == ACE355_PRECISION_FP8_WEIGHT_ONLY,
               "set_precision: unknown precision");
     if (!h->finalized) { set_error("set_precision: call ace355_dit_finalize first"); return ACE355_ERR_STATE; }
+    if (!h->lora.applied.empty() && precision != ACE355_PRECISION_BF16) {   // (the reference refuses LoRA on quantised models, H/lora/lifecycle.py:173-178)
+        set_error("set_precision: LoRA adapters are applied and are not supported on quantized weights; remove them first");
+        return ACE355_ERR_STATE;
+    }
     ACE_HIP(hipDeviceSynchronize());
     if (h->weights_fp8wo && precision != ACE355_PRECISION_FP8_WEIGHT_ONLY) {
         set_error("set_precision: the weights were rounded through fp8 (fp8_weight_only); load them again before selecting another precision");
@@ -1608,6 +1691,114 @@ int ace355_dit_graph_stats(ace355_dit* h, int64_t* captures, int64_t* replays) {
     if (captures) *captures = h->graph_captures;
     if (replays) *replays = h->graph_replays;
     return ACE355_OK;
+}
+
+int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_terms, void* stream) {
+    ACE_CHECK(h, "set_adapters: null handle");
+    ACE_CHECK(n_terms >= 0 && (n_terms == 0 || terms), "set_adapters: terms");
+    if (!h->finalized) { set_error("set_adapters: call ace355_dit_finalize first"); return ACE355_ERR_STATE; }
+    if (h->precision != ACE355_PRECISION_BF16 || h->weights_fp8wo) {   // H/lora/lifecycle.py:173-178
+        set_error(std::string("set_adapters: LoRA loading is not supported on quantized models. Current precision: ") +
+                  (h->weights_fp8wo ? "fp8_weight_only" : "mxfp8") + ". Load the weights again in bf16, then apply the adapter.");
+        return ACE355_ERR_STATE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // the terms per target, in call order; scale 0 drops a term
+    std::vector<std::string> order;
+    std::vector<std::vector<const ace355_lora_term*>> by;
+    std::vector<Dest> dests;
+    auto index_of = [&](const std::string& n) { for (size_t i = 0; i < order.size(); ++i) if (order[i] == n) return (int)i; return -1; };
+    for (int i = 0; i < n_terms; ++i) {
+        const ace355_lora_term& t = terms[i];
+        ACE_CHECK(t.name && t.A_dev && t.B_dev, "set_adapters: null name / A / B");
+        Dest d;
+        if (!lora_target(h, t.name, &d)) {
+            set_error(std::string("set_adapters: '") + t.name + "' is not a LoRA target (layers.{i}.{self_attn,cross_attn}.{q,k,v,o}_proj.weight, "
+                      "layers.{i}.mlp.{gate,up,down}_proj.weight)");
+            return ACE355_ERR_INVALID;
+        }
+        ACE_CHECK(t.rank >= 1 && std::isfinite(t.scale), "set_adapters: rank must be >= 1 and scale finite");
+        if (t.scale == 0.f) continue;
+        int k = index_of(t.name);
+        if (k < 0) { order.push_back(t.name); by.emplace_back(); dests.push_back(d); k = (int)order.size() - 1; }
+        by[k].push_back(&t);
+    }
+    const size_t n_merge = order.size();
+    for (const std::string& n : h->lora.applied) {   // merged before, no term now: its rows go back to the base
+        if (index_of(n) >= 0) continue;
+        Dest d;
+        lora_target(h, n, &d);
+        order.push_back(n); by.emplace_back(); dests.push_back(d);
+    }
+    if (order.empty()) return ACE355_OK;
+    ACE_HIP(hipStreamSynchronize(s));   // (the previous call's merge may still read the tables)
+    auto pristine_of = [&](const void* buf) -> bf16_t* {
+        for (auto& pr : h->lora.pristine) if (pr.first == buf) return pr.second;
+        return nullptr;
+    };
+    for (const Dest& d : dests) {   // first touch of a packed buffer: its base copy
+        if (pristine_of(d.dst)) continue;
+        const size_t n = packed_elems(h, d.dst);
+        void* q = nullptr;
+        ACE_HIP(hipMalloc(&q, n * sizeof(bf16_t)));
+        h->lora.pristine.push_back({(bf16_t*)d.dst, (bf16_t*)q});
+        ACE_HIP(hipMemcpyAsync(q, d.dst, n * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
+    }
+    std::vector<LoraTargetDev> tg;
+    std::vector<LoraTermDev> tm;
+    int tiles = 0;
+    bool kv = false, o = false;
+    for (size_t i = 0; i < order.size(); ++i) {
+        const Dest& d = dests[i];
+        ACE_CHECK(d.cols % 8 == 0, "set_adapters: target columns must be a multiple of 8");
+        LoraTargetDev x{};
+        x.dst = (bf16_t*)d.dst; x.src = pristine_of(d.dst); x.ld = d.dst_ld; x.row0 = d.dst_row0; x.mode = d.mode; x.p0 = d.p0;
+        x.rows = (int)d.rows; x.cols = (int)d.cols;
+        x.tiles_n = (x.cols + LORA_TILE_COLS - 1) / LORA_TILE_COLS;
+        x.tile0 = tiles;
+        tiles += (x.rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS * x.tiles_n;
+        x.term0 = (int)tm.size();
+        for (const ace355_lora_term* t : by[i]) tm.push_back(LoraTermDev{(const bf16_t*)t->A_dev, (const bf16_t*)t->B_dev, t->rank, t->scale});
+        x.nterms = (int)tm.size() - x.term0;
+        tg.push_back(x);
+        const std::string& n = order[i];
+        kv = kv || n.find(".cross_attn.k_proj.") != std::string::npos || n.find(".cross_attn.v_proj.") != std::string::npos;
+        o = o || n.find(".cross_attn.o_proj.") != std::string::npos;
+    }
+    const size_t tg_bytes = (tg.size() * sizeof(LoraTargetDev) + 255) / 256 * 256, bytes = tg_bytes + std::max<size_t>(tm.size(), 1) * sizeof(LoraTermDev);
+    if (bytes > h->lora.tab_bytes) {
+        if (h->lora.tab) hipFree(h->lora.tab);
+        h->lora.tab = nullptr; h->lora.tab_bytes = 0;
+        ACE_HIP(hipMalloc(&h->lora.tab, bytes));
+        h->lora.tab_bytes = bytes;
+    }
+    std::vector<char> host(bytes, 0);
+    memcpy(host.data(), tg.data(), tg.size() * sizeof(LoraTargetDev));
+    if (!tm.empty()) memcpy(host.data() + tg_bytes, tm.data(), tm.size() * sizeof(LoraTermDev));
+    ACE_HIP(hipMemcpyAsync(h->lora.tab, host.data(), bytes, hipMemcpyHostToDevice, s));
+    int rc = launch_lora_merge((const LoraTargetDev*)h->lora.tab, (int)tg.size(), tiles,
+                               (const LoraTermDev*)((char*)h->lora.tab + tg_bytes), s);
+    ACE_HIP(hipStreamSynchronize(s));   // (pageable source of the table copy; a merge is rare next to the requests it serves)
+    if (rc) return rc;
+    if (kv) h->lora.gen_kv++;   // condition slots built from the old cross k / v (or, broadcast, o) weights are stale now
+    if (o) h->lora.gen_o++;
+    h->lora.applied = std::set<std::string>(order.begin(), order.begin() + n_merge);
+    h->nf.key.clear();   // the folded-norm bias tables are products with the q / k / v and gate / up weights
+    if (h->dual.ctx) h->dual.ctx->nf.key.clear();
+    if (h->lora.applied.empty()) lora_free_pristine(h);   // the base is back everywhere (the stream was synchronised above)
+    return ACE355_OK;
+}
+
+int ace355_dit_read_weight(ace355_dit* h, const char* name, void* dst_dev, int dtype, void* stream) {
+    ACE_CHECK(h && name && dst_dev, "read_weight: null argument");
+    ACE_CHECK(dtype == ACE355_DTYPE_F32 || dtype == ACE355_DTYPE_BF16, "read_weight: dtype");
+    Dest d;
+    if (!lora_target(h, name, &d)) {
+        set_error(std::string("read_weight: '") + name + "' is not one of the projection weights read_weight serves");
+        return ACE355_ERR_INVALID;
+    }
+    return launch_lora_read((const bf16_t*)d.dst, d.dst_ld, d.mode, d.dst_row0, d.p0, d.rows, d.cols, dst_dev,
+                            dtype == ACE355_DTYPE_BF16 ? 1 : 0, (hipStream_t)stream);
 }
 
 int ace355_dit_set_tap(ace355_dit* h, int layer, float* dst_dev) {

@@ -660,13 +660,8 @@ __global__ void pack_kernel(const SRC* __restrict__ src, void* __restrict__ dst,
     if (i >= rows * cols) return;
     const long r = i / cols, c = i - r * cols;
     long di;
-    if (mode == PACK_ROWS) {
-        di = (dst_row0 + r) * dst_ld + c;
-    } else if (mode == PACK_ROWS_IL32) {
-        di = (dst_row0 + (r >> 5) * 64 + p0 * 32 + (r & 31)) * dst_ld + c;
-    } else if (mode == PACK_ROWS_HEADPAIR) {
-        const long d = r & 127;
-        di = (dst_row0 + (r - d) + (d < 64 ? 2 * d : 2 * (d - 64) + 1)) * dst_ld + c;
+    if (mode == PACK_ROWS || mode == PACK_ROWS_IL32 || mode == PACK_ROWS_HEADPAIR) {
+        di = pack_row(mode, r, dst_row0, p0) * dst_ld + c;
     } else if (mode == PACK_CONV_IN) {  // src [O][C][P] -> dst[o][p*C + c]
         const long cc = c / p1, pp = c - cc * p1;
         di = (dst_row0 + r) * dst_ld + pp * p0 + cc;
@@ -677,6 +672,12 @@ __global__ void pack_kernel(const SRC* __restrict__ src, void* __restrict__ dst,
     const float v = ldsrc<SRC>(src, i);
     if (dst_is_bf16) reinterpret_cast<bf16_t*>(dst)[di] = f2bf(v);
     else reinterpret_cast<float*>(dst)[di] = v;
+}
+
+// zero fill of integer accumulators that device-scope atomics add into (the folded norms' row sums, dit.hip forward_core)
+__global__ void zero_u64_kernel(unsigned long long* __restrict__ p, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = 0ull;
 }
 
 // mean over the sequence of every V head channel (fully-masked attention rows of the condition encoders, see AttnArgs::vmean)
@@ -1091,6 +1092,12 @@ int launch_latent_check(const float* x, long n, int* flags_dev, hipStream_t s) {
     ACE_HIP(hipMemsetAsync(flags_dev, 0, 2 * sizeof(int), s));
     const int g = (int)((n + 255) / 256) > 1024 ? 1024 : (int)((n + 255) / 256);
     hipLaunchKernelGGL(latent_check_kernel, dim3(g < 1 ? 1 : g), dim3(256), 0, s, x, n, flags_dev);
+    ACE_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_zero_u64(unsigned long long* p, long n, hipStream_t s) {
+    hipLaunchKernelGGL(zero_u64_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, p, n);
     ACE_LAUNCH_CHECK();
     return 0;
 }

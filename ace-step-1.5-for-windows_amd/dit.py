@@ -196,6 +196,51 @@ class NativeDit:
         with torch.cuda.device(self.device):
             native.check(self._lib.ace355_dit_set_precision(self._h, code), "dit_set_precision")
 
+    # ------------------------------------------------------------------ LoRA adapters, merged into the packed weights
+    def set_adapters(self, terms) -> None:
+        """Replace the WHOLE adapter state by ``terms`` (``ace355.lora.LoraTerm`` or ``(name, A, B, scale)`` tuples; an empty list
+        restores the base): every target weight becomes bf16(W0 + sum of scale x B @ A), whatever the earlier calls were
+        (include/ace355.h ``ace355_dit_set_adapters``).  A / B are converted to bf16 on this device, as the reference's
+        ``.to(self.dtype)`` does.  Synchronous: the merge has run on the current stream when this returns.  bf16 precision only."""
+        shapes = self.cfg.weight_shapes()
+        keep, rows = [], []   # (alive until the synchronous native call has returned)
+        with torch.cuda.device(self.device):
+            for name, A, B, scale in terms:
+                if name in shapes:
+                    out_f, in_f = shapes[name]
+                    if A.dim() != 2 or B.dim() != 2 or A.shape[1] != in_f or B.shape[0] != out_f or A.shape[0] != B.shape[1]:
+                        raise ValueError(f"set_adapters: A {tuple(A.shape)} / B {tuple(B.shape)} do not fit {name} [{out_f}, {in_f}]")
+                a = A.detach().to(self.device, torch.bfloat16).contiguous()
+                b = B.detach().to(self.device, torch.bfloat16).contiguous()
+                nm = name.encode()
+                keep += [a, b, nm]
+                rows.append((nm, native.ptr(a), native.ptr(b), int(a.shape[0]), float(scale)))
+            arr = (native.LoraTermC * max(len(rows), 1))(*[native.LoraTermC(*r) for r in rows])
+            native.check(self._lib.ace355_dit_set_adapters(self._h, arr, len(rows), native.current_stream_ptr()), "dit_set_adapters")
+        self._adapters_applied = any(float(r[4]) != 0.0 for r in rows)
+
+    def clear_adapters(self) -> None:
+        """Restore the base weights (``set_adapters([])``)."""
+        self.set_adapters([])
+
+    @property
+    def adapters_applied(self) -> bool:
+        return bool(getattr(self, "_adapters_applied", False))
+
+    def read_weight(self, name: str, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """The live (merged) weight ``name`` (one of the ten LoRA target kinds) in the reference layout [out, in]."""
+        shape = self.cfg.weight_shapes().get(name)
+        if shape is None:
+            raise ValueError(f"read_weight: unknown weight '{name}'")
+        out = torch.empty(shape, device=self.device, dtype=dtype)
+        code = native.DTYPE_BF16 if dtype == torch.bfloat16 else native.DTYPE_F32
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("read_weight: dtype must be float32 or bfloat16")
+        with torch.cuda.device(self.device):
+            native.check(self._lib.ace355_dit_read_weight(self._h, name.encode(), native.ptr(out), code, native.current_stream_ptr()),
+                         f"dit_read_weight({name})")
+        return out
+
     def set_norm_fold(self, enable) -> int:
         """RMSNorms folded into the neighbouring GEMM epilogues of sampler calls (default on; include/ace355.h).
         False / 0: off; True / 1: default (calls with >= 64 token rows); 2: every call the kernels support.  Returns the previous mode."""

@@ -65,6 +65,10 @@ class VaeConfigC(C.Structure):
     ]
 
 
+class LoraTermC(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("A_dev", C.c_void_p), ("B_dev", C.c_void_p), ("rank", C.c_int32), ("scale", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/ace355.h declares
 SIGNATURES = {
     "ace355_last_error": (C.c_char_p, []),
@@ -79,6 +83,8 @@ SIGNATURES = {
     "ace355_dit_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(SampleParamsC),
                                     C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
     "ace355_dit_set_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ace355_dit_set_adapters": (C.c_int, [C.c_void_p, C.POINTER(LoraTermC), C.c_int, C.c_void_p]),
+    "ace355_dit_read_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ace355_dit_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "ace355_dit_set_graph": (C.c_int, [C.c_void_p, C.c_int]),
     "ace355_dit_set_norm_fold": (C.c_int, [C.c_void_p, C.c_int]),

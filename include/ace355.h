@@ -202,6 +202,37 @@ int ace355_dit_dual_count(ace355_dit* h, int64_t* calls);
 int ace355_dit_set_dedup(ace355_dit* h, int enable);
 int ace355_dit_dedup_count(ace355_dit* h, int64_t* forwards);
 
+/* LoRA adapters, merged into the packed weights (PEFT LoraLayer semantics: the unmerged eval forward y = x W^T + scaling (x A^T) B^T
+ * equals a forward with W + scaling B A; the reference loads, removes, toggles and scales adapters in H/lora/lifecycle.py and
+ * H/lora/controls.py).  One term = one adapter on one target weight.  `name` is the reference key of the target, one of the ten
+ * kinds per layer: layers.{i}.{self_attn,cross_attn}.{q,k,v,o}_proj.weight and layers.{i}.mlp.{gate,up,down}_proj.weight;
+ * A_dev = lora_A.weight [rank, in], B_dev = lora_B.weight [out, rank], bf16 row-major, on the device (the reference casts them to
+ * the model dtype, .to(self.dtype)); scale = PEFT scaling[adapter] (alpha / r, or alpha / sqrt(r) with use_rslora) x the user's
+ * scale (H/lora/controls.py:83-113). */
+typedef struct ace355_lora_term {
+    const char* name;
+    const void* A_dev;
+    const void* B_dev;
+    int32_t rank;
+    float scale;
+} ace355_lora_term;
+/* Replace the WHOLE adapter state: afterwards every target weight is bf16_rne(float(W0) + sum_j s_j B_j A_j) (fp32 products, each
+ * term scaled in fp32, one rounding) and every other weight is W0, whatever the earlier calls were.  Several terms may name one target;
+ * terms with scale 0 are dropped (scale 0 gives the base bits); n_terms 0 restores the base.  The merge runs on `stream`, in place:
+ * weight addresses never change, so chain contexts, prefetch plans and captured sampler graphs (which replay with the new weights) stay
+ * valid.  The call is synchronous: it synchronises `stream` before it uploads its tables and again after the merge, so A / B may be
+ * released when it returns.  A target's base rows are kept in a pristine copy from the first merge that touches them until no adapter
+ * is left.
+ * Needs a finalized handle in ACE355_PRECISION_BF16 whose weights did not go through the fp8 round trip (the reference refuses LoRA on
+ * quantised models, H/lora/lifecycle.py:173-178): ERR_STATE otherwise.  An unknown name, rank < 1 or a null pointer: ERR_INVALID.
+ * While adapters are applied, ace355_dit_set_precision to another precision and ace355_dit_load_tensor return ERR_STATE.  A call
+ * that rewrites a cross-attention k / v (or o, for broadcast slots) projection makes the condition slots built before it stale:
+ * a forward / sample reading one returns ERR_STATE until ace355_dit_set_condition rebuilds it. */
+int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_terms, void* stream);
+/* Copy the live (merged) weight of one of the ten target kinds above to dst_dev in the reference layout [out, in] (the inverse of the
+ * packing's row map), as ACE355_DTYPE_F32 or ACE355_DTYPE_BF16; enqueued on `stream`.  Tests, and export of merged weights. */
+int ace355_dit_read_weight(ace355_dit* h, const char* name, void* dst_dev, int dtype, void* stream);
+
 /* Test / debug hook: after decoder layer `layer` (0-based) of every following forward, copy the fp32 residual stream
  * hidden_states [N*S, hidden] (the layer's output, base.py:539) to dst_dev; dst_dev NULL clears the tap.  Lets the parity
  * tests compare the per-layer activations the golden fixtures hold, not only the final velocity. */
