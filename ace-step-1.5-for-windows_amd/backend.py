@@ -190,6 +190,127 @@ class NativeDitMixin:
         out["target_latents"] = out["target_latents"].to(device=self.device, dtype=self.dtype)
         return out
 
+    # ---------------------------------------------------------------- lyric alignment (H/lyric_timestamp.py, H/lyric_score.py)
+    def _lyric_layers_config(self, custom_layers_config=None):
+        """The caller's config, else the host's ``custom_layers_config`` (acestep/handler.py:129), else the reference default."""
+        if custom_layers_config is not None:
+            return custom_layers_config
+        from .align import DEFAULT_LAYERS_HEADS
+        return getattr(self, "custom_layers_config", None) or DEFAULT_LAYERS_HEADS
+
+    def lyric_attention(self, pred_latent, encoder_hidden_states, context_latents, inference_steps: int = 8, seed: Optional[int] = 42,
+                        custom_layers_config=None, kind: str = "timestamp"):
+        """The cross-attention maps of the reference's alignment forward on the native DiT, in the handlers' layout and the host's dtype
+        (``ace355.align.lyric_attention``): one stack for ``kind="timestamp"``, an (lm, dit) pair for ``"score"``."""
+        if self.native_dit is None:
+            raise RuntimeError("native DiT backend is not initialised (call _init_native_dit)")
+        self._sync_native_adapters()
+        from .align import lyric_attention
+        return lyric_attention(self.native_dit, pred_latent, encoder_hidden_states, context_latents, inference_steps, seed,
+                               self._lyric_layers_config(custom_layers_config), kind, getattr(self, "dtype", torch.bfloat16))
+
+    def _lyric_segment(self, lyric_token_ids, vocal_language: str):
+        """The lyric token range: after the "# Languages / # Lyric" header the text encoder saw, up to <|endoftext|> (151643)."""
+        ids = lyric_token_ids[0].tolist() if isinstance(lyric_token_ids, torch.Tensor) else list(lyric_token_ids)
+        tok = getattr(self, "text_tokenizer", None)
+        if tok is None:
+            raise RuntimeError("lyric alignment needs the host's text_tokenizer")
+        start = len(tok.encode(f"# Languages\n{vocal_language}\n\n# Lyric\n", add_special_tokens=False))
+        end = ids.index(151643) if 151643 in ids else len(ids)
+        return ids[start:end], start, end
+
+    @staticmethod
+    def _timestamp_error(message: str) -> Dict[str, Any]:
+        return {"lrc_text": "", "sentence_timestamps": [], "token_timestamps": [], "success": False, "error": message}
+
+    @staticmethod
+    def _score_error(message: str) -> Dict[str, Any]:
+        return {"lm_score": 0.0, "dit_score": 0.0, "success": False, "error": message}
+
+    # host-side failures of the aligner stage that become an error payload (the reference's list, plus a missing scoring package or tokenizer)
+    _ALIGN_ERRORS = (ValueError, KeyError, RuntimeError, OSError, ImportError, AttributeError)
+
+    @torch.inference_mode()
+    def get_lyric_timestamp(self, pred_latent, encoder_hidden_states, encoder_attention_mask, context_latents, lyric_token_ids,
+                            total_duration_seconds: float, vocal_language: str = "en", inference_steps: int = 8, seed: int = 42,
+                            custom_layers_config=None) -> Dict[str, Any]:
+        """``get_lyric_timestamp`` (H/lyric_timestamp.py) with the maps from the native DiT; the host's ``MusicStampsAligner`` turns them into
+        LRC.  Without an active native DiT, or when the native part raises, the host's own method (further up the MRO) runs; a host without
+        one gets the error payload.  ``encoder_attention_mask`` is accepted and unused: the DiT discards it (base.py:1384-1385)."""
+        args = dict(pred_latent=pred_latent, encoder_hidden_states=encoder_hidden_states, encoder_attention_mask=encoder_attention_mask,
+                    context_latents=context_latents, lyric_token_ids=lyric_token_ids, total_duration_seconds=total_duration_seconds,
+                    vocal_language=vocal_language, inference_steps=inference_steps, seed=seed, custom_layers_config=custom_layers_config)
+        parent = getattr(super(), "get_lyric_timestamp", None)
+        if not (self.use_native_dit and self.native_dit is not None):
+            return parent(**args) if parent else self._timestamp_error("no lyric alignment backend available: the native DiT is not active")
+        if not isinstance(inference_steps, int) or inference_steps <= 0:
+            return self._timestamp_error(f"inference_steps must be a positive non-zero integer, got {inference_steps!r}")
+        layers = self._lyric_layers_config(custom_layers_config)
+        try:
+            matrix = self.lyric_attention(pred_latent, encoder_hidden_states, context_latents, inference_steps, seed, layers, "timestamp")
+        except Exception as exc:
+            logger.warning("[get_lyric_timestamp] native cross-attention maps failed (%s: %s)", type(exc).__name__, exc)
+            if parent:
+                return parent(**args)
+            return self._timestamp_error(f"Error generating timestamps: {exc}")
+        try:
+            ids, start, end = self._lyric_segment(lyric_token_ids, vocal_language)
+            from acestep.core.scoring.dit_alignment import MusicStampsAligner
+            aligner = MusicStampsAligner(self.text_tokenizer)
+            info = aligner.stamps_align_info(attention_matrix=matrix[:, :, start:end, :], lyrics_tokens=ids,
+                                             total_duration_seconds=total_duration_seconds, custom_config=layers, return_matrices=False,
+                                             violence_level=2.0, medfilt_width=1)
+            if info.get("calc_matrix") is None:
+                return self._timestamp_error(info.get("error", "Failed to process attention matrix"))
+            res = aligner.get_timestamps_and_lrc(calc_matrix=info["calc_matrix"], lyrics_tokens=ids,
+                                                 total_duration_seconds=total_duration_seconds)
+            return {"lrc_text": res["lrc_text"], "sentence_timestamps": res["sentence_timestamps"],
+                    "token_timestamps": res["token_timestamps"], "success": True, "error": None}
+        except self._ALIGN_ERRORS as exc:
+            logger.warning("[get_lyric_timestamp] failed (%s: %s)", type(exc).__name__, exc)
+            return self._timestamp_error(f"Error generating timestamps: {exc}")
+
+    @torch.inference_mode()
+    def get_lyric_score(self, pred_latent, encoder_hidden_states, encoder_attention_mask, context_latents, lyric_token_ids,
+                        vocal_language: str = "en", inference_steps: int = 8, seed: int = 42, custom_layers_config=None) -> Dict[str, Any]:
+        """``get_lyric_score`` (H/lyric_score.py) with the maps of its noise rows (lm) and mixed rows (dit) from the native DiT; the host's
+        ``MusicLyricScorer`` scores them.  Fallback and error payloads as ``get_lyric_timestamp``."""
+        args = dict(pred_latent=pred_latent, encoder_hidden_states=encoder_hidden_states, encoder_attention_mask=encoder_attention_mask,
+                    context_latents=context_latents, lyric_token_ids=lyric_token_ids, vocal_language=vocal_language,
+                    inference_steps=inference_steps, seed=seed, custom_layers_config=custom_layers_config)
+        parent = getattr(super(), "get_lyric_score", None)
+        if not (self.use_native_dit and self.native_dit is not None):
+            return parent(**args) if parent else self._score_error("no lyric alignment backend available: the native DiT is not active")
+        if not isinstance(inference_steps, int) or inference_steps <= 0:
+            return self._score_error(f"Error generating score: inference_steps must be a positive non-zero integer, got {inference_steps!r}")
+        layers = self._lyric_layers_config(custom_layers_config)
+        try:
+            lm, dit = self.lyric_attention(pred_latent, encoder_hidden_states, context_latents, inference_steps, seed, layers, "score")
+        except Exception as exc:
+            logger.warning("[get_lyric_score] native cross-attention maps failed (%s: %s)", type(exc).__name__, exc)
+            if parent:
+                return parent(**args)
+            return self._score_error(f"Error generating score: {exc}")
+        try:
+            ids, start, end = self._lyric_segment(lyric_token_ids, vocal_language)
+            if start >= lm.shape[-2]:
+                return self._score_error("Lyrics indices out of bounds")
+            from acestep.core.scoring.dit_score import MusicLyricScorer
+            aligner = MusicLyricScorer(self.text_tokenizer)
+
+            def one(matrix):
+                info = aligner.lyrics_alignment_info(attention_matrix=matrix[..., start:end, :], token_ids=ids, custom_config=layers,
+                                                     return_matrices=False, medfilt_width=1)
+                if info.get("energy_matrix") is None:
+                    return 0.0
+                res = aligner.calculate_score(energy_matrix=info["energy_matrix"], type_mask=info["type_mask"],
+                                              path_coords=info["path_coords"])
+                return float(res.get("lyrics_score", res.get("final_score", 0.0)))
+            return {"lm_score": one(lm), "dit_score": one(dit), "success": True, "error": None}
+        except self._ALIGN_ERRORS as exc:
+            logger.warning("[get_lyric_score] failed (%s: %s)", type(exc).__name__, exc)
+            return self._score_error(f"Error generating score: {exc}")
+
 
 class NativeVaeMixin:
     """Required host attributes: ``vae`` (state_dict + config) or ``vae_state_dict``/``vae_config``, ``device``."""
@@ -309,6 +430,8 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin):
         self._lora_registry: Dict[str, list] = {}
         self._active_loras: Dict[str, float] = {}
         self._lora_active_adapter: Optional[str] = None
+        from .align import DEFAULT_LAYERS_HEADS
+        self.custom_layers_config = {k: list(v) for k, v in DEFAULT_LAYERS_HEADS.items()}   # acestep/handler.py:129
 
     def initialize_service(self, dit_config: DitConfig, decoder_state_dict: Dict[str, torch.Tensor],
                            null_condition_emb: torch.Tensor, vae_config: Optional[VaeConfig] = None,

@@ -297,6 +297,20 @@ int ace355_attention(const void* q, const void* k, const void* v, void* out, int
     return attention_hook(q, k, v, out, N, Sq, Skv, Hq, Hkv, window, scale, nullptr, stream);
 }
 
+int ace355_cross_attention_probs(const void* q, const void* k, float* out, int N, int Sq, int Skv, int Hq, int Hkv, int q_ld, int k_ld,
+                                 const int32_t* heads_host, int n_heads, float scale, void* stream) {
+    ACE_CHECK(q && k && out && heads_host, "cross_attention_probs: null pointer");
+    ACE_CHECK(N > 0 && N <= ACE355_MAX_SEQS && n_heads > 0 && n_heads <= XATTN_MAX_HEADS, "cross_attention_probs: N / n_heads");
+    XattnArgs a{};
+    a.q = (const bf16_t*)q; a.q_seq_stride = (long)Sq * q_ld; a.q_ld = q_ld;
+    for (int i = 0; i < N; ++i) a.k_tab[i] = (unsigned long long)((const bf16_t*)k + (size_t)i * Skv * k_ld);
+    a.k_ld = k_ld;
+    a.out = out;
+    a.N = N; a.Sq = Sq; a.Skv = Skv; a.Hq = Hq; a.Hkv = Hkv; a.n_heads = n_heads; a.scale = scale;
+    for (int i = 0; i < n_heads; ++i) a.heads[i] = heads_host[i];
+    return launch_xattn_probs(a, (hipStream_t)stream);
+}
+
 int ace355_attention_masked(const void* q, const void* k, const void* v, void* out, int N, int Sq, int Skv, int Hq, int Hkv,
                             int window, float scale, const int32_t* kv_len_host, void* stream) {
     ACE_CHECK(kv_len_host, "attention_masked: null kv_len");

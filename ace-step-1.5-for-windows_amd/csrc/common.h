@@ -363,4 +363,17 @@ int launch_lora_merge(const LoraTargetDev* targets_dev, int n_targets, int total
 int launch_lora_read(const bf16_t* w, long ld, int mode, long row0, int p0, long rows, long cols, void* dst, int dst_is_bf16,
                      hipStream_t s);
 
+// Cross-attention probabilities (xattn_probs.hip, ace355_dit_cross_attention_maps / ace355_cross_attention_probs): for query heads
+// heads[p], out[p][n][j][s] = softmax_j(scale q[n][s] . k[n][j]) in fp32, j < Skv, s < Sq
+constexpr int XATTN_MAX_HEADS = 64;
+struct XattnArgs {
+    const bf16_t* q; long q_seq_stride; int q_ld;   // q[n * q_seq_stride + s * q_ld + 128 h + d] (head-normed)
+    unsigned long long k_tab[64]; int k_ld;         // k[n]: k_tab[n] + j * k_ld + 128 hkv + d (head-normed)
+    float* out;                                     // [n_heads][N][Skv][Sq]
+    int N, Sq, Skv, Hq, Hkv, n_heads;
+    int heads[XATTN_MAX_HEADS];
+    float scale;
+};
+int launch_xattn_probs(const XattnArgs& a, hipStream_t s);
+
 }  // namespace ace355

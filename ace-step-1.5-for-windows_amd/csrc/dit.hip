@@ -578,9 +578,20 @@ int normfold_prepare(ace355_dit* h, const ace355_sample_params* p, int N, int T,
     return 0;
 }
 
+// Cross-attention capture of ace355_dit_cross_attention_maps: the query heads requested per layer, and where their maps go.  Eager
+// calls on the handle itself only (never a chain context, never under graph capture).
+struct XattnPlan {
+    std::vector<std::vector<int>> heads;   // [NL]: requested query heads of each layer, increasing
+    std::vector<long> pair0;               // [NL]: index of the layer's first pair in the output
+    int last = -1;                         // the last layer with a request: the forward stops after its maps
+    float* out = nullptr;                  // [n_pairs][N][L][S] fp32
+};
+
 // Decoder body on a packed patch input xin[N][Tpad][192]; writes vpad[N][Tpad][64].
 // temb_rows == 1: every sequence shares one timestep (the sampler); else one row per sequence.
-int forward_core(ace355_dit* h, int N, int T, const int* slots, int temb_rows, hipStream_t s) {
+// plan != null: the forward writes the requested cross-attention maps right after each layer's cross-q GEMM and returns after those of
+// plan->last, without that layer's attention, cross o_proj and MLP, the later layers, norm_out and proj_out (vpad is not written).
+int forward_core(ace355_dit* h, int N, int T, const int* slots, int temb_rows, hipStream_t s, const XattnPlan* plan = nullptr) {
     const int S = (T + 1) / 2, M = N * S;
     const int D = h->D, F = h->F, QD = h->QD, KVD = h->KVD, QKV = QD + 2 * KVD;
     const int Sp = ((S + 63) / 64) * 64;
@@ -765,6 +776,21 @@ int forward_core(ace355_dit* h, int N, int T, const int* slots, int temb_rows, h
         if (mx_qc) rc = gemm_mx(h, nullptr, D, W.mx_qc, h->qkv, QD, Mc, QD, D, ep, s);
         else rc = gemm(h, h->xn, D, W.wq_c, D, h->qkv, QD, Mc, QD, D, ep, s);
         if (rc) return rc;
+        if (plan && !plan->heads[li].empty()) {   // the requested probabilities of this layer (xattn_probs.hip); no broadcast slot here
+            XattnArgs x{};
+            x.q = h->qkv; x.q_seq_stride = (long)S * QD; x.q_ld = QD;
+            for (int i = 0; i < Nc; ++i) x.k_tab[i] = (unsigned long long)(h->slots[slots[i]].kv + (size_t)li * L * 2 * KVD);
+            x.k_ld = 2 * KVD;
+            x.out = plan->out + (size_t)plan->pair0[li] * Nc * L * S;
+            x.N = Nc; x.Sq = S; x.Skv = L; x.Hq = h->HQ; x.Hkv = h->KVH; x.scale = scale;
+            x.n_heads = (int)plan->heads[li].size();
+            for (int i = 0; i < x.n_heads; ++i) x.heads[i] = plan->heads[li][i];
+            if ((rc = launch_xattn_probs(x, s))) return rc;
+            if (li == plan->last) {
+                h->pf_next.w = nullptr;   // (nothing pending may reach the first GEMM of the handle's next call)
+                return 0;
+            }
+        }
         bool cao_is_mx = false;
         {
             AttnArgs a{};
@@ -1318,6 +1344,52 @@ int ace355_dit_forward(ace355_dit* h, const float* x_dev, const float* ctx_dev, 
     rc = forward_core(h, N, T, slots_host, N, s);
     if (rc) return rc;
     return launch_copy_v(h->vpad, v_out_dev, N, T, Tpad, s);
+}
+
+int ace355_dit_cross_attention_maps(ace355_dit* h, const float* x_dev, const float* ctx_dev, const float* t_host, const float* t_r_host,
+                                    const int32_t* slots_host, int N, int T, const int32_t* pairs_host, int n_pairs, float* maps_out_dev,
+                                    void* stream) {
+    ACE_CHECK(h && x_dev && ctx_dev && t_host && t_r_host && slots_host && pairs_host && maps_out_dev,
+              "dit_cross_attention_maps: null argument");
+    if (!h->finalized) { set_error("dit_cross_attention_maps: call ace355_dit_finalize first"); return ACE355_ERR_STATE; }
+    ACE_CHECK(N > 0 && N <= ACE355_MAX_SEQS && T > 0, "dit_cross_attention_maps: N in [1,64], T > 0");
+    ACE_CHECK(n_pairs >= 1, "dit_cross_attention_maps: n_pairs >= 1");
+    ACE_CHECK(h->HQ <= XATTN_MAX_HEADS, "dit_cross_attention_maps: more query heads than the kernel's head table holds");
+    XattnPlan plan;
+    plan.heads.resize(h->NL);
+    plan.pair0.assign(h->NL, 0);
+    for (int i = 0; i < n_pairs; ++i) {
+        const int li = pairs_host[2 * i], hd = pairs_host[2 * i + 1];
+        ACE_CHECK(li >= 0 && li < h->NL && hd >= 0 && hd < h->HQ, "dit_cross_attention_maps: (layer, head) out of range");
+        ACE_CHECK(i == 0 || li > pairs_host[2 * i - 2] || (li == pairs_host[2 * i - 2] && hd > pairs_host[2 * i - 1]),
+                  "dit_cross_attention_maps: pairs must be strictly increasing (sorted, no duplicates)");
+        if (plan.heads[li].empty()) plan.pair0[li] = i;
+        plan.heads[li].push_back(hd);
+        plan.last = li;
+    }
+    int L = -1;
+    for (int i = 0; i < N; ++i) {
+        const int sl = slots_host[i];
+        ACE_CHECK(sl >= 0 && sl < ACE355_MAX_SLOTS && h->slots[sl].valid, "dit_cross_attention_maps: condition slot not set");
+        ACE_CHECK(!h->slots[sl].broadcast, "dit_cross_attention_maps: broadcast condition slot (its cross-attention is a constant: no maps)");
+        if (L < 0) L = h->slots[sl].L;
+        ACE_CHECK(h->slots[sl].L == L, "dit_cross_attention_maps: the condition slots of one call must share L");
+    }
+    if (int rc0 = check_slot_generation(h, slots_host, N)) return rc0;
+    plan.out = maps_out_dev;
+    hipStream_t s = (hipStream_t)stream;
+    h->vt_key_N = h->vt_key_S = -1;   // (see ace355_dit_sample)
+    h->cu_slots = 0;
+    int rc = ensure_workspace(h, N, T, s);
+    if (rc) return rc;
+    const int Tpad = 2 * ((T + 1) / 2);
+    rc = launch_pack_xin(x_dev, ctx_dev, h->xin, N, T, Tpad, s);
+    if (rc) return rc;
+    rc = time_embed(h, t_host, t_r_host, N, s);
+    if (rc) return rc;
+    h->nf.on = false;
+    h->nf.emb_on = false;
+    return forward_core(h, N, T, slots_host, N, s, &plan);
 }
 
 int ace355_dit_sample(ace355_dit* h, const float* xt0_dev, const float* ctx_dev, int B, int T, const ace355_sample_params* p,

@@ -109,6 +109,9 @@ class NativeDit:
             # (no host sync: `enc` is consumed by work queued on THIS stream, and torch's caching allocator only hands its block
             #  to later work of the same stream - record_stream covers a caller that allocated it on another one)
             enc.record_stream(torch.cuda.current_stream())
+        if not hasattr(self, "_slot_rows"):
+            self._slot_rows = {}
+        self._slot_rows[int(slot)] = int(L)   # (the output shape of cross_attention_maps)
 
     # ------------------------------------------------------------------ compute
     def forward(self, x: torch.Tensor, ctx: torch.Tensor, t: Sequence[float], t_r: Sequence[float], slots: Sequence[int]) -> torch.Tensor:
@@ -123,6 +126,34 @@ class NativeDit:
             native.check(self._lib.ace355_dit_forward(self._h, native.ptr(x), native.ptr(ctx), ta, tr, sl, N, T, native.ptr(out),
                                                       native.current_stream_ptr()), "dit_forward")
         return out
+
+    def cross_attention_maps(self, x: torch.Tensor, ctx: torch.Tensor, t: Sequence[float], t_r: Sequence[float], slots: Sequence[int],
+                             pairs: Sequence[Sequence[int]]) -> torch.Tensor:
+        """Cross-attention probabilities of the (layer, head) ``pairs`` (strictly increasing) for the forward ``forward`` would run:
+        fp32 ``[n_pairs, N, L, S]`` on this device, the reference's ``attn_weights[n, head, s, j]`` transposed to ``[L, S]``
+        (include/ace355.h ``ace355_dit_cross_attention_maps``).  The forward stops after the last requested layer."""
+        N, T, _ = x.shape
+        L = self._slot_L(slots)
+        S = (T + 1) // 2
+        x = x.detach().to(self.device, torch.float32).contiguous()
+        ctx = ctx.detach().to(self.device, torch.float32).contiguous()
+        flat = [int(v) for pr in pairs for v in pr]
+        n_pairs = len(flat) // 2
+        out = torch.empty(max(n_pairs, 1), N, max(L, 1), S, device=self.device, dtype=torch.float32)
+        ta = (C.c_float * N)(*[float(v) for v in t])
+        tr = (C.c_float * N)(*[float(v) for v in t_r])
+        sl = (C.c_int32 * N)(*[int(v) for v in slots])
+        pa = (C.c_int32 * max(len(flat), 1))(*flat)
+        with torch.cuda.device(self.device):
+            native.check(self._lib.ace355_dit_cross_attention_maps(self._h, native.ptr(x), native.ptr(ctx), ta, tr, sl, N, T, pa, n_pairs,
+                                                                   native.ptr(out), native.current_stream_ptr()),
+                         "dit_cross_attention_maps")
+        return out
+
+    def _slot_L(self, slots: Sequence[int]) -> int:
+        """Key count of the condition slots (recorded by ``set_condition``; the native call checks them again)."""
+        Ls = getattr(self, "_slot_rows", {})
+        return int(Ls.get(int(slots[0]), 0)) if len(slots) else 0
 
     def sample(self, xt0: torch.Tensor, ctx: torch.Tensor, t_sched: torch.Tensor, guidance_scale: float = 7.0,
                cfg_interval_start: float = 0.0, cfg_interval_end: float = 1.0, infer_method: str = "ode", use_adg: bool = False,

@@ -80,6 +80,9 @@ SIGNATURES = {
     "ace355_dit_set_condition": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ace355_dit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                      C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ace355_dit_cross_attention_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                  C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
+                                                  C.c_void_p]),
     "ace355_dit_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(SampleParamsC),
                                     C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
     "ace355_dit_set_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
@@ -159,6 +162,8 @@ SIGNATURES = {
                                        C.c_float, C.c_void_p]),
     "ace355_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_float, C.c_void_p]),
+    "ace355_cross_attention_probs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_float, C.c_void_p]),
     "ace355_attention_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_float, C.POINTER(C.c_int32), C.c_void_p]),
     "ace355_linear_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),

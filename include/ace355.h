@@ -111,6 +111,23 @@ int ace355_dit_set_condition(ace355_dit* h, int slot, const float* enc_dev, int 
 int ace355_dit_forward(ace355_dit* h, const float* x_dev, const float* ctx_dev, const float* t_host,
                        const float* t_r_host, const int32_t* slots_host, int N, int T, float* v_out_dev, void* stream);
 
+/* Cross-attention probabilities for lyric alignment: the reference's get_lyric_timestamp / get_lyric_score call the decoder with
+ * output_attentions=True (handler/lyric_timestamp.py:78, lyric_score.py:97) and read the maps P = softmax_fp32(q k^T scale) of
+ * eager_attention_forward (base.py:352) for a few (layer, head) pairs (custom_layers_config, acestep/handler.py:129).  Both padding
+ * masks are discarded (base.py:1384-1385): every encoder row is attended.  Query head h reads KV head h / (Hq / Hkv) (repeat_kv).
+ * Same inputs as ace355_dit_forward; pairs_host = n_pairs (layer, head) int32 pairs in strictly increasing order.  maps_out dev f32
+ * [n_pairs][N][L][S] (S = ceil(T / 2)): attn_weights[n, head, s, j] of that layer, transposed to [L, S] as the handlers do.  The scores
+ * are not rounded to bf16 before the softmax (the reference's GPU matmul does; its fp32 CPU path does not).
+ * The forward stops after the maps of the last requested layer: that layer's attention and MLP and every later layer do not run (no map
+ * depends on them; the reference runs them and discards the work, base.py:1454-1456).  Eager only (never captured); captured sampler
+ * graphs stay valid.  Every precision; in ACE355_PRECISION_MXFP8 the maps carry that mode's projection numerics.
+ * ERR_INVALID: a null pointer, n_pairs < 1, a layer outside [0, num_layers) or a head outside [0, num_heads), pairs unsorted or
+ * duplicated, N outside [1, ACE355_MAX_SEQS], a slot not set or broadcast (rows == 1), slots of different L.  ERR_STATE: not finalized, a
+ * stale slot (ace355_dit_set_adapters).  Nothing is enqueued on error. */
+int ace355_dit_cross_attention_maps(ace355_dit* h, const float* x_dev, const float* ctx_dev, const float* t_host,
+                                    const float* t_r_host, const int32_t* slots_host, int N, int T, const int32_t* pairs_host,
+                                    int n_pairs, float* maps_out_dev, void* stream);
+
 /* Knobs of generate_audio (base.py:1796-1812) that survive past prepare_condition. */
 typedef struct ace355_sample_params {
     int32_t num_steps;          /* len(t_sched) - 1 */
@@ -495,6 +512,11 @@ int ace355_headnorm_rope(void* x_bf16_dev, int M, int ld, int col0, int heads, c
  * window < 0 = full, else |i-j| <= window.  out bf16 [N,Sq,Hq*128]. */
 int ace355_attention(const void* q_dev, const void* k_dev, const void* v_dev, void* out_dev, int N, int Sq, int Skv,
                      int Hq, int Hkv, int window, float scale, void* stream);
+/* Cross-attention probabilities (the kernel behind ace355_dit_cross_attention_maps): q bf16 [N*Sq, q_ld] (head h at column 128 h),
+ * k bf16 [N*Skv, k_ld] (KV head g at column 128 g); for the n_heads query heads heads_host[], out f32 [n_heads][N][Skv][Sq] =
+ * softmax over the keys of scale q.k in fp32.  q_ld, k_ld multiples of 8, pointers 16-byte aligned; enqueued on `stream`. */
+int ace355_cross_attention_probs(const void* q_dev, const void* k_dev, float* out_dev, int N, int Sq, int Skv, int Hq, int Hkv,
+                                 int q_ld, int k_ld, const int32_t* heads_host, int n_heads, float scale, void* stream);
 /* Same with the key-padding mask of the condition encoders (create_4d_mask, base.py:117-124, prefix form): keys
  * j >= kv_len_host[n] are masked; a query with no valid key attends uniformly to ALL keys, as the reference's
  * finfo.min additive mask does. */
