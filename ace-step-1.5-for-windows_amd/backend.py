@@ -28,7 +28,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 
 import torch
 
-from .config import DitConfig, VaeConfig
+from .config import DitConfig, TextEncoderConfig, VaeConfig
 
 logger = logging.getLogger("ace355")
 
@@ -386,6 +386,34 @@ class NativeVaeMixin:
         return self._tiled_decode_inner(latents, chunk_size, overlap, offload_wav_to_cpu)
 
 
+class NativeTextEncoderMixin:
+    """Required host attributes: ``text_encoder`` (the loaded ``Qwen3Model``), ``device``; optional ``offload_to_cpu``."""
+
+    use_native_text_encoder: bool = False
+
+    def _init_native_text_encoder(self) -> bool:
+        """Swap ``self.text_encoder`` for ``modswap.NativeTextEncoderSwap`` (the PyTorch module stays inside as the per-call fallback;
+        its state_dict keys are unchanged).  Same policy as ``_init_native_dit``: refused under CPU offload or off a CUDA device, and any
+        failure is logged and leaves the PyTorch module in place.  Never raises."""
+        try:
+            if getattr(self, "offload_to_cpu", False) or not str(getattr(self, "device", "cpu")).startswith("cuda"):
+                logger.info("[native-text-encoder] CPU offload active or no GPU device; keeping the PyTorch path")
+                self.use_native_text_encoder = False
+                return False
+            if getattr(self, "text_encoder", None) is None:
+                raise RuntimeError("no text encoder loaded")
+            from .modswap import swap_in_text_encoder
+            wrapper = swap_in_text_encoder(self, self.device)
+            self.use_native_text_encoder = True
+            cfg = object.__getattribute__(wrapper, "_native").cfg
+            logger.info("[native-text-encoder] packed for gfx950 (%d layers, hidden %d)", cfg.num_hidden_layers, cfg.hidden_size)
+            return True
+        except Exception as exc:
+            logger.warning("[native-text-encoder] init failed (%s: %s); PyTorch path stays active", type(exc).__name__, exc)
+            self.use_native_text_encoder = False
+            return False
+
+
 class _ModelShell:
     """What the mixins read from ``self.model``: decoder state dict, null embedding, config."""
 
@@ -402,7 +430,7 @@ class _ModelShell:
         self.null_condition_emb = null_condition_emb
 
 
-class NativeHandler(NativeDitMixin, NativeVaeMixin):
+class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
     """Self-contained counterpart of ``AceStepHandler`` for the denoise + decode path.
 
     Differences from the reference handler are confined to what is out of scope: conditioning arrives pre-embedded
@@ -414,6 +442,7 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin):
     def __init__(self):
         self.model = None
         self.vae = None
+        self.text_encoder = None
         self.device = "cpu"
         self.dtype = torch.float32
         self.use_lora = False
@@ -436,9 +465,13 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin):
     def initialize_service(self, dit_config: DitConfig, decoder_state_dict: Dict[str, torch.Tensor],
                            null_condition_emb: torch.Tensor, vae_config: Optional[VaeConfig] = None,
                            vae_state_dict: Optional[Dict[str, torch.Tensor]] = None, device: str = "auto",
-                           use_native: bool = True, model_variant: str = "sft"):
+                           use_native: bool = True, model_variant: str = "sft",
+                           text_encoder_config: Optional[TextEncoderConfig] = None,
+                           text_encoder_state_dict: Optional[Dict[str, torch.Tensor]] = None):
         """Counterpart of ``initialize_service`` (handler/init_service_orchestrator.py:15-110) for pre-loaded weights.
         Re-entry is allowed (:30-31).  Returns ``(status_message, success)`` like the reference.
+        ``text_encoder_config`` + ``text_encoder_state_dict`` (``Qwen3Model.state_dict()`` keys): the handler also gets
+        ``text_encoder`` (a ``NativeTextEncoder``) and the reference's ``infer_text_embeddings`` / ``infer_lyric_embeddings`` work.
         ``model_variant`` names the checkpoint family (the reference reads it off the checkpoint directory,
         handler/init_service_catalog.py:69-73): "base" ignores explicit ``timesteps`` like its model, "sft" honours them,
         "turbo" selects the 8-step table sampler without CFG."""
@@ -461,10 +494,29 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin):
             ok = self._init_native_dit()
             if ok and vae_state_dict is not None:
                 ok = self._init_native_vae()
+            if ok and (text_encoder_config is not None or text_encoder_state_dict is not None):
+                if text_encoder_config is None or text_encoder_state_dict is None:
+                    raise ValueError("text_encoder_config and text_encoder_state_dict go together")
+                from .textenc import NativeTextEncoder
+                self.text_encoder = None
+                te = NativeTextEncoder(text_encoder_config, device, out_dtype=self.dtype)
+                te.load_state_dict(text_encoder_state_dict)
+                self.text_encoder, self.use_native_text_encoder = te, True
             return ("native backend ready" if ok else "native backend failed to initialise"), bool(ok)
         except Exception as exc:
             logger.exception("initialize_service failed")
             return f"Error: {exc!s}", False
+
+    # ------------------------------------------------------------------ text encoder (conditioning_embed.py:71-79)
+    def infer_text_embeddings(self, text_token_idss):
+        """Infer text-token embeddings via text encoder."""
+        with torch.inference_mode():
+            return self.text_encoder(input_ids=text_token_idss, lyric_attention_mask=None).last_hidden_state
+
+    def infer_lyric_embeddings(self, lyric_token_ids):
+        """Infer lyric-token embeddings via text encoder embedding table."""
+        with torch.inference_mode():
+            return self.text_encoder.embed_tokens(lyric_token_ids)
 
     # ------------------------------------------------------------------ LoRA (H/lora/lifecycle.py, H/lora/controls.py)
     def add_lora(self, lora_path: str, adapter_name: Optional[str] = None) -> str:

@@ -157,6 +157,70 @@ class CondConfig:
 
 
 @dataclass
+class TextEncoderConfig:
+    """Fields of transformers' ``Qwen3Config`` that ``Qwen3Model`` (the reference's text encoder, Qwen3-Embedding-0.6B,
+    init_service_loader.py:146-161) uses.  Defaults: the published 0.6B checkpoint."""
+
+    hidden_size: int = 1024
+    intermediate_size: int = 3072
+    num_hidden_layers: int = 28
+    num_attention_heads: int = 16
+    num_key_value_heads: int = 8
+    head_dim: int = 128
+    vocab_size: int = 151669
+    rms_norm_eps: float = 1e-6
+    rope_theta: float = 1000000.0
+
+    @classmethod
+    def from_reference(cls, cfg) -> "TextEncoderConfig":
+        """From a ``Qwen3Config``.  ``rope_theta`` is ``config.rope_theta`` up to transformers 4.57 (the reference pins < 4.58) and
+        ``config.rope_parameters["rope_theta"]`` from 5.x on.  Variants the native stack does not compute raise ``NotImplementedError``."""
+        if getattr(cfg, "use_sliding_window", False):
+            raise NotImplementedError("ace355: text encoder with use_sliding_window")
+        lt = getattr(cfg, "layer_types", None)
+        if lt is not None and any(t != "full_attention" for t in lt):
+            raise NotImplementedError(f"ace355: text encoder layer types {sorted(set(lt))}")
+        if getattr(cfg, "attention_bias", False):
+            raise NotImplementedError("ace355: text encoder with attention_bias")
+        rp = getattr(cfg, "rope_parameters", None) or {}
+        rs = getattr(cfg, "rope_scaling", None) or {}
+        for spec in (rp, rs):
+            kind = spec.get("rope_type", spec.get("type", "default")) if isinstance(spec, dict) else "default"
+            if kind not in (None, "default"):
+                raise NotImplementedError(f"ace355: text encoder rope type '{kind}'")
+        theta = getattr(cfg, "rope_theta", None)
+        if theta is None and isinstance(rp, dict):
+            theta = rp.get("rope_theta")
+        if theta is None:
+            raise ValueError("ace355: the text encoder config carries no rope_theta")
+        head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+        return cls(hidden_size=cfg.hidden_size, intermediate_size=cfg.intermediate_size, num_hidden_layers=cfg.num_hidden_layers,
+                   num_attention_heads=cfg.num_attention_heads, num_key_value_heads=cfg.num_key_value_heads, head_dim=head_dim,
+                   vocab_size=cfg.vocab_size, rms_norm_eps=float(cfg.rms_norm_eps), rope_theta=float(theta))
+
+    def weight_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """Names/shapes of ``Qwen3Model.state_dict()`` (the rotary buffer is not persistent)."""
+        D, Fh, hd = self.hidden_size, self.intermediate_size, self.head_dim
+        q, kv = self.num_attention_heads * hd, self.num_key_value_heads * hd
+        s: Dict[str, Tuple[int, ...]] = {"embed_tokens.weight": (self.vocab_size, D)}
+        for li in range(self.num_hidden_layers):
+            r = f"layers.{li}."
+            s[r + "self_attn.q_proj.weight"] = (q, D)
+            s[r + "self_attn.k_proj.weight"] = (kv, D)
+            s[r + "self_attn.v_proj.weight"] = (kv, D)
+            s[r + "self_attn.o_proj.weight"] = (D, q)
+            s[r + "self_attn.q_norm.weight"] = (hd,)
+            s[r + "self_attn.k_norm.weight"] = (hd,)
+            s[r + "mlp.gate_proj.weight"] = (Fh, D)
+            s[r + "mlp.up_proj.weight"] = (Fh, D)
+            s[r + "mlp.down_proj.weight"] = (D, Fh)
+            s[r + "input_layernorm.weight"] = (D,)
+            s[r + "post_attention_layernorm.weight"] = (D,)
+        s["norm.weight"] = (D,)
+        return s
+
+
+@dataclass
 class DetokConfig:
     """Fields of ``AceStepConfig`` used by ``AudioTokenDetokenizer`` (modeling_acestep_v15_base.py:862-994)."""
 

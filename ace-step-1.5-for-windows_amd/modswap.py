@@ -78,6 +78,53 @@ class NativeModuleSwap(torch.nn.Module):
             return getattr(super().__getattr__("_reference"), item)
 
 
+class _NativeEmbedTokens:
+    """``wrapper.embed_tokens``: callable like the reference's ``nn.Embedding``; the native gather first, the kept module's own
+    ``embed_tokens`` on ValueError / RuntimeError / NotImplementedError.  Other attributes (``weight``, ``num_embeddings`` ...) are the
+    reference embedding's."""
+
+    def __init__(self, swap: "NativeTextEncoderSwap"):
+        self._swap = swap
+
+    def __call__(self, ids):
+        swap = self._swap
+        try:
+            out = object.__getattribute__(swap, "_native").embed_tokens(ids)
+            swap.native_calls += 1
+            return out
+        except (ValueError, RuntimeError, NotImplementedError) as exc:
+            swap.native_failures += 1
+            if swap.native_failures <= 3:
+                logger.warning("[native-%s] embed_tokens %s: %s; running the PyTorch embedding for this call", swap._swap_name,
+                               type(exc).__name__, exc)
+            return swap._reference.embed_tokens(ids)
+
+    def __getattr__(self, item):
+        return getattr(self._swap._reference.embed_tokens, item)
+
+
+class NativeTextEncoderSwap(NativeModuleSwap):
+    """``NativeModuleSwap`` for the caption text encoder (``handler.text_encoder``, a ``Qwen3Model``): besides the forward,
+    ``embed_tokens`` (conditioning_embed.py:76-79) reaches the native gather - the base class's ``__getattr__`` would hand out the
+    reference's ``nn.Embedding`` - with that embedding as the fallback."""
+
+    @property
+    def embed_tokens(self):
+        return _NativeEmbedTokens(self)
+
+
+def swap_in_text_encoder(parent, device, attr: str = "text_encoder") -> NativeTextEncoderSwap:
+    """``parent.<attr> = NativeTextEncoderSwap(NativeTextEncoder.from_reference(parent.<attr>), parent.<attr>)``; output in the
+    module's own dtype.  Raises whatever ``from_reference`` raises (the caller logs and keeps the PyTorch module)."""
+    from .textenc import NativeTextEncoder
+    ref = getattr(parent, attr)
+    if isinstance(ref, NativeModuleSwap):  # re-entry
+        ref = ref._reference
+    wrapper = NativeTextEncoderSwap(NativeTextEncoder.from_reference(ref, device), ref, attr)
+    setattr(parent, attr, wrapper)
+    return wrapper
+
+
 def swap_in(parent: torch.nn.Module, attr: str, native_cls, device, out_dtype: torch.dtype = torch.float32) -> NativeModuleSwap:
     """``parent.<attr> = NativeModuleSwap(native_cls.from_reference(parent.<attr>), parent.<attr>)``; returns the wrapper.
     Raises whatever ``from_reference`` raises (caller logs and keeps the PyTorch module, like ``_init_native_dit``)."""

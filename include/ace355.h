@@ -364,6 +364,41 @@ int ace355_cond_encode(ace355_cond* h, const float* text_dev, const int32_t* tex
                        int Nref, int Tref, int B, float* enc_out_dev, int32_t* enc_len_out_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Caption text encoder: transformers' Qwen3Model as the reference loads it (Qwen3-Embedding-0.6B,
+ * init_service_loader.py:146-161) = embed_tokens + num_layers pre-norm decoder layers with causal GQA self-attention + final
+ * RMSNorm.  Replaces `self.text_encoder(input_ids=..., lyric_attention_mask=None).last_hidden_state` and
+ * `self.text_encoder.embed_tokens(ids)` of conditioning_embed.py:71-79.  No attention mask: right-padded ids run purely causally.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ace355_textenc ace355_textenc;
+
+#define ACE355_TEXTENC_MAX_TOKENS 65536 /* ids per encode / embed call (the reference sends at most 16 x 256 or 8 x 2048) */
+
+typedef struct ace355_textenc_config {
+    int32_t hidden_size;        /* 1024 */
+    int32_t intermediate_size;  /* 3072 */
+    int32_t num_layers;         /* 28 */
+    int32_t num_heads;          /* 16: must be 2 * num_kv_heads */
+    int32_t num_kv_heads;       /* 8 */
+    int32_t head_dim;           /* 128 (only value supported) */
+    int32_t vocab_size;         /* 151669 */
+    float rms_norm_eps;         /* 1e-6 */
+    float rope_theta;           /* 1e6 */
+} ace355_textenc_config;
+
+/* ACE355_ERR_UNSUPPORTED for head_dim != 128 or num_heads != 2 * num_kv_heads. */
+int ace355_textenc_create(const ace355_textenc_config* cfg, ace355_textenc** out);
+void ace355_textenc_destroy(ace355_textenc* h);
+/* name = a key of Qwen3Model.state_dict() ("embed_tokens.weight", "layers.3.self_attn.q_proj.weight", "norm.weight", ...);
+ * the rotary buffers are not tensors of this call.  Same contract as ace355_dit_load_tensor. */
+int ace355_textenc_load_tensor(ace355_textenc* h, const char* name, const void* data, int dtype, int64_t numel, int is_device);
+int ace355_textenc_finalize(ace355_textenc* h);
+/* ids host int32 [N, S] -> out dev bf16 [N, S, hidden] (last_hidden_state).  Ids outside [0, vocab) are refused with
+ * ACE355_ERR_INVALID before anything is launched.  The ids are copied before the call returns. */
+int ace355_textenc_encode(ace355_textenc* h, const int32_t* ids_host, int N, int S, void* out_dev, void* stream);
+/* ids host int32 [n] -> out dev bf16 [n, hidden] = rows of embed_tokens.weight (out 16-byte aligned); same id check. */
+int ace355_textenc_embed(ace355_textenc* h, const int32_t* ids_host, int64_t n, void* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Audio-token detokenizer of the LM-hint path: AudioTokenDetokenizer.forward,
  * base.py:886-994, as called by _decode_audio_codes_to_latents (handler/audio_codes.py:49-66) and by
  * prepare_condition (base.py:1646-1647).  Input = the quantizer's output for the 5 Hz audio codes, output =
