@@ -198,6 +198,11 @@ struct ace355_vae {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
     double flops = 0;
     long launches = 0;
+    // stage taps (ace355_vae_set_tap): [0] decoder, [1] encoder; stage -> (destination, capacity in bytes).  tap_stages is the stage
+    // list of the running call (empty when that half has no tap: nothing is looked up or copied), tap_next the next stage to come
+    std::map<int, std::pair<void*, size_t>> taps[2];
+    std::vector<ace355_vae_stage_info> tap_stages;
+    int tap_next = 0;
 };
 
 namespace {
@@ -528,14 +533,105 @@ static int episnake_on() {
     }
     return on;
 }
-static int run_res_unit(ace355_vae* h, const ResUnitW& R, bf16_t*& state, bf16_t*& tmp, int B, long L, int C, hipStream_t s,
-                        const SnakeP* out_snake = nullptr) {
+static bool unit_fused(int C) {
     static int fuse = -1;
     if (fuse < 0) {
         const char* e = getenv("ACE355_CONV_FUSE_RU");  // 0: two launches per unit everywhere (A/B runs)
         fuse = e ? atoi(e) : 1;
     }
-    if (fuse && C == 128) {
+    return fuse && C == 128;
+}
+
+// The stored tensors of a decode of T latent frames / an encode of T samples, in launch order (ace355.h: ACE355_VAE_STAGE_*).  The
+// decode / encode below walk the same sequence and tap_stage checks every stage's kind against this list as it comes.
+static void stage_push(std::vector<ace355_vae_stage_info>& v, int kind, int block, int unit, int channels, int flags, int src, int res,
+                       int dil, long rows) {
+    ace355_vae_stage_info si;
+    si.kind = kind; si.block = block; si.unit = unit; si.channels = channels; si.flags = flags; si.src = src; si.res = res;
+    si.dilation = dil; si.rows = rows;
+    v.push_back(si);
+}
+static void stage_push_unit(std::vector<ace355_vae_stage_info>& v, int block, int unit, int C, int dil, long rows, bool epi, bool out_snake) {
+    const int in = (int)v.size() - 1;
+    const int osn = out_snake ? ACE355_VAE_FLAG_OUT_SNAKE : 0;
+    if (unit_fused(C)) {
+        stage_push(v, ACE355_VAE_STAGE_UNIT, block, unit, C, ACE355_VAE_FLAG_FUSED | ACE355_VAE_FLAG_IN_SNAKE | osn, in, in, dil, rows);
+        return;
+    }
+    stage_push(v, ACE355_VAE_STAGE_UNIT_K7, block, unit, C, ACE355_VAE_FLAG_IN_SNAKE | (epi ? ACE355_VAE_FLAG_OUT_SNAKE : 0), in, -1, dil, rows);
+    stage_push(v, ACE355_VAE_STAGE_UNIT_K1, block, unit, C, (epi ? 0 : ACE355_VAE_FLAG_IN_SNAKE) | osn, in + 1, in, 1, rows);
+}
+static int stage_list(const ace355_vae* h, int enc, long T, std::vector<ace355_vae_stage_info>& v) {
+    v.clear();
+    const ace355_vae_config& c = h->cfg;
+    if (!enc) {
+        const bool epi = episnake_on() != 0 && !h->blocks.empty();
+        stage_push(v, ACE355_VAE_STAGE_INPUT, -1, -1, c.decoder_input_channels, 0, -1, -1, 1, T);
+        stage_push(v, ACE355_VAE_STAGE_CONV_IN, -1, -1, h->conv1.N, epi ? ACE355_VAE_FLAG_OUT_SNAKE : 0, 0, -1, 1, T);
+        long L = T;
+        for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
+            const BlockW& Bk = h->blocks[bi];
+            L = (L - 1) * Bk.stride - 2 * Bk.pad + 2 * Bk.stride;
+            stage_push(v, ACE355_VAE_STAGE_CONVT, (int)bi, -1, Bk.cout, epi ? 0 : ACE355_VAE_FLAG_IN_SNAKE, (int)v.size() - 1, -1, 1, L);
+            for (int j = 0; j < 3; ++j) stage_push_unit(v, (int)bi, j, Bk.cout, Bk.ru[j].dil, L, epi, epi && j == 2);
+        }
+        return 0;
+    }
+    const bool epi = episnake_on() != 0;
+    const int EH = 2 * c.decoder_input_channels;
+    stage_push(v, ACE355_VAE_STAGE_INPUT, -1, -1, 64, 0, -1, -1, 1, T);
+    stage_push(v, ACE355_VAE_STAGE_CONV_IN, -1, -1, EH, 0, 0, -1, 1, T);
+    long L = T;
+    for (size_t bi = 0; bi < h->e_blocks.size(); ++bi) {
+        const EncBlockW& Bk = h->e_blocks[bi];
+        for (int j = 0; j < 3; ++j) stage_push_unit(v, (int)bi, j, Bk.cin, Bk.ru[j].dil, L, epi, epi && j == 2);
+        L = (L + 2 * Bk.pad - 2 * Bk.stride) / Bk.stride + 1;
+        ACE_CHECK(L > 0, "vae stages: audio shorter than one latent frame");
+        stage_push(v, ACE355_VAE_STAGE_DOWN, (int)bi, -1, Bk.cout,
+                   (epi ? 0 : ACE355_VAE_FLAG_IN_SNAKE) | (epi && bi + 1 == h->e_blocks.size() ? ACE355_VAE_FLAG_OUT_SNAKE : 0), (int)v.size() - 1,
+                   -1, 1, L);
+    }
+    stage_push(v, ACE355_VAE_STAGE_HEAD, -1, -1, EH,
+               ACE355_VAE_FLAG_F32_NCL | ((!epi || h->e_blocks.empty()) ? ACE355_VAE_FLAG_IN_SNAKE : 0), (int)v.size() - 1, -1, 1, L);
+    return 0;
+}
+// The stage that was just launched: copy it out when it is tapped.  Without a tap on this half tap_stages is empty and nothing happens.
+static int tap_stage(ace355_vae* h, int enc, int kind, const void* p, int B, hipStream_t s) {
+    if (h->tap_stages.empty()) return 0;
+    const int k = h->tap_next++;
+    ACE_CHECK(k < (int)h->tap_stages.size() && h->tap_stages[k].kind == kind, "vae tap: the stage list and the launch sequence disagree");
+    auto it = h->taps[enc].find(k);
+    if (it == h->taps[enc].end()) return 0;
+    const ace355_vae_stage_info& si = h->tap_stages[k];
+    const size_t bytes = (size_t)B * si.rows * si.channels * ((si.flags & ACE355_VAE_FLAG_F32_NCL) ? 4 : 2);
+    ACE_CHECK(bytes <= it->second.second, "vae tap: the destination is smaller than the stage");
+    ACE_HIP(hipMemcpyAsync(it->second.first, p, bytes, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+// Start of a decode / encode: with a tap on this half the call must be one whole-sequence window over the whole batch
+static int tap_begin(ace355_vae* h, int enc, long T, bool single_window) {
+    h->tap_stages.clear();
+    h->tap_next = 0;
+    if (h->taps[enc].empty()) return 0;
+    if (!single_window) {
+        set_error("vae tap: the call splits into several windows under the activation budget; a tap needs one whole-sequence window");
+        return ACE355_ERR_STATE;
+    }
+    int rc = stage_list(h, enc, T, h->tap_stages);
+    if (rc) { h->tap_stages.clear(); return rc; }
+    ACE_CHECK(h->taps[enc].rbegin()->first < (int)h->tap_stages.size(), "vae tap: no such stage");
+    return 0;
+}
+static int tap_end(ace355_vae* h) {
+    const bool ok = h->tap_stages.empty() || h->tap_next == (int)h->tap_stages.size();
+    h->tap_stages.clear();
+    ACE_CHECK(ok, "vae tap: the stage list and the launch sequence disagree");
+    return 0;
+}
+
+static int run_res_unit(ace355_vae* h, const ResUnitW& R, bf16_t*& state, bf16_t*& tmp, int B, long L, int C, hipStream_t s,
+                        int enc, const SnakeP* out_snake = nullptr) {
+    if (unit_fused(C)) {
         // C = 128: one workgroup tile spans all channels, so the k = 1 conv runs on the k = 7 result inside the same kernel
         // (conv.hip, ConvArgs::w2).  The unit's output lands in `tmp` (neighbouring tiles still read `state`'s halo rows):
         // the two buffers trade places.
@@ -551,7 +647,7 @@ static int run_res_unit(ace355_vae* h, const ResUnitW& R, bf16_t*& state, bf16_t
         const int rcf = run_conv(h, f, s);
         if (rcf) return rcf;
         std::swap(state, tmp);
-        return 0;
+        return tap_stage(h, enc, ACE355_VAE_STAGE_UNIT, state, B, s);
     }
     ConvArgs a{};
     a.x = state; a.x_batch_stride = L * C; a.L_in = (int)L; a.Cin = C;
@@ -563,6 +659,7 @@ static int run_res_unit(ace355_vae* h, const ResUnitW& R, bf16_t*& state, bf16_t
     if (epi) a.osnake_a = R.s2.ea, a.osnake_b = R.s2.ib;   // tmp = snake2(conv_k7(...)): its only reader is the k = 1 conv below
     int rc = run_conv(h, a, s);
     if (rc) return rc;
+    if ((rc = tap_stage(h, enc, ACE355_VAE_STAGE_UNIT_K7, tmp, B, s))) return rc;
     a = ConvArgs{};
     a.x = tmp; a.x_batch_stride = L * C; a.L_in = (int)L; a.Cin = C;
     a.w = R.c2.w; a.bias = R.c2.bias;
@@ -572,7 +669,8 @@ static int run_res_unit(ace355_vae* h, const ResUnitW& R, bf16_t*& state, bf16_t
     a.y = state; a.y_batch_stride = L * C;
     a.B = B; a.M = (int)L; a.N = C; a.taps = 1; a.dil = 1; a.center = 0;
     a.y_shift = 0; a.y_valid = L * C; a.out_mode = 0;
-    return run_conv(h, a, s);
+    if ((rc = run_conv(h, a, s))) return rc;
+    return tap_stage(h, enc, ACE355_VAE_STAGE_UNIT_K1, state, B, s);
 }
 
 // Bytes of the three ping-pong activation buffers for a decode of `nb` items x `frames` latent frames (largest stage: L * C).
@@ -620,6 +718,7 @@ static int decode_window(ace355_vae* h, int b0, int nb, int T, int ws, int we, i
     const bool epi = episnake_on() != 0 && !h->blocks.empty();
     if (epi) a.osnake_a = h->blocks[0].s1.ea, a.osnake_b = h->blocks[0].s1.ib;   // conv1's only reader: block 0's Snake -> transposed conv
     if ((rc = run_conv(h, a, s))) return rc;
+    if ((rc = tap_stage(h, 0, ACE355_VAE_STAGE_CONV_IN, cur, nb, s))) return rc;
 
     for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
         const BlockW& Bk = h->blocks[bi];
@@ -635,8 +734,9 @@ static int decode_window(ace355_vae* h, int b0, int nb, int T, int ws, int we, i
         a.B = nb; a.M = (int)L + 1; a.N = Bk.ct.N; a.taps = 2; a.dil = 1; a.center = 1;
         a.y_shift = -(long)Bk.pad * Bk.cout; a.y_valid = Lout * Bk.cout; a.out_mode = 0;
         if ((rc = run_conv(h, a, s))) return rc;
+        if ((rc = tap_stage(h, 0, ACE355_VAE_STAGE_CONVT, nxt, nb, s))) return rc;
         for (int j = 0; j < 3; ++j)  // x + conv_k1(snake2(conv_k7_dil(snake1(x)))), in place on the block state (vae_model.py:79-87)
-            if ((rc = run_res_unit(h, Bk.ru[j], nxt, tmp, nb, Lout, Bk.cout, s, j == 2 ? next_snake : nullptr))) return rc;
+            if ((rc = run_res_unit(h, Bk.ru[j], nxt, tmp, nb, Lout, Bk.cout, s, 0, j == 2 ? next_snake : nullptr))) return rc;
         std::swap(cur, nxt);
         L = Lout;
     }
@@ -725,8 +825,10 @@ int ace355_vae_decode(ace355_vae* h, const float* z_dev, int B, int T, float* wa
         ACE_HIP(hipMalloc((void**)&h->zin, zel * 2 + 256));
         h->zin_elems = zel;
     }
-    int rc = launch_ncl_to_nlc(z_dev, h->zin, B, c.decoder_input_channels, T, s);
+    int rc = tap_begin(h, 0, T, nb == B && tc == T);
     if (rc) return rc;
+    if ((rc = launch_ncl_to_nlc(z_dev, h->zin, B, c.decoder_input_channels, T, s))) return rc;
+    if ((rc = tap_stage(h, 0, ACE355_VAE_STAGE_INPUT, h->zin, B, s))) return rc;
     h->last_plan[0] = nb; h->last_plan[1] = tc; h->last_plan[2] = ov;
     for (int b0 = 0; b0 < B; b0 += nb) {
         const int nbw = std::min(nb, B - b0);
@@ -736,7 +838,7 @@ int ace355_vae_decode(ace355_vae* h, const float* z_dev, int B, int T, float* wa
             if ((rc = decode_window(h, b0, nbw, T, ws, we, cs, ce, wav_out_dev, s))) return rc;
         }
     }
-    return ACE355_OK;
+    return tap_end(h);
 }
 
 int ace355_vae_set_decode_budget(ace355_vae* h, int64_t bytes, int overlap_frames) {
@@ -782,13 +884,15 @@ int ace355_vae_encode(ace355_vae* h, const float* audio_dev, const float* noise_
     long T = L;
     for (const EncBlockW& Bk : h->e_blocks) T = (T + 2 * Bk.pad - 2 * Bk.stride) / Bk.stride + 1;
     ACE_CHECK(T > 0, "vae_encode: audio shorter than one latent frame");
+    int rct = tap_begin(h, 1, L, nb == B);
+    if (rct) return rct;
     for (int b0 = 0; b0 < B; b0 += nb) {
         const int n = std::min(nb, B - b0);
         int rc = encode_group(h, audio_dev + (size_t)b0 * c.audio_channels * L, noise_dev ? noise_dev + (size_t)b0 * Z * T : nullptr, n, L,
                               latents_out_dev + (size_t)b0 * Z * T, (hipStream_t)stream);
         if (rc) return rc;
     }
-    return ACE355_OK;
+    return tap_end(h);
 }
 
 static int encode_group(ace355_vae* h, const float* audio_dev, const float* noise_dev, int B, int64_t L, float* latents_out_dev, hipStream_t s) {
@@ -830,6 +934,7 @@ static int encode_group(ace355_vae* h, const float* audio_dev, const float* nois
 
     bf16_t *cur = h->buf[0], *nxt = h->buf[1], *tmp = h->buf[2];
     int rc;
+    if ((rc = tap_stage(h, 1, ACE355_VAE_STAGE_INPUT, h->ain, B, s))) return rc;
     ConvArgs a{};
     // conv1 (k7 over the audio channels, vae_model.py:166) as one tap over the im2col'ed rows
     a.x = h->ain; a.x_batch_stride = L * 64; a.L_in = (int)L; a.Cin = 64;
@@ -838,12 +943,13 @@ static int encode_group(ace355_vae* h, const float* audio_dev, const float* nois
     a.B = B; a.M = (int)L; a.N = EH; a.taps = 1; a.dil = 1; a.center = 0;
     a.y_shift = 0; a.y_valid = L * EH; a.out_mode = 0;
     if ((rc = run_conv(h, a, s))) return rc;
+    if ((rc = tap_stage(h, 1, ACE355_VAE_STAGE_CONV_IN, cur, B, s))) return rc;
     long Lc = L;
     const bool epi = episnake_on() != 0;   // (run_res_unit: the Snakes with one reader move to their producers, as in the decoder)
     for (size_t bi = 0; bi < h->e_blocks.size(); ++bi) {
         const EncBlockW& Bk = h->e_blocks[bi];
         for (int j = 0; j < 3; ++j)   // (s1 is tiled `stride` times: its first cin entries are the per-channel parameters)
-            if ((rc = run_res_unit(h, Bk.ru[j], cur, tmp, B, Lc, Bk.cin, s, (epi && j == 2) ? &Bk.s1 : nullptr))) return rc;
+            if ((rc = run_res_unit(h, Bk.ru[j], cur, tmp, B, Lc, Bk.cin, s, 1, (epi && j == 2) ? &Bk.s1 : nullptr))) return rc;
         // snake -> Conv1d(k = 2s, stride s) as 2 taps over the shifted view x'[r][c'] = x_flat[(r*s - pad)*cin + c'] (vae_model.py:113-115)
         const long Lo = (Lc + 2 * Bk.pad - 2 * Bk.stride) / Bk.stride + 1;
         a = ConvArgs{};
@@ -856,6 +962,7 @@ static int encode_group(ace355_vae* h, const float* audio_dev, const float* nois
         a.B = B; a.M = (int)Lo; a.N = Bk.cout; a.taps = 2; a.dil = 1; a.center = 0;
         a.y_shift = 0; a.y_valid = Lo * Bk.cout; a.out_mode = 0;
         if ((rc = run_conv(h, a, s))) return rc;
+        if ((rc = tap_stage(h, 1, ACE355_VAE_STAGE_DOWN, nxt, B, s))) return rc;
         std::swap(cur, nxt);
         Lc = Lo;
     }
@@ -869,6 +976,7 @@ static int encode_group(ace355_vae* h, const float* audio_dev, const float* nois
     a.B = B; a.M = (int)Lc; a.N = EH; a.taps = 3; a.dil = 1; a.center = 1;
     a.out_mode = 1; a.n_real = EH;
     if ((rc = run_conv(h, a, s))) return rc;
+    if ((rc = tap_stage(h, 1, ACE355_VAE_STAGE_HEAD, h->e_head, B, s))) return rc;
     const long total = (long)B * Z * Lc;
     hipLaunchKernelGGL(gaussian_head_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->e_head, noise_dev, latents_out_dev, Z, Lc, total);
     ACE_LAUNCH_CHECK();
@@ -883,6 +991,34 @@ int ace355_vae_latent_frames(const ace355_vae* h, int64_t L) {
         if (T <= 0) return -1;
     }
     return (int)T;
+}
+
+int ace355_vae_num_stages(const ace355_vae* h, int encoder) {
+    if (!h || !h->finalized || (encoder && !h->has_encoder)) return -1;
+    std::vector<ace355_vae_stage_info> v;
+    if (stage_list(h, encoder != 0, encoder ? (long)h->hop * 4 : 4, v)) return -1;   // (the count does not depend on the length)
+    return (int)v.size();
+}
+
+int ace355_vae_get_stage(const ace355_vae* h, int encoder, int stage, int64_t T, ace355_vae_stage_info* out) {
+    ACE_CHECK(h && out && T > 0, "vae_get_stage: bad argument");
+    if (!h->finalized || (encoder && !h->has_encoder)) { set_error("vae_get_stage: not finalized, or no encoder.* tensors were loaded"); return ACE355_ERR_STATE; }
+    std::vector<ace355_vae_stage_info> v;
+    int rc = stage_list(h, encoder != 0, (long)T, v);
+    if (rc) return rc;
+    ACE_CHECK(stage >= 0 && stage < (int)v.size(), "vae_get_stage: no such stage");
+    *out = v[stage];
+    return ACE355_OK;
+}
+
+int ace355_vae_set_tap(ace355_vae* h, int encoder, int stage, void* dst_dev, int64_t capacity_bytes) {
+    ACE_CHECK(h, "vae_set_tap: null handle");
+    if (!h->finalized || (encoder && !h->has_encoder)) { set_error("vae_set_tap: not finalized, or no encoder.* tensors were loaded"); return ACE355_ERR_STATE; }
+    ACE_CHECK(stage >= 0 && stage < ace355_vae_num_stages(h, encoder), "vae_set_tap: no such stage");
+    ACE_CHECK(!dst_dev || capacity_bytes > 0, "vae_set_tap: capacity");
+    if (dst_dev) h->taps[encoder ? 1 : 0][stage] = {dst_dev, (size_t)capacity_bytes};
+    else h->taps[encoder ? 1 : 0].erase(stage);
+    return ACE355_OK;
 }
 
 int ace355_vae_set_profile(ace355_vae* h, int enable) {

@@ -73,6 +73,18 @@ class VaeConfigC(C.Structure):
     ]
 
 
+class VaeStageInfoC(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("block", C.c_int32), ("unit", C.c_int32), ("channels", C.c_int32), ("flags", C.c_int32),
+        ("src", C.c_int32), ("res", C.c_int32), ("dilation", C.c_int32), ("rows", C.c_int64),
+    ]
+
+
+# ACE355_VAE_STAGE_* / ACE355_VAE_FLAG_* of include/ace355.h
+VAE_STAGE_INPUT, VAE_STAGE_CONV_IN, VAE_STAGE_CONVT, VAE_STAGE_UNIT, VAE_STAGE_UNIT_K7, VAE_STAGE_UNIT_K1, VAE_STAGE_DOWN, VAE_STAGE_HEAD = range(8)
+VAE_FLAG_IN_SNAKE, VAE_FLAG_OUT_SNAKE, VAE_FLAG_FUSED, VAE_FLAG_F32_NCL = 1, 2, 4, 8
+
+
 class LoraTermC(C.Structure):
     _fields_ = [("name", C.c_char_p), ("A_dev", C.c_void_p), ("B_dev", C.c_void_p), ("rank", C.c_int32), ("scale", C.c_float)]
 
@@ -124,6 +136,9 @@ SIGNATURES = {
     "ace355_vae_latent_frames": (C.c_int, [C.c_void_p, C.c_int64]),
     "ace355_vae_set_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "ace355_vae_get_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "ace355_vae_num_stages": (C.c_int, [C.c_void_p, C.c_int]),
+    "ace355_vae_get_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.POINTER(VaeStageInfoC)]),
+    "ace355_vae_set_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     "ace355_cond_create": (C.c_int, [C.POINTER(CondConfigC), C.POINTER(C.c_void_p)]),
     "ace355_cond_destroy": (None, [C.c_void_p]),
     "ace355_cond_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int64, C.c_int]),

@@ -111,6 +111,37 @@ class NativeVae:
                                                      native.current_stream_ptr()), "vae_encode")
         return out
 
+    # ---- test / debug hooks: the stored activation of every stage of a decode or an encode (include/ace355.h, ACE355_VAE_STAGE_*)
+    def num_stages(self, encoder: bool = False) -> int:
+        n = int(self._lib.ace355_vae_num_stages(self._h, 1 if encoder else 0))
+        if n < 0:
+            raise RuntimeError("ace355: vae stages need a finalized handle (and encoder.* weights for the encoder)")
+        return n
+
+    def stage_info(self, encoder: bool, stage: int, T: int) -> Dict[str, int]:
+        """Stage ``stage`` of a decode of ``T`` latent frames (``encoder`` false) or an encode of ``T`` samples per item."""
+        si = native.VaeStageInfoC()
+        native.check(self._lib.ace355_vae_get_stage(self._h, 1 if encoder else 0, int(stage), int(T), C.byref(si)), "vae_get_stage")
+        return {name: int(getattr(si, name)) for name, _t in native.VaeStageInfoC._fields_}
+
+    def stages(self, encoder: bool, T: int):
+        return [self.stage_info(encoder, k, T) for k in range(self.num_stages(encoder))]
+
+    def stage_buffer(self, info: Dict[str, int], B: int) -> torch.Tensor:
+        """An empty tensor on this device with a stage's stored layout: bf16 [B, rows, channels] or f32 [B, channels, rows]."""
+        if info["flags"] & native.VAE_FLAG_F32_NCL:
+            return torch.empty(B, info["channels"], info["rows"], device=self.device, dtype=torch.float32)
+        return torch.empty(B, info["rows"], info["channels"], device=self.device, dtype=torch.bfloat16)
+
+    def set_tap(self, encoder: bool, stage: int, dst: torch.Tensor = None) -> None:
+        """Copy the stored activation of ``stage`` into ``dst`` (kept alive by the caller) on every following decode / encode;
+        ``dst`` None clears the tap.  A tapped call that would split into windows raises instead of tapping one window."""
+        if dst is not None and not (dst.is_cuda and dst.is_contiguous()):
+            raise ValueError("ace355: a tap destination must be a contiguous tensor on the device")
+        with torch.cuda.device(self.device):
+            native.check(self._lib.ace355_vae_set_tap(self._h, 1 if encoder else 0, int(stage), native.ptr(dst) if dst is not None else 0,
+                                                      dst.numel() * dst.element_size() if dst is not None else 0), "vae_set_tap")
+
     def set_profile(self, enable: bool) -> None:
         native.check(self._lib.ace355_vae_set_profile(self._h, 1 if enable else 0), "vae_set_profile")
 

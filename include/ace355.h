@@ -320,6 +320,47 @@ int ace355_vae_latent_frames(const ace355_vae* h, int64_t L);
 int ace355_vae_set_profile(ace355_vae* h, int enable);
 int ace355_vae_get_profile(ace355_vae* h, double* conv_ms, double* conv_flops, int64_t* conv_launches);
 
+/* Test / debug hooks: the stored activations of a decode or an encode, one STAGE per stored tensor, in launch order.
+ * Decoder: the bf16 NLC image of z; conv1; per block the transposed conv and its three residual units (the waveform is the call's own
+ * output).  Encoder: the im2col image of the audio; the first conv; per block the three units and the strided conv; the head (mean | scale,
+ * before the Gaussian arithmetic).  A residual unit that runs as ONE launch is one stage (UNIT); one that runs as two launches is two
+ * (UNIT_K7: the k = 7 result as stored for the k = 1 conv, UNIT_K1: the unit's output), so every stage but INPUT is the output of exactly
+ * one conv launch.  Which form a unit takes, and where the Snakes are applied, depends on the width and on the A/B switches of the process
+ * (ACE355_CONV_FUSE_RU, ACE355_VAE_EPISNAKE): the flags below say it, so a test never hard-codes the rounding points. */
+#define ACE355_VAE_STAGE_INPUT 0   /* decoder: bf16(z) as [T][64]; encoder: bf16 im2col rows [L][64], column k * audio_channels + c = audio[c][l + k - 3] */
+#define ACE355_VAE_STAGE_CONV_IN 1 /* decoder.conv1 / encoder.conv1 */
+#define ACE355_VAE_STAGE_CONVT 2   /* decoder.block.{block}.conv_t1 */
+#define ACE355_VAE_STAGE_UNIT 3    /* ...block.{block}.res_unit{unit + 1}, one launch */
+#define ACE355_VAE_STAGE_UNIT_K7 4 /* ...res_unit{unit + 1}.conv1 (+ snake2 when OUT_SNAKE) */
+#define ACE355_VAE_STAGE_UNIT_K1 5 /* ...res_unit{unit + 1}.conv2 + the unit's input */
+#define ACE355_VAE_STAGE_DOWN 6    /* encoder.block.{block}.conv1 (strided) */
+#define ACE355_VAE_STAGE_HEAD 7    /* encoder.conv2: f32 [2 * latent channels][T] per item */
+#define ACE355_VAE_FLAG_IN_SNAKE 1  /* the launch applies the layer's input Snake while staging its input (rounded to bf16 there) */
+#define ACE355_VAE_FLAG_OUT_SNAKE 2 /* the stored tensor already carries its (single) reader's Snake, applied to the fp32 sum */
+#define ACE355_VAE_FLAG_FUSED 4     /* residual unit in one launch: the k = 7 result meets snake2 unrounded and is never stored */
+#define ACE355_VAE_FLAG_F32_NCL 8   /* stored as f32 [channels][rows] per item; otherwise bf16 [rows][channels] */
+typedef struct ace355_vae_stage_info {
+    int32_t kind;      /* ACE355_VAE_STAGE_* */
+    int32_t block;     /* block index, -1 outside the blocks */
+    int32_t unit;      /* residual unit 0..2, -1 otherwise */
+    int32_t channels;
+    int32_t flags;     /* ACE355_VAE_FLAG_* */
+    int32_t src;       /* stage the launch reads (-1: the call's input) */
+    int32_t res;       /* stage added as the residual, -1: none */
+    int32_t dilation;  /* of the k = 7 conv of a unit, else 1 */
+    int64_t rows;      /* per item */
+} ace355_vae_stage_info;
+/* Number of stages of the decoder (encoder == 0) or the encoder; negative before finalize / without encoder weights. */
+int ace355_vae_num_stages(const ace355_vae* h, int encoder);
+/* Stage `stage` of a decode of T latent frames (encoder == 0) or an encode of T audio samples per item. */
+int ace355_vae_get_stage(const ace355_vae* h, int encoder, int stage, int64_t T, ace355_vae_stage_info* out);
+/* After stage `stage` of every following decode / encode, copy the stored activation of the whole batch ([B] x the stage's per-item
+ * layout) to dst_dev (hipMemcpyAsync on the call's stream); capacity_bytes is checked against the stage's size at each call
+ * (ACE355_ERR_INVALID).  dst_dev NULL clears the tap; several stages may be tapped at once.  A tapped call must run as ONE whole-sequence
+ * window over the whole batch: if the budget splits it, it returns ACE355_ERR_STATE and launches nothing.  Taps only observe: the conv
+ * launches and their arguments are those of an untapped call. */
+int ace355_vae_set_tap(ace355_vae* h, int encoder, int stage, void* dst_dev, int64_t capacity_bytes);
+
 /* ------------------------------------------------------------------------------------------
  * Condition encoder: AceStepConditionEncoder.forward, base.py:1509-1554
  * = text_projector + AceStepLyricEncoder (base.py:577-731) + AceStepTimbreEncoder (base.py:997-1178)

@@ -318,8 +318,13 @@ def test_apg_euler(lib, gpu_device, B, T):
 @pytest.mark.parametrize("B,L,Cin,Cout,taps,dil,snake,res", [
     (2, 300, 128, 128, 7, 1, True, False), (1, 517, 128, 128, 7, 9, True, False), (2, 200, 256, 256, 7, 3, True, False),
     (2, 300, 128, 128, 1, 1, True, True), (1, 40, 64, 2048, 7, 1, False, False), (1, 1000, 128, 2, 7, 1, True, False),
-    # >= 4096 workgroups at Cin >= 256: the launcher picks the 8-wave 256-row tile (ragged last tile: 66000 % 256 = 208)
-    (4, 66000, 256, 256, 7, 3, True, True)])
+    # wgs128 = 516 * 2 * 4 = 4128, but a residual keeps a launch off the 8-wave form (launch_conv: tall = !w2 && !res && ...): the 4-wave
+    # 128-row tile with a residual, ragged last tile (66000 % 128 = 80)
+    (4, 66000, 256, 256, 7, 3, True, True),
+    # its residual-free twin: wgs128 = 4128 >= 1400 -> the 8-wave conv_kernel<128, 256>, ragged last tile (66000 % 256 = 208)
+    (4, 66000, 256, 256, 7, 3, True, False),
+    # wgs128 = 235 * 4 * 8 = 7520 >= 1400 -> 8-wave, dilation 9 (54 halo rows), 30000 % 256 = 48; and without the Snake (plain staging)
+    (8, 30000, 512, 512, 7, 9, True, False), (8, 30000, 512, 512, 7, 9, False, False)])
 def test_conv1d_nlc(lib, gpu_device, B, L, Cin, Cout, taps, dil, snake, res):
     from oracle import oobleck as o_vae
     g = torch.Generator().manual_seed(L + Cin + taps + dil)
@@ -343,6 +348,19 @@ def test_conv1d_nlc(lib, gpu_device, B, L, Cin, Cout, taps, dil, snake, res):
                                _p(rd) if res else None, _p(y), B, L, Cin, Cout, taps, dil, None))
     # fast sin + bf16 rounding of snake(x) may flip a bf16 ulp on a few inputs: 6e-3 relative L2
     assert _rel(y.cpu(), ref) < 6e-3, _rel(y.cpu(), ref)
+    # ... and every element against the fp64 conv of the same operands (tests/_vae_layers.py): |got - ref| <= 2^-8 |ref| + tau absref,
+    # absref = the conv of the absolute values; tau = 2^-21 without a Snake, the measured Snake tau of the k = 7 / k = 1 stages with
+    import _vae_layers as vl
+    x64 = x.double().transpose(1, 2)
+    if snake:
+        x64 = vl.bf16r(vl.snake64(x64, alpha, beta))
+    ref64, absref = vl.linear_pair("conv", x64, w.double(), bias, dil=dil, res=r.double().transpose(1, 2) if res else None)
+    flags = vl.IN_SNAKE if snake else 0
+    tau = vl.tau_for(vl.UNIT_K7 if taps > 1 else vl.UNIT_K1, flags, taps * Cin)
+    chk = vl.compare(y.cpu().double().transpose(1, 2), ref64, absref, vl.U_BF16, tau, f"conv1d_nlc B={B} L={L} {Cin}->{Cout} k={taps} d={dil}")
+    print(f"conv1d_nlc B={B} L={L} {Cin}->{Cout} k={taps} dil={dil} snake={snake} res={res}: measured excess {chk['excess']:.3e} absref, "
+          f"tau {tau:.3e} (ceiling 1/(4K) {vl.tau_ceiling(taps * Cin):.3e})")
+    assert chk["n_over"] == 0, chk["report"]
 
 
 def test_gemm_tile_forms_give_the_same_bits(gpu_device, tmp_path):
