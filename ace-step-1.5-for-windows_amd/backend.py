@@ -68,8 +68,8 @@ class NativeDitMixin:
             return False
 
     def _native_adapter_terms(self):
-        """The LoRA terms the native DiT should carry now.  Default: the PEFT-wrapped ``self.model.decoder`` (the reference loads
-        adapters there after ``initialize_service``, H/lora/lifecycle.py:164-283), read by duck typing.  Hosts with a registry of their
+        """The LoRA / LoKr terms the native DiT should carry now.  Default: the PEFT-wrapped ``self.model.decoder`` and its LyCORIS
+        network (the reference loads adapters there after ``initialize_service``, H/lora/lifecycle.py:164-283), read by duck typing.  Hosts with a registry of their
         own override this (``NativeHandler``)."""
         from .lora import terms_from_decoder
         return terms_from_decoder(self.model.decoder, getattr(self.native_dit, "cfg", None))
@@ -77,7 +77,7 @@ class NativeDitMixin:
     def _sync_native_adapters(self) -> None:
         """Bring the native DiT's merged adapters in line with the host's: nothing at all while ``use_lora`` is off and nothing is
         applied; a re-merge when the terms' fingerprint (names, scales, tensors, in-place versions) changed; the base back when
-        ``use_lora`` turned off.  ``UnsupportedAdapter`` (LoKr, DoRA, ...) propagates."""
+        ``use_lora`` turned off.  ``UnsupportedAdapter`` (DoRA, Tucker LoKr, ...) propagates."""
         applied = getattr(self, "_native_adapter_key", None)
         if not getattr(self, "use_lora", False):
             if applied is not None:
@@ -459,6 +459,7 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
         self._lora_registry: Dict[str, list] = {}
         self._active_loras: Dict[str, float] = {}
         self._lora_active_adapter: Optional[str] = None
+        self._adapter_type: Optional[str] = None   # "lora" | "lokr" (lifecycle.py:236, 242)
         from .align import DEFAULT_LAYERS_HEADS
         self.custom_layers_config = {k: list(v) for k, v in DEFAULT_LAYERS_HEADS.items()}   # acestep/handler.py:129
 
@@ -520,9 +521,10 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
 
     # ------------------------------------------------------------------ LoRA (H/lora/lifecycle.py, H/lora/controls.py)
     def add_lora(self, lora_path: str, adapter_name: Optional[str] = None) -> str:
-        """Load the PEFT LoRA directory ``lora_path`` as ``adapter_name`` (default: the directory's name) and make it the active adapter
-        (lifecycle.py:164-286).  The native DiT merges it at the next request (``_sync_native_adapters``)."""
+        """Load the PEFT LoRA directory or LoKr artefact ``lora_path`` as ``adapter_name`` (default: the path's last component) and make
+        it the active adapter (lifecycle.py:164-286).  The native DiT merges it at the next request (``_sync_native_adapters``)."""
         import os
+        from .lokr import read_lokr_adapter, resolve_lokr_weights_path
         from .lora import read_peft_adapter
         if self.model is None:
             return "❌ Model not initialized. Please initialize service first."
@@ -539,13 +541,25 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
             (os.path.basename(lora_path.rstrip(os.sep)) or "default")
         if name in self._lora_registry:
             return f"❌ Adapter name already in use: {name}. Use a different name or remove it first."
+        lokr_path = resolve_lokr_weights_path(lora_path)
+        if self._lora_registry and lokr_path is not None and self._adapter_type != "lokr":   # lifecycle.py:244-246
+            return "❌ LoKr cannot be added as a second adapter when PEFT is already loaded."
+        if self._lora_registry and self._adapter_type == "lokr":
+            return "❌ A LoKr adapter is loaded; unload it before loading another adapter."
         try:
-            terms = read_peft_adapter(lora_path, self.model.config)
             dev = torch.device(self.device)
-            self._lora_registry[name] = [t._replace(A=t.A.to(dev, self.dtype), B=t.B.to(dev, self.dtype)) for t in terms]
+            if lokr_path is not None:
+                logger.info("Loading LoKr adapter from %s as '%s'", lokr_path, name)
+                terms = read_lokr_adapter(lokr_path, self.model.config)
+                self._lora_registry[name] = [t._replace(**{f: getattr(t, f).to(dev, self.dtype) for f in t._fields[1:7]
+                                                           if getattr(t, f) is not None}) for t in terms]
+            else:
+                terms = read_peft_adapter(lora_path, self.model.config)
+                self._lora_registry[name] = [t._replace(A=t.A.to(dev, self.dtype), B=t.B.to(dev, self.dtype)) for t in terms]
         except Exception as exc:
             logger.exception("Failed to load LoRA adapter")
             return f"❌ Failed to load LoRA: {exc!s}"
+        self._adapter_type = "lokr" if lokr_path is not None else "lora"
         self.lora_loaded = True
         self.use_lora = True
         self._active_loras[name] = 1.0
@@ -554,7 +568,12 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
 
     def load_lora(self, lora_path: str) -> str:
         """Single-adapter form of ``add_lora`` (lifecycle.py:289-295)."""
-        return self.add_lora(lora_path, adapter_name=None)
+        from .lokr import resolve_lokr_weights_path
+        lokr_path = resolve_lokr_weights_path(lora_path.strip()) if isinstance(lora_path, str) else None
+        message = self.add_lora(lora_path, adapter_name=None)
+        if lokr_path is not None and message.startswith("✅"):
+            return f"✅ LoKr loaded from {lokr_path}"
+        return message
 
     def remove_lora(self, adapter_name: str) -> str:
         if not self._lora_registry:
@@ -580,6 +599,7 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
         self._lora_active_adapter = None
         self.lora_loaded = False
         self.use_lora = False
+        self._adapter_type = None
         self.lora_scale = 1.0
         return "✅ LoRA unloaded, using base model"
 
@@ -588,7 +608,7 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
         if use_lora and not self.lora_loaded:
             return "❌ No LoRA adapter loaded. Please load a LoRA first."
         self.use_lora = bool(use_lora)
-        return f"✅ LoRA {'enabled' if use_lora else 'disabled'}"
+        return f"✅ {self._adapter_label()} {'enabled' if use_lora else 'disabled'}"
 
     def set_lora_scale(self, adapter_name_or_scale, scale: Optional[float] = None) -> str:
         """Scale of one adapter, clamped to [0, 1] (controls.py:83-113): ``set_lora_scale(0.5)`` for the active adapter or
@@ -614,9 +634,10 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
             return f"❌ Adapter '{name}' not in loaded adapters: {list(self._lora_registry.keys())}"
         self._active_loras[name] = value
         self.lora_scale = value
+        label = self._adapter_label()   # (controls.py:115-127)
         if not self.use_lora:
-            return f"✅ LoRA scale ({name}): {value:.2f} (LoRA disabled)"
-        return f"✅ LoRA scale ({name}): {value:.2f}"
+            return f"✅ {label} scale ({name}): {value:.2f} ({label} disabled)"
+        return f"✅ {label} scale ({name}): {value:.2f}"
 
     def set_active_lora_adapter(self, adapter_name: str) -> str:
         """Only the active adapter applies (PEFT's set_adapter; controls.py:193-205)."""
@@ -625,9 +646,13 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
         self._lora_active_adapter = adapter_name
         return f"✅ Active LoRA adapter: {adapter_name}"
 
+    def _adapter_label(self) -> str:
+        return "LoKr" if self._adapter_type == "lokr" else "LoRA"   # (controls.py:78)
+
     def get_lora_status(self) -> Dict[str, Any]:
         return {"loaded": self.lora_loaded, "active": self.use_lora, "scale": self.lora_scale, "scales": dict(self._active_loras),
-                "active_adapter": self._lora_active_adapter, "adapters": list(self._lora_registry.keys())}
+                "active_adapter": self._lora_active_adapter, "adapters": list(self._lora_registry.keys()),
+                "adapter_type": self._adapter_type, "label": self._adapter_label()}
 
     def _native_adapter_terms(self):
         """The active adapter of this handler's registry, at its scale."""

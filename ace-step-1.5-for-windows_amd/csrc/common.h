@@ -363,6 +363,38 @@ int launch_lora_merge(const LoraTargetDev* targets_dev, int n_targets, int total
 int launch_lora_read(const bf16_t* w, long ld, int mode, long row0, int p0, long rows, long cols, void* dst, int dst_is_bf16,
                      hipStream_t s);
 
+// LoKr merge (lokr.hip, ace355_dit_set_adapters_mixed): W' = bf16_rne(float(W0) + sum_j s_j (W1_j kron W2_j)).  A pre-pass writes the
+// fp32 product a @ b of every decomposed factor into a scratch table of the handle; one merge launch then covers the tiles of every
+// Kronecker target (LoraTargetDev, as the LoRA merge: nterms 0 copies the pristine rows back).
+constexpr int LOKR_TILE_ROWS = 64, LOKR_TILE_COLS = 128;
+// LDS floats of the merge kernel: the W1 and W2 sub-blocks of one (tile, term).  With a = min(out_k, 64), b = min(in_n, 128) a tile
+// meets at most (63 / a + 2)(127 / b + 2) entries of W1 (exactly 64 / a resp. 128 / b where a | 64 resp. b | 128, tiles being aligned)
+// and a x b of W2 (row pitch lokr_w2_pitch(b)): the sum peaks at a = b = 1 (a dense W1) with 64 x 128 + 1 and at a = 64, b = 128 with
+// 4 + 64 x 132.  A launch asks for the largest need among its terms (lokr_lds_floats), so the usual splits leave room for more
+// workgroups per CU.
+constexpr int LOKR_LDS_FLOATS = 64 * 132 + 64;
+// LDS row pitch of a staged W2 block of nn columns: a multiple of 4 floats where the 16-byte paths need it, odd otherwise
+__host__ __device__ __forceinline__ int lokr_w2_pitch(int nn) { return nn % 4 == 0 ? nn + 4 : nn | 1; }
+struct KronFactorDev {   // one decomposed factor: dst [rows, cols] fp32 = a [rows, rank] @ b [rank, cols]
+    const bf16_t* a;
+    const bf16_t* b;
+    float* dst;
+    int rows, cols, rank;
+    int tile0, tiles_n;  // first tile of this factor in the pre-pass launch, column tiles per row tile
+};
+struct KronTermDev {
+    const void* w1;      // [out_l, in_m]: bf16 as given (w1_f32 0) or the fp32 product in the scratch table (w1_f32 1)
+    const void* w2;      // [out_k, in_n], likewise
+    int w1_f32, w2_f32;
+    int out_l, out_k, in_m, in_n;
+    float scale;
+    int wide;            // in_n % 8 == 0, in_n <= LOKR_TILE_COLS and w2 16-byte aligned: W2 is staged and read 16 bytes at a time
+};
+int lokr_lds_floats(int out_k, int in_n);   // worst case over the tiles of a term (<= LOKR_LDS_FLOATS for every split)
+int launch_lokr_factors(const KronFactorDev* jobs_dev, int n_jobs, int total_tiles, hipStream_t s);
+int launch_lokr_merge(const LoraTargetDev* targets_dev, int n_targets, int total_tiles, const KronTermDev* terms_dev, int lds_floats,
+                      hipStream_t s);
+
 // Cross-attention probabilities (xattn_probs.hip, ace355_dit_cross_attention_maps / ace355_cross_attention_probs): for query heads
 // heads[p], out[p][n][j][s] = softmax_j(scale q[n][s] . k[n][j]) in fp32, j < Skv, s < Sq
 constexpr int XATTN_MAX_HEADS = 64;

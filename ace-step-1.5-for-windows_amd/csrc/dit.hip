@@ -178,6 +178,8 @@ struct ace355_dit {
         long gen_kv = 0, gen_o = 0;     // bumped by a call that rewrites a cross-attention k / v resp. o projection (condition slots)
         void* tab = nullptr;            // device copy of the launch's target + term tables
         size_t tab_bytes = 0;
+        float* kscratch = nullptr;      // fp32 products of the decomposed Kronecker factors of the last call (lokr.hip)
+        size_t kscratch_floats = 0;
     } lora;
 
     // profiling
@@ -1172,6 +1174,7 @@ void ace355_dit_destroy(ace355_dit* h) {
     if (h->stage) hipFree(h->stage);
     lora_free_pristine(h);
     if (h->lora.tab) hipFree(h->lora.tab);
+    if (h->lora.kscratch) hipFree(h->lora.kscratch);
     if (h->rope_cos) hipFree(h->rope_cos);
     if (h->rope_sin) hipFree(h->rope_sin);
     if (h->enc_bf) hipFree(h->enc_bf);
@@ -1765,9 +1768,11 @@ int ace355_dit_graph_stats(ace355_dit* h, int64_t* captures, int64_t* replays) {
     return ACE355_OK;
 }
 
-int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_terms, void* stream) {
+// ace355_dit_set_adapters (n_kron 0: its launches are those of the LoRA merge alone) and ace355_dit_set_adapters_mixed
+static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n_terms, const ace355_kron_term* kron, int n_kron, void* stream) {
     ACE_CHECK(h, "set_adapters: null handle");
     ACE_CHECK(n_terms >= 0 && (n_terms == 0 || terms), "set_adapters: terms");
+    ACE_CHECK(n_kron >= 0 && (n_kron == 0 || kron), "set_adapters: kron terms");
     if (!h->finalized) { set_error("set_adapters: call ace355_dit_finalize first"); return ACE355_ERR_STATE; }
     if (h->precision != ACE355_PRECISION_BF16 || h->weights_fp8wo) {   // H/lora/lifecycle.py:173-178
         set_error(std::string("set_adapters: LoRA loading is not supported on quantized models. Current precision: ") +
@@ -1778,29 +1783,56 @@ int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_
     // the terms per target, in call order; scale 0 drops a term
     std::vector<std::string> order;
     std::vector<std::vector<const ace355_lora_term*>> by;
+    std::vector<std::vector<const ace355_kron_term*>> kby;
     std::vector<Dest> dests;
     auto index_of = [&](const std::string& n) { for (size_t i = 0; i < order.size(); ++i) if (order[i] == n) return (int)i; return -1; };
+    auto not_a_target = [&](const char* name) {
+        set_error(std::string("set_adapters: '") + name + "' is not a LoRA target (layers.{i}.{self_attn,cross_attn}.{q,k,v,o}_proj.weight, "
+                  "layers.{i}.mlp.{gate,up,down}_proj.weight)");
+        return ACE355_ERR_INVALID;
+    };
+    std::set<std::string> lora_named;
     for (int i = 0; i < n_terms; ++i) {
         const ace355_lora_term& t = terms[i];
         ACE_CHECK(t.name && t.A_dev && t.B_dev, "set_adapters: null name / A / B");
         Dest d;
-        if (!lora_target(h, t.name, &d)) {
-            set_error(std::string("set_adapters: '") + t.name + "' is not a LoRA target (layers.{i}.{self_attn,cross_attn}.{q,k,v,o}_proj.weight, "
-                      "layers.{i}.mlp.{gate,up,down}_proj.weight)");
-            return ACE355_ERR_INVALID;
-        }
+        if (!lora_target(h, t.name, &d)) return not_a_target(t.name);
         ACE_CHECK(t.rank >= 1 && std::isfinite(t.scale), "set_adapters: rank must be >= 1 and scale finite");
+        if (n_kron) lora_named.insert(t.name);
         if (t.scale == 0.f) continue;
         int k = index_of(t.name);
-        if (k < 0) { order.push_back(t.name); by.emplace_back(); dests.push_back(d); k = (int)order.size() - 1; }
+        if (k < 0) { order.push_back(t.name); by.emplace_back(); kby.emplace_back(); dests.push_back(d); k = (int)order.size() - 1; }
         by[k].push_back(&t);
+    }
+    for (int i = 0; i < n_kron; ++i) {
+        const ace355_kron_term& t = kron[i];
+        ACE_CHECK(t.name, "set_adapters: null name in a Kronecker term");
+        Dest d;
+        if (!lora_target(h, t.name, &d)) return not_a_target(t.name);
+        // exactly one of {w} / {w_a, w_b} per factor; r = 0 for a full factor, >= 1 for a decomposed one
+        const bool f1 = t.w1_dev && !t.w1a_dev && !t.w1b_dev && t.r1 == 0, d1 = !t.w1_dev && t.w1a_dev && t.w1b_dev && t.r1 >= 1;
+        const bool f2 = t.w2_dev && !t.w2a_dev && !t.w2b_dev && t.r2 == 0, d2 = !t.w2_dev && t.w2a_dev && t.w2b_dev && t.r2 >= 1;
+        ACE_CHECK(t.r1 >= 0 && t.r2 >= 0, "set_adapters: a Kronecker factor's rank must be >= 0");
+        ACE_CHECK((f1 || d1) && (f2 || d2), "set_adapters: each Kronecker factor needs exactly one of {w} (rank 0) / {w_a, w_b} (rank >= 1)");
+        ACE_CHECK(t.out_l >= 1 && t.out_k >= 1 && t.in_m >= 1 && t.in_n >= 1 && (long)t.out_l * t.out_k == d.rows &&
+                  (long)t.in_m * t.in_n == d.cols, "set_adapters: out_l x out_k / in_m x in_n do not give the target's [out, in]");
+        ACE_CHECK(std::isfinite(t.scale), "set_adapters: scale must be finite");
+        ACE_CHECK(lokr_lds_floats(t.out_k, t.in_n) <= LOKR_LDS_FLOATS, "set_adapters: Kronecker split exceeds the merge tile's LDS");
+        if (lora_named.count(t.name)) {   // the reference never has both (H/lora/lifecycle.py:244-246)
+            set_error(std::string("set_adapters: '") + t.name + "' is named by a LoRA term and by a Kronecker term");
+            return ACE355_ERR_INVALID;
+        }
+        if (t.scale == 0.f) continue;
+        int k = index_of(t.name);
+        if (k < 0) { order.push_back(t.name); by.emplace_back(); kby.emplace_back(); dests.push_back(d); k = (int)order.size() - 1; }
+        kby[k].push_back(&t);
     }
     const size_t n_merge = order.size();
     for (const std::string& n : h->lora.applied) {   // merged before, no term now: its rows go back to the base
         if (index_of(n) >= 0) continue;
         Dest d;
         lora_target(h, n, &d);
-        order.push_back(n); by.emplace_back(); dests.push_back(d);
+        order.push_back(n); by.emplace_back(); kby.emplace_back(); dests.push_back(d);
     }
     if (order.empty()) return ACE355_OK;
     ACE_HIP(hipStreamSynchronize(s));   // (the previous call's merge may still read the tables)
@@ -1816,28 +1848,81 @@ int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_
         h->lora.pristine.push_back({(bf16_t*)d.dst, (bf16_t*)q});
         ACE_HIP(hipMemcpyAsync(q, d.dst, n * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
     }
-    std::vector<LoraTargetDev> tg;
+    // the scratch table of the decomposed Kronecker factors' fp32 products
+    size_t scratch_floats = 0;
+    bool any_kron = false;
+    for (size_t i = 0; i < n_merge; ++i)
+        for (const ace355_kron_term* t : kby[i]) {
+            any_kron = true;
+            if (t->r1) scratch_floats += ((size_t)t->out_l * t->in_m + 3) / 4 * 4;
+            if (t->r2) scratch_floats += ((size_t)t->out_k * t->in_n + 3) / 4 * 4;
+        }
+    if (scratch_floats > h->lora.kscratch_floats) {
+        if (h->lora.kscratch) hipFree(h->lora.kscratch);
+        h->lora.kscratch = nullptr; h->lora.kscratch_floats = 0;
+        ACE_HIP(hipMalloc((void**)&h->lora.kscratch, scratch_floats * sizeof(float)));
+        h->lora.kscratch_floats = scratch_floats;
+    }
+    // LoRA targets (and, in a call without Kronecker terms, the restored ones) go to the LoRA launch, Kronecker targets (and, beside
+    // them, the restored ones) to the LoKr launch
+    std::vector<LoraTargetDev> tg, ktg;
     std::vector<LoraTermDev> tm;
-    int tiles = 0;
+    std::vector<KronTermDev> ktm;
+    std::vector<KronFactorDev> jobs;
+    int tiles = 0, ktiles = 0, jtiles = 0, klds = 4;
+    size_t scratch_at = 0;
     bool kv = false, o = false;
+    auto factor = [&](const void* a, const void* b, int rows, int cols, int rank) -> const void* {
+        KronFactorDev f{};
+        f.a = (const bf16_t*)a; f.b = (const bf16_t*)b; f.dst = h->lora.kscratch + scratch_at;
+        f.rows = rows; f.cols = cols; f.rank = rank;
+        f.tiles_n = (cols + 127) / 128; f.tile0 = jtiles;
+        jtiles += (rows + 63) / 64 * f.tiles_n;
+        scratch_at += ((size_t)rows * cols + 3) / 4 * 4;
+        jobs.push_back(f);
+        return f.dst;
+    };
     for (size_t i = 0; i < order.size(); ++i) {
         const Dest& d = dests[i];
         ACE_CHECK(d.cols % 8 == 0, "set_adapters: target columns must be a multiple of 8");
+        const bool to_kron = !kby[i].empty() || (by[i].empty() && any_kron);
         LoraTargetDev x{};
         x.dst = (bf16_t*)d.dst; x.src = pristine_of(d.dst); x.ld = d.dst_ld; x.row0 = d.dst_row0; x.mode = d.mode; x.p0 = d.p0;
         x.rows = (int)d.rows; x.cols = (int)d.cols;
-        x.tiles_n = (x.cols + LORA_TILE_COLS - 1) / LORA_TILE_COLS;
-        x.tile0 = tiles;
-        tiles += (x.rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS * x.tiles_n;
-        x.term0 = (int)tm.size();
-        for (const ace355_lora_term* t : by[i]) tm.push_back(LoraTermDev{(const bf16_t*)t->A_dev, (const bf16_t*)t->B_dev, t->rank, t->scale});
-        x.nterms = (int)tm.size() - x.term0;
-        tg.push_back(x);
+        if (to_kron) {
+            x.tiles_n = (x.cols + LOKR_TILE_COLS - 1) / LOKR_TILE_COLS;
+            x.tile0 = ktiles;
+            ktiles += (x.rows + LOKR_TILE_ROWS - 1) / LOKR_TILE_ROWS * x.tiles_n;
+            x.term0 = (int)ktm.size();
+            for (const ace355_kron_term* t : kby[i]) {
+                KronTermDev u{};
+                u.w1 = t->r1 ? factor(t->w1a_dev, t->w1b_dev, t->out_l, t->in_m, t->r1) : t->w1_dev; u.w1_f32 = t->r1 ? 1 : 0;
+                u.w2 = t->r2 ? factor(t->w2a_dev, t->w2b_dev, t->out_k, t->in_n, t->r2) : t->w2_dev; u.w2_f32 = t->r2 ? 1 : 0;
+                u.out_l = t->out_l; u.out_k = t->out_k; u.in_m = t->in_m; u.in_n = t->in_n; u.scale = t->scale;
+                u.wide = t->in_n % 8 == 0 && t->in_n <= LOKR_TILE_COLS && (u.w2_f32 || (uintptr_t)u.w2 % 16 == 0);
+                klds = std::max(klds, lokr_lds_floats(t->out_k, t->in_n));
+                ktm.push_back(u);
+            }
+            x.nterms = (int)ktm.size() - x.term0;
+            ktg.push_back(x);
+        } else {
+            x.tiles_n = (x.cols + LORA_TILE_COLS - 1) / LORA_TILE_COLS;
+            x.tile0 = tiles;
+            tiles += (x.rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS * x.tiles_n;
+            x.term0 = (int)tm.size();
+            for (const ace355_lora_term* t : by[i]) tm.push_back(LoraTermDev{(const bf16_t*)t->A_dev, (const bf16_t*)t->B_dev, t->rank, t->scale});
+            x.nterms = (int)tm.size() - x.term0;
+            tg.push_back(x);
+        }
         const std::string& n = order[i];
         kv = kv || n.find(".cross_attn.k_proj.") != std::string::npos || n.find(".cross_attn.v_proj.") != std::string::npos;
         o = o || n.find(".cross_attn.o_proj.") != std::string::npos;
     }
-    const size_t tg_bytes = (tg.size() * sizeof(LoraTargetDev) + 255) / 256 * 256, bytes = tg_bytes + std::max<size_t>(tm.size(), 1) * sizeof(LoraTermDev);
+    auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t tg_bytes = pad(tg.size() * sizeof(LoraTargetDev)), tm_bytes = std::max<size_t>(tm.size(), 1) * sizeof(LoraTermDev);
+    const size_t ktg_at = any_kron ? pad(tg_bytes + tm_bytes) : tg_bytes + tm_bytes, ktm_at = ktg_at + pad(ktg.size() * sizeof(LoraTargetDev));
+    const size_t job_at = ktm_at + pad(ktm.size() * sizeof(KronTermDev));
+    const size_t bytes = any_kron ? job_at + std::max<size_t>(jobs.size(), 1) * sizeof(KronFactorDev) : tg_bytes + tm_bytes;
     if (bytes > h->lora.tab_bytes) {
         if (h->lora.tab) hipFree(h->lora.tab);
         h->lora.tab = nullptr; h->lora.tab_bytes = 0;
@@ -1845,11 +1930,18 @@ int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_
         h->lora.tab_bytes = bytes;
     }
     std::vector<char> host(bytes, 0);
-    memcpy(host.data(), tg.data(), tg.size() * sizeof(LoraTargetDev));
+    if (!tg.empty()) memcpy(host.data(), tg.data(), tg.size() * sizeof(LoraTargetDev));
     if (!tm.empty()) memcpy(host.data() + tg_bytes, tm.data(), tm.size() * sizeof(LoraTermDev));
+    if (!ktg.empty()) memcpy(host.data() + ktg_at, ktg.data(), ktg.size() * sizeof(LoraTargetDev));
+    if (!ktm.empty()) memcpy(host.data() + ktm_at, ktm.data(), ktm.size() * sizeof(KronTermDev));
+    if (!jobs.empty()) memcpy(host.data() + job_at, jobs.data(), jobs.size() * sizeof(KronFactorDev));
     ACE_HIP(hipMemcpyAsync(h->lora.tab, host.data(), bytes, hipMemcpyHostToDevice, s));
-    int rc = launch_lora_merge((const LoraTargetDev*)h->lora.tab, (int)tg.size(), tiles,
-                               (const LoraTermDev*)((char*)h->lora.tab + tg_bytes), s);
+    char* tab = (char*)h->lora.tab;
+    int rc = launch_lora_merge((const LoraTargetDev*)tab, (int)tg.size(), tiles, (const LoraTermDev*)(tab + tg_bytes), s);
+    if (!rc && any_kron) {
+        rc = launch_lokr_factors((const KronFactorDev*)(tab + job_at), (int)jobs.size(), jtiles, s);
+        if (!rc) rc = launch_lokr_merge((const LoraTargetDev*)(tab + ktg_at), (int)ktg.size(), ktiles, (const KronTermDev*)(tab + ktm_at), klds, s);
+    }
     ACE_HIP(hipStreamSynchronize(s));   // (pageable source of the table copy; a merge is rare next to the requests it serves)
     if (rc) return rc;
     if (kv) h->lora.gen_kv++;   // condition slots built from the old cross k / v (or, broadcast, o) weights are stale now
@@ -1859,6 +1951,15 @@ int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_
     if (h->dual.ctx) h->dual.ctx->nf.key.clear();
     if (h->lora.applied.empty()) lora_free_pristine(h);   // the base is back everywhere (the stream was synchronised above)
     return ACE355_OK;
+}
+
+int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_terms, void* stream) {
+    return set_adapters_impl(h, terms, n_terms, nullptr, 0, stream);
+}
+
+int ace355_dit_set_adapters_mixed(ace355_dit* h, const ace355_lora_term* lora, int n_lora, const ace355_kron_term* kron, int n_kron,
+                                  void* stream) {
+    return set_adapters_impl(h, lora, n_lora, kron, n_kron, stream);
 }
 
 int ace355_dit_read_weight(ace355_dit* h, const char* name, void* dst_dev, int dtype, void* stream) {

@@ -229,26 +229,51 @@ class NativeDit:
 
     # ------------------------------------------------------------------ LoRA adapters, merged into the packed weights
     def set_adapters(self, terms) -> None:
-        """Replace the WHOLE adapter state by ``terms`` (``ace355.lora.LoraTerm`` or ``(name, A, B, scale)`` tuples; an empty list
-        restores the base): every target weight becomes bf16(W0 + sum of scale x B @ A), whatever the earlier calls were
-        (include/ace355.h ``ace355_dit_set_adapters``).  A / B are converted to bf16 on this device, as the reference's
-        ``.to(self.dtype)`` does.  Synchronous: the merge has run on the current stream when this returns.  bf16 precision only."""
+        """Replace the WHOLE adapter state by ``terms`` (an empty list restores the base): ``ace355.lora.LoraTerm`` / ``(name, A, B,
+        scale)`` tuples and ``ace355.lokr.KronTerm`` / 8-tuples, mixed freely.  Every target weight becomes bf16(W0 + sum of scale x
+        B @ A) resp. bf16(W0 + sum of scale x kron(W1, W2)), whatever the earlier calls were (include/ace355.h
+        ``ace355_dit_set_adapters`` / ``ace355_dit_set_adapters_mixed``; the latter is called only when a Kronecker term is present).
+        The tensors are converted to bf16 on this device, as the reference's ``.to(self.dtype)`` does.  Synchronous: the merge has run
+        on the current stream when this returns.  bf16 precision only."""
+        from .lokr import KronTerm, term_dims
         shapes = self.cfg.weight_shapes()
-        keep, rows = [], []   # (alive until the synchronous native call has returned)
+        keep, rows, krows = [], [], []   # (alive until the synchronous native call has returned)
         with torch.cuda.device(self.device):
-            for name, A, B, scale in terms:
+            def dev(x):
+                if x is None:
+                    return 0
+                if x.dtype == torch.bfloat16 and x.device == self.device and x.is_contiguous():
+                    y = x   # (already what the merge reads: a default LoKr adapter has 200 to 600 such tensors)
+                else:
+                    y = x.detach().to(self.device, torch.bfloat16).contiguous()
+                keep.append(y)
+                return native.ptr(y)
+            for term in terms:
+                nm = term[0].encode()
+                keep.append(nm)
+                if len(term) == 8:
+                    kt = KronTerm(*term)
+                    out_l, out_k, in_m, in_n, r1, r2 = term_dims(kt)
+                    if kt.name in shapes and (out_l * out_k, in_m * in_n) != tuple(shapes[kt.name]):
+                        raise ValueError(f"set_adapters: W1 [{out_l}, {in_m}] kron W2 [{out_k}, {in_n}] does not fit {kt.name} "
+                                         f"{list(shapes[kt.name])}")
+                    krows.append((nm, dev(kt.w1), dev(kt.w1_a), dev(kt.w1_b), dev(kt.w2), dev(kt.w2_a), dev(kt.w2_b),
+                                  out_l, out_k, in_m, in_n, r1, r2, float(kt.scale)))
+                    continue
+                name, A, B, scale = term
                 if name in shapes:
                     out_f, in_f = shapes[name]
                     if A.dim() != 2 or B.dim() != 2 or A.shape[1] != in_f or B.shape[0] != out_f or A.shape[0] != B.shape[1]:
                         raise ValueError(f"set_adapters: A {tuple(A.shape)} / B {tuple(B.shape)} do not fit {name} [{out_f}, {in_f}]")
-                a = A.detach().to(self.device, torch.bfloat16).contiguous()
-                b = B.detach().to(self.device, torch.bfloat16).contiguous()
-                nm = name.encode()
-                keep += [a, b, nm]
-                rows.append((nm, native.ptr(a), native.ptr(b), int(a.shape[0]), float(scale)))
+                rows.append((nm, dev(A), dev(B), int(A.shape[0]), float(scale)))
             arr = (native.LoraTermC * max(len(rows), 1))(*[native.LoraTermC(*r) for r in rows])
-            native.check(self._lib.ace355_dit_set_adapters(self._h, arr, len(rows), native.current_stream_ptr()), "dit_set_adapters")
-        self._adapters_applied = any(float(r[4]) != 0.0 for r in rows)
+            if krows:
+                karr = (native.KronTermC * len(krows))(*[native.KronTermC(*r) for r in krows])
+                native.check(self._lib.ace355_dit_set_adapters_mixed(self._h, arr, len(rows), karr, len(krows), native.current_stream_ptr()),
+                             "dit_set_adapters_mixed")
+            else:
+                native.check(self._lib.ace355_dit_set_adapters(self._h, arr, len(rows), native.current_stream_ptr()), "dit_set_adapters")
+        self._adapters_applied = any(float(r[-1]) != 0.0 for r in rows + krows)
 
     def clear_adapters(self) -> None:
         """Restore the base weights (``set_adapters([])``)."""

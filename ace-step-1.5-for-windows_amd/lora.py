@@ -6,7 +6,8 @@ forward ``y = x W^T + scaling * (x A^T) B^T`` equals a forward with ``W + scalin
 packed bf16 weights (``NativeDit.set_adapters``, include/ace355.h ``ace355_dit_set_adapters``).  One term = ``(name, A, B, scale)`` for
 one adapter on one target weight, ``name`` the reference key of the target (``layers.3.cross_attn.k_proj.weight``).
 
-What the merge does not cover raises ``UnsupportedAdapter``, which the seam turns into the PyTorch path: LoKr / LyCORIS, DoRA, adapters
+LoKr (LyCORIS) adapters are the other family the handle merges: ``ace355.lokr``.
+What the merge does not cover raises ``UnsupportedAdapter``, which the seam turns into the PyTorch path: DoRA, adapters
 with trained biases, ``modules_to_save``, ``fan_in_fan_out``, already merged PEFT modules, and targets outside the ten projection kinds.
 This module needs neither ``peft`` nor ``lycoris`` (it reads the attributes the reference itself reads,
 core/lora/introspection.py:77-90).
@@ -148,12 +149,16 @@ def _active(mod) -> List[str]:
     return [act] if isinstance(act, str) else list(act)
 
 
-def terms_from_decoder(decoder, cfg=None) -> List[LoraTerm]:
+def terms_from_decoder(decoder, cfg=None) -> list:
     """Terms of a PEFT-wrapped decoder, by duck typing (no ``peft`` import): every module with ``lora_A`` / ``lora_B`` / ``scaling``
-    whose adapters are enabled contributes ``scaling[a]``, ``lora_A[a].weight``, ``lora_B[a].weight`` for each active adapter ``a``."""
-    if getattr(decoder, "_lycoris_net", None) is not None:
-        raise UnsupportedAdapter("LoKr / LyCORIS network on the decoder: not merged natively")
-    terms: List[LoraTerm] = []
+    whose adapters are enabled contributes ``scaling[a]``, ``lora_A[a].weight``, ``lora_B[a].weight`` for each active adapter ``a``.
+    A LyCORIS network on the decoder (``_lycoris_net``) contributes its LoKr modules as ``ace355.lokr.KronTerm``, ahead of them."""
+    terms: list = []
+    net = getattr(decoder, "_lycoris_net", None)
+    if net is not None:   # LoKr (H/lora/lifecycle.py:101-155): its modules as Kronecker terms (lokr.py)
+        from .lokr import terms_from_lycoris
+        terms += terms_from_lycoris(net, cfg)
+    n_kron = len(terms)
     for mname, mod in decoder.named_modules():
         if hasattr(mod, "modules_to_save") and hasattr(mod, "original_module"):
             raise UnsupportedAdapter(f"modules_to_save wrapper at {mname}: not merged natively")
@@ -174,14 +179,20 @@ def terms_from_decoder(decoder, cfg=None) -> List[LoraTerm]:
                 raise UnsupportedAdapter(f"adapter '{a}' at {mname} trains a bias: not merged natively")
             name = _target_name(_module_path(mname), getattr(cfg, "num_hidden_layers", None))
             terms.append(LoraTerm(name, mod.lora_A[a].weight, mod.lora_B[a].weight, float(mod.scaling[a])))
-    _check_shapes(terms, cfg)
+    _check_shapes(terms[n_kron:], cfg)
     return terms
 
 
 def fingerprint(terms) -> tuple:
-    """A cheap key of a term list: names, scales, the A / B storages and their in-place version counters."""
+    """A cheap key of a term list: names, scales, the A / B (for a ``KronTerm``: the factor) storages and their in-place version
+    counters."""
+    def ident(x):
+        return None if x is None else (x.data_ptr(), x._version, tuple(x.shape), str(x.device))
     key = []
     for t in terms:
+        if hasattr(t, "w1_a"):   # ace355.lokr.KronTerm
+            key.append(("kron", t.name, float(t.scale)) + tuple(ident(x) for x in t[1:7]))
+            continue
         key.append((t.name, float(t.scale), t.A.data_ptr(), t.A._version, tuple(t.A.shape), t.B.data_ptr(), t.B._version,
                     tuple(t.B.shape), str(t.A.device)))
     return tuple(key)

@@ -89,6 +89,13 @@ class LoraTermC(C.Structure):
     _fields_ = [("name", C.c_char_p), ("A_dev", C.c_void_p), ("B_dev", C.c_void_p), ("rank", C.c_int32), ("scale", C.c_float)]
 
 
+class KronTermC(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("w1_dev", C.c_void_p), ("w1a_dev", C.c_void_p), ("w1b_dev", C.c_void_p),
+                ("w2_dev", C.c_void_p), ("w2a_dev", C.c_void_p), ("w2b_dev", C.c_void_p),
+                ("out_l", C.c_int32), ("out_k", C.c_int32), ("in_m", C.c_int32), ("in_n", C.c_int32), ("r1", C.c_int32), ("r2", C.c_int32),
+                ("scale", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/ace355.h declares
 SIGNATURES = {
     "ace355_last_error": (C.c_char_p, []),
@@ -107,6 +114,7 @@ SIGNATURES = {
                                     C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
     "ace355_dit_set_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ace355_dit_set_adapters": (C.c_int, [C.c_void_p, C.POINTER(LoraTermC), C.c_int, C.c_void_p]),
+    "ace355_dit_set_adapters_mixed": (C.c_int, [C.c_void_p, C.POINTER(LoraTermC), C.c_int, C.POINTER(KronTermC), C.c_int, C.c_void_p]),
     "ace355_dit_read_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ace355_dit_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "ace355_dit_set_graph": (C.c_int, [C.c_void_p, C.c_int]),

@@ -246,6 +246,30 @@ typedef struct ace355_lora_term {
  * that rewrites a cross-attention k / v (or o, for broadcast slots) projection makes the condition slots built before it stale:
  * a forward / sample reading one returns ERR_STATE until ace355_dit_set_condition rebuilds it. */
 int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_terms, void* stream);
+/* LoKr adapters (LyCORIS LokrModule semantics, restated from its published source: the weight delta of a module is
+ * scale x multiplier x kron(W1, W2), each factor held in full or as a low-rank product w_a @ w_b).  The reference loads a LoKr
+ * artefact through LyCORIS (H/lora/lifecycle.py:16-155, 232-236) and toggles / scales it with set_multiplier
+ * (H/lora/controls.py:12-32, 49-55, 121-129).  One term on a target [out, in] with out = out_l out_k, in = in_m in_n:
+ *     dW[l out_k + k, m in_n + n] = scale W1[l, m] W2[k, n],
+ *     W1 = w1 [out_l, in_m] or w1a [out_l, r1] @ w1b [r1, in_m],   W2 = w2 [out_k, in_n] or w2a [out_k, r2] @ w2b [r2, in_n].
+ * All factor tensors are bf16, row-major, on the device (the reference casts the decoder, LyCORIS modules included, to the model
+ * dtype: lifecycle.py:251).  `name` is one of the ten target kinds of ace355_lora_term. */
+typedef struct ace355_kron_term {
+    const char* name;                       /* same ten target kinds as ace355_lora_term */
+    const void *w1_dev, *w1a_dev, *w1b_dev; /* exactly one of {w1} / {w1a, w1b} set */
+    const void *w2_dev, *w2a_dev, *w2b_dev; /* exactly one of {w2} / {w2a, w2b} set */
+    int32_t out_l, out_k, in_m, in_n, r1, r2;   /* r1 / r2 = 0 for a full factor */
+    float scale;
+} ace355_kron_term;
+/* ace355_dit_set_adapters for a state that mixes both families: replaces the WHOLE adapter state, with the same synchrony,
+ * pristine-copy lifetime, stale-slot marking and precision refusals.  Every rewritten weight is bf16_rne(float(W0) + sum_j dW_j):
+ * a decomposed factor's product is formed in fp32 (rank order) in a scratch table of the handle, the Kronecker products and the
+ * sum over a target's terms (call order) are fp32, one rounding.  n_kron 0 IS ace355_dit_set_adapters (the same launches, the same
+ * bits).  Several Kronecker terms may name one target; scale 0 drops a term.  ERR_INVALID: a target named by both a LoRA and a
+ * Kronecker term (the reference never has both, lifecycle.py:244-246), out_l out_k != out or in_m in_n != in, a missing or doubled
+ * factor pointer (a full factor has rank 0, a decomposed one rank >= 1), a rank below 0, a non-finite scale, an unknown name. */
+int ace355_dit_set_adapters_mixed(ace355_dit* h, const ace355_lora_term* lora, int n_lora, const ace355_kron_term* kron, int n_kron,
+                                  void* stream);
 /* Copy the live (merged) weight of one of the ten target kinds above to dst_dev in the reference layout [out, in] (the inverse of the
  * packing's row map), as ACE355_DTYPE_F32 or ACE355_DTYPE_BF16; enqueued on `stream`.  Tests, and export of merged weights. */
 int ace355_dit_read_weight(ace355_dit* h, const char* name, void* dst_dev, int dtype, void* stream);
