@@ -27,7 +27,9 @@ def _prefix_lengths(mask: torch.Tensor, what: str) -> torch.Tensor:
     return lens.to(torch.int32)
 
 
-class NativeCondEncoder:
+class NativeCondEncoder(native.Owner):
+    _destroy = "ace355_cond_destroy"
+
     def __init__(self, cfg: CondConfig, device: Union[str, torch.device] = "cuda:0", out_dtype: torch.dtype = torch.float32):
         self.cfg = cfg
         self.device = torch.device(device)
@@ -36,10 +38,7 @@ class NativeCondEncoder:
         n = max(cfg.num_lyric_encoder_hidden_layers, cfg.num_timbre_encoder_hidden_layers)
         if len(cfg.layer_types) < n or n > 64:
             raise ValueError("ace355: layer_types shorter than the encoder stacks")
-        mask = 0
-        for i in range(n):
-            if cfg.layer_types[i] == "sliding_attention":
-                mask |= 1 << i
+        mask = native.sliding_mask(cfg.layer_types, n)
         c = native.CondConfigC(cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim,
                                cfg.text_hidden_dim, cfg.timbre_hidden_dim, cfg.num_lyric_encoder_hidden_layers,
                                cfg.num_timbre_encoder_hidden_layers, cfg.sliding_window, mask, cfg.rms_norm_eps, cfg.rope_theta)
@@ -55,32 +54,9 @@ class NativeCondEncoder:
         self.load_state_dict(encoder_module.state_dict())
         return self
 
-    def close(self):
-        if getattr(self, "_h", None):
-            with torch.cuda.device(self.device):
-                self._lib.ace355_cond_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         """Keys of ``AceStepConditionEncoder.state_dict()``; rotary ``inv_freq`` buffers are skipped."""
-        with torch.cuda.device(self.device):
-            for name, t in sd.items():
-                if "rotary_emb" in name:
-                    continue
-                t = t.detach()
-                if t.dtype not in (torch.float32, torch.bfloat16):
-                    t = t.float()
-                t = t.contiguous()
-                dt = native.DTYPE_F32 if t.dtype == torch.float32 else native.DTYPE_BF16
-                native.check(self._lib.ace355_cond_load_tensor(self._h, name.encode(), native.ptr(t), dt, t.numel(),
-                                                               1 if t.is_cuda else 0), f"cond_load_tensor({name})")
-            native.check(self._lib.ace355_cond_finalize(self._h), "cond_finalize")
+        native.load_state_dict(self._lib.ace355_cond_load_tensor, self._lib.ace355_cond_finalize, self._h, sd, "cond", self.device)
 
     def __call__(self, text_hidden_states: torch.Tensor, text_attention_mask: torch.Tensor, lyric_hidden_states: torch.Tensor,
                  lyric_attention_mask: torch.Tensor, refer_audio_acoustic_hidden_states_packed: torch.Tensor,

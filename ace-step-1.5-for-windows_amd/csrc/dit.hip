@@ -12,8 +12,7 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/ace355.h"
-#include "common.h"
+#include "encoder.h"
 
 using namespace ace355;
 
@@ -47,19 +46,13 @@ struct CondSlot {
 
 }  // namespace
 
-struct ace355_dit {
+struct ace355_dit : LoadBase {
     ace355_dit_config cfg;
     int D, F, QD, KVD, NL, KVH, HQ, OUTC;
     std::vector<LayerW> layers;
     bf16_t *w_in = nullptr, *w_out = nullptr, *w_cond = nullptr;
     float *b_in = nullptr, *b_out = nullptr, *b_cond = nullptr, *norm_out = nullptr, *sst_out = nullptr;
     TimeEmbedW te[2];
-    std::set<std::string> loaded;
-    size_t expected_tensors = 0;
-    bool finalized = false;
-    std::vector<void*> allocs;
-    void* stage = nullptr;
-    size_t stage_bytes = 0;
 
     // workspace
     int ws_N = 0, ws_T = 0;
@@ -191,49 +184,25 @@ struct ace355_dit {
 
 namespace {
 
-template <typename T>
-int dev_alloc(std::vector<void*>& bag, T** p, size_t n) {
-    void* q = nullptr;
-    ACE_HIP(hipMalloc(&q, n * sizeof(T) + 256));
-    bag.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return 0;
-}
-#define ALLOC(bag, ptr, n)                         \
-    do {                                           \
-        int _rc = dev_alloc(bag, &(ptr), (n));     \
-        if (_rc) return _rc;                       \
-    } while (0)
-
-struct Dest {
-    void* dst;
-    int is_bf16;
-    int mode;
-    long rows, cols, dst_ld, dst_row0;
-    int p0, p1;
-};
-
 // Map a reference state_dict key to its packed destination.
-bool resolve(ace355_dit* h, const std::string& name, Dest* d) {
+bool resolve(ace355_dit* h, const std::string& name, PackDest* d) {
     const long D = h->D, F = h->F, QD = h->QD, KVD = h->KVD;
     auto rows = [&](void* dst, int bf, long r, long c, long ld, long row0) {
-        *d = Dest{dst, bf, PACK_ROWS, r, c, ld, row0, 0, 0};
+        *d = PackDest{dst, bf, PACK_ROWS, r, c, ld, row0, 0, 0};
         return true;
     };
     if (name.rfind("layers.", 0) == 0) {
-        const size_t dot = name.find('.', 7);
-        if (dot == std::string::npos) return false;
-        const int li = atoi(name.substr(7, dot - 7).c_str());
-        if (li < 0 || li >= h->NL) return false;
+        int li;
+        std::string r;
+        if (!parse_layer_index(name, 0, h->NL, &li, &r)) return false;
         LayerW& L = h->layers[li];
-        const std::string r = name.substr(dot + 1);
         if (r == "scale_shift_table") return rows(L.sst, 0, 6, D, D, 0);
         if (r == "self_attn_norm.weight") return rows(L.n_sa, 0, 1, D, D, 0);
         if (r == "cross_attn_norm.weight") return rows(L.n_ca, 0, 1, D, D, 0);
         if (r == "mlp_norm.weight") return rows(L.n_mlp, 0, 1, D, D, 0);
         // self-attention q / k rows in the head-pair order (common.h PackMode): RoPE partners adjacent
-        if (r == "self_attn.q_proj.weight") { *d = Dest{L.wqkv, 1, PACK_ROWS_HEADPAIR, QD, D, D, 0, 0, 0}; return true; }
-        if (r == "self_attn.k_proj.weight") { *d = Dest{L.wqkv, 1, PACK_ROWS_HEADPAIR, KVD, D, D, QD, 0, 0}; return true; }
+        if (r == "self_attn.q_proj.weight") { *d = PackDest{L.wqkv, 1, PACK_ROWS_HEADPAIR, QD, D, D, 0, 0, 0}; return true; }
+        if (r == "self_attn.k_proj.weight") { *d = PackDest{L.wqkv, 1, PACK_ROWS_HEADPAIR, KVD, D, D, QD, 0, 0}; return true; }
         if (r == "self_attn.v_proj.weight") return rows(L.wqkv, 1, KVD, D, D, QD + KVD);
         if (r == "self_attn.o_proj.weight") return rows(L.wo, 1, D, QD, QD, 0);
         if (r == "self_attn.q_norm.weight") return rows(L.qn_s, 0, 1, 128, 128, 0);
@@ -244,15 +213,15 @@ bool resolve(ace355_dit* h, const std::string& name, Dest* d) {
         if (r == "cross_attn.o_proj.weight") return rows(L.wo_c, 1, D, QD, QD, 0);
         if (r == "cross_attn.q_norm.weight") return rows(L.qn_c, 0, 1, 128, 128, 0);
         if (r == "cross_attn.k_norm.weight") return rows(L.kn_c, 0, 1, 128, 128, 0);
-        if (r == "mlp.gate_proj.weight") { *d = Dest{L.wgu, 1, PACK_ROWS_IL32, F, D, D, 0, 0, 0}; return true; }
-        if (r == "mlp.up_proj.weight") { *d = Dest{L.wgu, 1, PACK_ROWS_IL32, F, D, D, 0, 1, 0}; return true; }
+        if (r == "mlp.gate_proj.weight") { *d = PackDest{L.wgu, 1, PACK_ROWS_IL32, F, D, D, 0, 0, 0}; return true; }
+        if (r == "mlp.up_proj.weight") { *d = PackDest{L.wgu, 1, PACK_ROWS_IL32, F, D, D, 0, 1, 0}; return true; }
         if (r == "mlp.down_proj.weight") return rows(L.wdown, 1, D, F, F, 0);
         return false;
     }
     const int C = h->cfg.in_channels, P = h->cfg.patch_size, OC = h->OUTC;
-    if (name == "proj_in.1.weight") { *d = Dest{h->w_in, 1, PACK_CONV_IN, D, (long)C * P, (long)C * P, 0, C, P}; return true; }
+    if (name == "proj_in.1.weight") { *d = PackDest{h->w_in, 1, PACK_CONV_IN, D, (long)C * P, (long)C * P, 0, C, P}; return true; }
     if (name == "proj_in.1.bias") return rows(h->b_in, 0, 1, D, D, 0);
-    if (name == "proj_out.1.weight") { *d = Dest{h->w_out, 1, PACK_CONVT_OUT, D, (long)OC * P, D, 0, OC, P}; return true; }
+    if (name == "proj_out.1.weight") { *d = PackDest{h->w_out, 1, PACK_CONVT_OUT, D, (long)OC * P, D, 0, OC, P}; return true; }
     if (name == "proj_out.1.bias") return rows(h->b_out, 0, 1, OC, OC, 0);  // duplicated per patch position at finalize
     for (int e = 0; e < 2; ++e) {
         const std::string p = e == 0 ? "time_embed." : "time_embed_r.";
@@ -276,15 +245,13 @@ bool resolve(ace355_dit* h, const std::string& name, Dest* d) {
 
 // The ten LoRA target kinds of a layer (ace355_dit_set_adapters / ace355_dit_read_weight): the Linear projections of resolve(), by
 // their canonical reference key only
-bool lora_target(ace355_dit* h, const std::string& name, Dest* d) {
+bool lora_target(ace355_dit* h, const std::string& name, PackDest* d) {
     static const char* kinds[] = {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
                                   "cross_attn.q_proj.weight", "cross_attn.k_proj.weight", "cross_attn.v_proj.weight", "cross_attn.o_proj.weight",
                                   "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight"};
-    if (name.rfind("layers.", 0) != 0) return false;
-    const size_t dot = name.find('.', 7);
-    if (dot == std::string::npos || dot == 7 || dot - 7 > 2) return false;
-    const std::string li = name.substr(7, dot - 7), r = name.substr(dot + 1);
-    if (li.find_first_not_of("0123456789") != std::string::npos || std::to_string(atoi(li.c_str())) != li) return false;
+    int li;
+    std::string r;
+    if (!parse_layer_index(name, 0, h->NL, &li, &r)) return false;
     bool kind = false;
     for (const char* k : kinds) kind = kind || r == k;
     return kind && resolve(h, name, d);
@@ -1153,7 +1120,7 @@ void ace355_dit_destroy(ace355_dit* h) {
     if (!h) return;
     hipDeviceSynchronize();
     chain_ctx_destroy(h->dual.ctx);
-    for (void* p : h->allocs) hipFree(p);
+    free_base(h);
     for (void* p : h->ws_allocs) hipFree(p);
     for (void* p : h->mx_allocs) hipFree(p);
     for (void* p : h->nf.allocs) hipFree(p);
@@ -1171,7 +1138,6 @@ void ace355_dit_destroy(ace355_dit* h) {
     if (h->graph_stream) hipStreamDestroy(h->graph_stream);
     if (h->graph_in) hipEventDestroy(h->graph_in);
     if (h->graph_out) hipEventDestroy(h->graph_out);
-    if (h->stage) hipFree(h->stage);
     lora_free_pristine(h);
     if (h->lora.tab) hipFree(h->lora.tab);
     if (h->lora.kscratch) hipFree(h->lora.kscratch);
@@ -1191,52 +1157,26 @@ int ace355_dit_load_tensor(ace355_dit* h, const char* name, const void* data, in
         set_error("dit_load_tensor: LoRA adapters are applied; restore the base weights first (ace355_dit_set_adapters with no terms)");
         return ACE355_ERR_STATE;
     }
-    Dest d;
-    if (!resolve(h, name, &d)) {
-        set_error(std::string("dit_load_tensor: unknown tensor name '") + name + "'");
-        return ACE355_ERR_INVALID;
-    }
-    if (numel != d.rows * d.cols) {
-        set_error(std::string("dit_load_tensor: wrong element count for '") + name + "': got " + std::to_string(numel) +
-                  ", expected " + std::to_string(d.rows * d.cols));
-        return ACE355_ERR_INVALID;
-    }
-    const size_t esz = dtype == ACE355_DTYPE_F32 ? 4 : 2;
-    const void* src = data;
-    if (!is_device) {
-        const size_t bytes = (size_t)numel * esz;
-        if (bytes > h->stage_bytes) {
-            if (h->stage) ACE_HIP(hipFree(h->stage));
-            h->stage = nullptr;
-            ACE_HIP(hipMalloc(&h->stage, bytes));
-            h->stage_bytes = bytes;
-        }
-        ACE_HIP(hipMemcpy(h->stage, data, bytes, hipMemcpyHostToDevice));
-        src = h->stage;
-    }
-    int rc = launch_pack(src, dtype, d.dst, d.is_bf16, d.mode, d.rows, d.cols, d.dst_ld, d.dst_row0, d.p0, d.p1, nullptr);
+    PackDest d;
+    if (!resolve(h, name, &d)) return unknown_tensor("dit_load_tensor", name);
+    int rc = load_packed(h, d, name, data, dtype, numel, is_device, "dit_load_tensor");
     if (rc) return rc;
     if (std::string(name) == "proj_out.1.bias") {  // bias[p*64 + c] = b[c]
+        const void* src = is_device ? data : h->stage;
         rc = launch_pack(src, dtype, h->b_out, 0, PACK_ROWS, 1, h->OUTC, h->OUTC, 0, 0, 0, nullptr);
         if (rc) return rc;
         rc = launch_pack(src, dtype, h->b_out + h->OUTC, 0, PACK_ROWS, 1, h->OUTC, h->OUTC, 0, 0, 0, nullptr);
         if (rc) return rc;
+        ACE_HIP(hipDeviceSynchronize());
     }
-    ACE_HIP(hipDeviceSynchronize());
-    h->loaded.insert(name);
-    h->finalized = false;
     h->weights_fp8wo = false;   // (fresh weights: the round trip, if wanted, is applied again by set_precision)
     return ACE355_OK;
 }
 
 int ace355_dit_finalize(ace355_dit* h) {
     ACE_CHECK(h, "dit_finalize: null handle");
-    if (h->loaded.size() != h->expected_tensors) {
-        set_error("dit_finalize: " + std::to_string(h->loaded.size()) + " of " + std::to_string(h->expected_tensors) +
-                  " tensors loaded");
-        return ACE355_ERR_STATE;
-    }
-    if (h->stage) { hipFree(h->stage); h->stage = nullptr; h->stage_bytes = 0; }
+    if (int rc = finalize_loaded(h, "dit_finalize")) return rc;
+    h->finalized = false;   // (until the table below exists)
     {   // modulated norms: scale_shift_table rows (shift_msa, scale_msa, gate_msa, c_shift, c_scale, c_gate), base.py:492-497
         std::vector<ModEntry> tab;
         for (const LayerW& L : h->layers) {
@@ -1784,7 +1724,7 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
     std::vector<std::string> order;
     std::vector<std::vector<const ace355_lora_term*>> by;
     std::vector<std::vector<const ace355_kron_term*>> kby;
-    std::vector<Dest> dests;
+    std::vector<PackDest> dests;
     auto index_of = [&](const std::string& n) { for (size_t i = 0; i < order.size(); ++i) if (order[i] == n) return (int)i; return -1; };
     auto not_a_target = [&](const char* name) {
         set_error(std::string("set_adapters: '") + name + "' is not a LoRA target (layers.{i}.{self_attn,cross_attn}.{q,k,v,o}_proj.weight, "
@@ -1795,7 +1735,7 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
     for (int i = 0; i < n_terms; ++i) {
         const ace355_lora_term& t = terms[i];
         ACE_CHECK(t.name && t.A_dev && t.B_dev, "set_adapters: null name / A / B");
-        Dest d;
+        PackDest d;
         if (!lora_target(h, t.name, &d)) return not_a_target(t.name);
         ACE_CHECK(t.rank >= 1 && std::isfinite(t.scale), "set_adapters: rank must be >= 1 and scale finite");
         if (n_kron) lora_named.insert(t.name);
@@ -1807,7 +1747,7 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
     for (int i = 0; i < n_kron; ++i) {
         const ace355_kron_term& t = kron[i];
         ACE_CHECK(t.name, "set_adapters: null name in a Kronecker term");
-        Dest d;
+        PackDest d;
         if (!lora_target(h, t.name, &d)) return not_a_target(t.name);
         // exactly one of {w} / {w_a, w_b} per factor; r = 0 for a full factor, >= 1 for a decomposed one
         const bool f1 = t.w1_dev && !t.w1a_dev && !t.w1b_dev && t.r1 == 0, d1 = !t.w1_dev && t.w1a_dev && t.w1b_dev && t.r1 >= 1;
@@ -1830,7 +1770,7 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
     const size_t n_merge = order.size();
     for (const std::string& n : h->lora.applied) {   // merged before, no term now: its rows go back to the base
         if (index_of(n) >= 0) continue;
-        Dest d;
+        PackDest d;
         lora_target(h, n, &d);
         order.push_back(n); by.emplace_back(); kby.emplace_back(); dests.push_back(d);
     }
@@ -1840,7 +1780,7 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
         for (auto& pr : h->lora.pristine) if (pr.first == buf) return pr.second;
         return nullptr;
     };
-    for (const Dest& d : dests) {   // first touch of a packed buffer: its base copy
+    for (const PackDest& d : dests) {   // first touch of a packed buffer: its base copy
         if (pristine_of(d.dst)) continue;
         const size_t n = packed_elems(h, d.dst);
         void* q = nullptr;
@@ -1883,7 +1823,7 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
         return f.dst;
     };
     for (size_t i = 0; i < order.size(); ++i) {
-        const Dest& d = dests[i];
+        const PackDest& d = dests[i];
         ACE_CHECK(d.cols % 8 == 0, "set_adapters: target columns must be a multiple of 8");
         const bool to_kron = !kby[i].empty() || (by[i].empty() && any_kron);
         LoraTargetDev x{};
@@ -1965,7 +1905,7 @@ int ace355_dit_set_adapters_mixed(ace355_dit* h, const ace355_lora_term* lora, i
 int ace355_dit_read_weight(ace355_dit* h, const char* name, void* dst_dev, int dtype, void* stream) {
     ACE_CHECK(h && name && dst_dev, "read_weight: null argument");
     ACE_CHECK(dtype == ACE355_DTYPE_F32 || dtype == ACE355_DTYPE_BF16, "read_weight: dtype");
-    Dest d;
+    PackDest d;
     if (!lora_target(h, name, &d)) {
         set_error(std::string("read_weight: '") + name + "' is not one of the projection weights read_weight serves");
         return ACE355_ERR_INVALID;

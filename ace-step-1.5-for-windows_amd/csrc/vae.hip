@@ -9,8 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/ace355.h"
-#include "common.h"
+#include "encoder.h"   // dev_alloc
 
 using namespace ace355;
 
@@ -209,11 +208,7 @@ namespace {
 
 template <typename T>
 int valloc(ace355_vae* h, T** p, size_t n) {
-    void* q = nullptr;
-    ACE_HIP(hipMalloc(&q, n * sizeof(T) + 256));
-    h->allocs.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return 0;
+    return dev_alloc(h->allocs, p, n);
 }
 
 const RawT* find(ace355_vae* h, const std::string& k) {

@@ -49,15 +49,14 @@ def prepare_noise(shape, seed: Union[int, List[int], None]) -> torch.Tensor:
     return torch.randn(shape, generator=g, dtype=torch.float32)
 
 
-class NativeDit:
+class NativeDit(native.Owner):
+    _destroy = "ace355_dit_destroy"
+
     def __init__(self, cfg: DitConfig, device: Union[str, torch.device] = "cuda:0"):
         self.cfg = cfg
         self.device = torch.device(device)
         self._lib = native.lib()
-        mask = 0
-        for i, t in enumerate(cfg.layer_types):
-            if t == "sliding_attention":
-                mask |= 1 << i
+        mask = native.sliding_mask(cfg.layer_types, len(cfg.layer_types))
         c = native.DitConfigC(cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers, cfg.num_attention_heads,
                               cfg.num_key_value_heads, cfg.head_dim, int(cfg.sliding_window or 0), cfg.patch_size,
                               cfg.in_channels, cfg.audio_acoustic_hidden_dim, cfg.rms_norm_eps, cfg.rope_theta, mask)
@@ -68,33 +67,9 @@ class NativeDit:
         self._finalized = False
 
     # ------------------------------------------------------------------ lifecycle
-    def close(self):
-        if getattr(self, "_h", None):
-            with torch.cuda.device(self.device):
-                self._lib.ace355_dit_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         """Ingest ``AceStepDiTModel.state_dict()`` (fp32 or bf16, CPU or this device). Extra keys raise."""
-        with torch.cuda.device(self.device):
-            for name, t in sd.items():
-                if "rotary_emb" in name:
-                    continue
-                t = t.detach()
-                if t.dtype not in (torch.float32, torch.bfloat16):
-                    t = t.float()
-                t = t.contiguous()
-                is_dev = 1 if t.is_cuda else 0
-                dt = native.DTYPE_F32 if t.dtype == torch.float32 else native.DTYPE_BF16
-                native.check(self._lib.ace355_dit_load_tensor(self._h, name.encode(), native.ptr(t), dt, t.numel(), is_dev),
-                             f"dit_load_tensor({name})")
-            native.check(self._lib.ace355_dit_finalize(self._h), "dit_finalize")
+        native.load_state_dict(self._lib.ace355_dit_load_tensor, self._lib.ace355_dit_finalize, self._h, sd, "dit", self.device)
         self._finalized = True
 
     # ------------------------------------------------------------------ conditioning

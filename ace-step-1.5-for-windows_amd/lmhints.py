@@ -64,16 +64,15 @@ def fsq_output_from_indices(indices: torch.Tensor, project_out_weight: torch.Ten
     return _linear(codes, project_out_weight, project_out_bias)
 
 
-class NativeDetokenizer:
+class NativeDetokenizer(native.Owner):
+    _destroy = "ace355_detok_destroy"
+
     def __init__(self, cfg: DetokConfig, device: Union[str, torch.device] = "cuda:0", out_dtype: torch.dtype = torch.float32):
         self.cfg = cfg
         self.device = torch.device(device)
         self.out_dtype = out_dtype
         self._lib = native.lib()
-        mask = 0
-        for i in range(cfg.num_attention_pooler_hidden_layers):
-            if cfg.layer_types[i] == "sliding_attention":
-                mask |= 1 << i
+        mask = native.sliding_mask(cfg.layer_types, cfg.num_attention_pooler_hidden_layers)
         c = native.DetokConfigC(cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim,
                                 cfg.num_attention_pooler_hidden_layers, cfg.pool_window_size, cfg.audio_acoustic_hidden_dim,
                                 cfg.sliding_window, mask, cfg.rms_norm_eps, cfg.rope_theta)
@@ -89,31 +88,8 @@ class NativeDetokenizer:
         self.load_state_dict(module.state_dict())
         return self
 
-    def close(self):
-        if getattr(self, "_h", None):
-            with torch.cuda.device(self.device):
-                self._lib.ace355_detok_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        with torch.cuda.device(self.device):
-            for name, t in sd.items():
-                if "rotary_emb" in name:
-                    continue
-                t = t.detach()
-                if t.dtype not in (torch.float32, torch.bfloat16):
-                    t = t.float()
-                t = t.contiguous()
-                dt = native.DTYPE_F32 if t.dtype == torch.float32 else native.DTYPE_BF16
-                native.check(self._lib.ace355_detok_load_tensor(self._h, name.encode(), native.ptr(t), dt, t.numel(),
-                                                                1 if t.is_cuda else 0), f"detok_load_tensor({name})")
-            native.check(self._lib.ace355_detok_finalize(self._h), "detok_finalize")
+        native.load_state_dict(self._lib.ace355_detok_load_tensor, self._lib.ace355_detok_finalize, self._h, sd, "detok", self.device)
 
     def __call__(self, x: torch.Tensor, attention_mask=None) -> torch.Tensor:
         """x [B, T5, hidden] -> [B, T5 * pool_window_size, 64] (``AudioTokenDetokenizer.forward``; the reference never
@@ -151,11 +127,12 @@ def fsq_quantize(z: torch.Tensor, project_in_weight: torch.Tensor, project_in_bi
     return quantized, idx
 
 
-class NativeAudioTokenizer:
+class NativeAudioTokenizer(native.Owner):
     """Call-compatible with the reference's ``AceStepAudioTokenizer`` (``model.tokenizer``, base.py:1181-1223): ``forward(x)`` with
     ``x [B, T5, pool, 64]`` and ``tokenize(x [B, T5 * pool, 64])`` return ``(quantized [B, T5, hidden], indices [B, T5, 1])``.  The
     acoustic projection and the attention pooler run natively (``ace355_tok_*``); the quantizer (``quantizer.project_in / project_out``
     of the state dict) is the [n, hidden] x [hidden, 6] product + rounding of ``fsq_quantize``."""
+    _destroy = "ace355_tok_destroy"
 
     def __init__(self, cfg: DetokConfig, device: Union[str, torch.device] = "cuda:0", out_dtype: torch.dtype = torch.float32):
         self.cfg = cfg
@@ -163,10 +140,7 @@ class NativeAudioTokenizer:
         self.out_dtype = out_dtype
         self.pool_window_size = cfg.pool_window_size
         self._lib = native.lib()
-        mask = 0
-        for i in range(cfg.num_attention_pooler_hidden_layers):
-            if cfg.layer_types[i] == "sliding_attention":
-                mask |= 1 << i
+        mask = native.sliding_mask(cfg.layer_types, cfg.num_attention_pooler_hidden_layers)
         c = native.DetokConfigC(cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim,
                                 cfg.num_attention_pooler_hidden_layers, cfg.pool_window_size, cfg.audio_acoustic_hidden_dim,
                                 cfg.sliding_window, mask, cfg.rms_norm_eps, cfg.rope_theta)
@@ -182,37 +156,18 @@ class NativeAudioTokenizer:
         self.load_state_dict(module.state_dict())
         return self
 
-    def close(self):
-        if getattr(self, "_h", None):
-            with torch.cuda.device(self.device):
-                self._lib.ace355_tok_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         """Keys of ``AceStepAudioTokenizer.state_dict()``; ``quantizer.*`` entries are kept for ``fsq_quantize`` (only the two
         projections are read: ``quantizer.project_in.{weight,bias}``, ``quantizer.project_out.{weight,bias}``)."""
         self._q = {}
-        with torch.cuda.device(self.device):
-            for name, t in sd.items():
-                if "rotary_emb" in name:
-                    continue
-                t = t.detach()
-                if name.startswith("quantizer."):
-                    self._q[name[len("quantizer."):]] = t.float().to(self.device)
-                    continue
-                if t.dtype not in (torch.float32, torch.bfloat16):
-                    t = t.float()
-                t = t.contiguous()
-                dt = native.DTYPE_F32 if t.dtype == torch.float32 else native.DTYPE_BF16
-                native.check(self._lib.ace355_tok_load_tensor(self._h, name.encode(), native.ptr(t), dt, t.numel(),
-                                                              1 if t.is_cuda else 0), f"tok_load_tensor({name})")
-            native.check(self._lib.ace355_tok_finalize(self._h), "tok_finalize")
+
+        def keep_quantizer(name, t):
+            if name.startswith("quantizer."):
+                self._q[name[len("quantizer."):]] = t.float().to(self.device)
+                return True
+            return False
+        native.load_state_dict(self._lib.ace355_tok_load_tensor, self._lib.ace355_tok_finalize, self._h, sd, "tok", self.device,
+                               skip=keep_quantizer)
 
     def pool(self, x: torch.Tensor) -> torch.Tensor:
         """x [B, T5, pool, 64] or [B, T5 * pool, 64] -> pooled [B, T5, hidden] fp32 (everything before the quantizer)."""

@@ -259,3 +259,45 @@ def ptr(t) -> int:
         return 0
     assert t.is_contiguous(), "ace355: tensors crossing the C ABI must be contiguous"
     return int(t.data_ptr())
+
+
+def sliding_mask(layer_types, n: int) -> int:
+    """Bit i set when layer i < n is a ``sliding_attention`` layer (the ``sliding_layer_mask`` of the C configs)."""
+    return sum(1 << i for i in range(n) if layer_types[i] == "sliding_attention")
+
+
+def load_state_dict(load_fn, finalize_fn, handle, sd, what: str, device, skip=None) -> None:
+    """Feed a state dict to ``<what>_load_tensor`` and seal it with ``<what>_finalize``: fp32 / bf16 as they are, other dtypes as
+    fp32, CPU or GPU.  Rotary ``inv_freq`` buffers are skipped, and so is every entry for which ``skip(name, tensor)`` is true."""
+    import torch
+    with torch.cuda.device(device):
+        for name, t in sd.items():
+            if "rotary_emb" in name:
+                continue
+            t = t.detach()
+            if skip is not None and skip(name, t):
+                continue
+            if t.dtype not in (torch.float32, torch.bfloat16):
+                t = t.float()
+            t = t.contiguous()
+            dt = DTYPE_F32 if t.dtype == torch.float32 else DTYPE_BF16
+            check(load_fn(handle, name.encode(), ptr(t), dt, t.numel(), 1 if t.is_cuda else 0), f"{what}_load_tensor({name})")
+        check(finalize_fn(handle), f"{what}_finalize")
+
+
+class Owner:
+    """Base of the classes that own a native handle: ``_destroy`` names the library's destroy function."""
+    _destroy = ""
+
+    def close(self):
+        if getattr(self, "_h", None):
+            import torch
+            with torch.cuda.device(self.device):
+                getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

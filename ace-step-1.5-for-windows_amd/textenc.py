@@ -46,7 +46,9 @@ def _host_ids(ids, vocab: int, what: str) -> torch.Tensor:
     return t.to(torch.int32).contiguous()
 
 
-class NativeTextEncoder:
+class NativeTextEncoder(native.Owner):
+    _destroy = "ace355_textenc_destroy"
+
     def __init__(self, cfg: TextEncoderConfig, device: Union[str, torch.device] = "cuda:0", out_dtype: torch.dtype = torch.bfloat16):
         self.cfg = cfg
         self.device = torch.device(device)
@@ -71,32 +73,10 @@ class NativeTextEncoder:
         self.load_state_dict(module.state_dict())
         return self
 
-    def close(self):
-        if getattr(self, "_h", None):
-            with torch.cuda.device(self.device):
-                self._lib.ace355_textenc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         """Keys of ``Qwen3Model.state_dict()``; rotary buffers are skipped."""
-        with torch.cuda.device(self.device):
-            for name, t in sd.items():
-                if "rotary_emb" in name:
-                    continue
-                t = t.detach()
-                if t.dtype not in (torch.float32, torch.bfloat16):
-                    t = t.float()
-                t = t.contiguous()
-                dt = native.DTYPE_F32 if t.dtype == torch.float32 else native.DTYPE_BF16
-                native.check(self._lib.ace355_textenc_load_tensor(self._h, name.encode(), native.ptr(t), dt, t.numel(),
-                                                                  1 if t.is_cuda else 0), f"textenc_load_tensor({name})")
-            native.check(self._lib.ace355_textenc_finalize(self._h), "textenc_finalize")
+        native.load_state_dict(self._lib.ace355_textenc_load_tensor, self._lib.ace355_textenc_finalize, self._h, sd, "textenc",
+                               self.device)
 
     def __call__(self, input_ids=None, attention_mask=None, *args, lyric_attention_mask=None, output_hidden_states=None,
                  output_attentions=None, use_cache=None, return_dict=None, **kwargs) -> TextEncoderOutput:

@@ -14,7 +14,9 @@ from . import native
 from .config import VaeConfig
 
 
-class NativeVae:
+class NativeVae(native.Owner):
+    _destroy = "ace355_vae_destroy"
+
     def __init__(self, cfg: VaeConfig, device: Union[str, torch.device] = "cuda:0"):
         self.cfg = cfg
         self.device = torch.device(device)
@@ -30,18 +32,6 @@ class NativeVae:
             native.check(self._lib.ace355_vae_create(C.byref(c), C.byref(h)), "vae_create")
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            with torch.cuda.device(self.device):
-                self._lib.ace355_vae_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     @property
     def hop(self) -> int:
         return int(self._lib.ace355_vae_hop(self._h))
@@ -50,18 +40,8 @@ class NativeVae:
         """Keys of ``AutoencoderOobleck.state_dict()``: the decoder half is required, the encoder half optional
         (``encode`` needs it)."""
         self.has_encoder = any(k.startswith("encoder.") for k in sd)
-        with torch.cuda.device(self.device):
-            for name, t in sd.items():
-                if not (name.startswith("decoder.") or name.startswith("encoder.")):
-                    continue
-                t = t.detach()
-                if t.dtype not in (torch.float32, torch.bfloat16):
-                    t = t.float()
-                t = t.contiguous()
-                dt = native.DTYPE_F32 if t.dtype == torch.float32 else native.DTYPE_BF16
-                native.check(self._lib.ace355_vae_load_tensor(self._h, name.encode(), native.ptr(t), dt, t.numel(),
-                                                              1 if t.is_cuda else 0), f"vae_load_tensor({name})")
-            native.check(self._lib.ace355_vae_finalize(self._h), "vae_finalize")
+        native.load_state_dict(self._lib.ace355_vae_load_tensor, self._lib.ace355_vae_finalize, self._h, sd, "vae", self.device,
+                               skip=lambda name, t: not name.startswith(("decoder.", "encoder.")))
 
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         """z [B, 64, T] (the reference's layout) -> waveform fp32 [B, 2, hop*T] on this device."""
