@@ -6,7 +6,7 @@
 #include <string>
 
 #include "../../include/ace355.h"
-#include "common.h"
+#include "gemm_plan.h"
 #include <dlfcn.h>
 #include <stdlib.h>
 
@@ -98,6 +98,25 @@ const char* ace355_last_error(void) { return g_err.c_str(); }
 int ace355_version(void) { return 100; }
 
 int ace355_gemm_set_k_rotation(int mode) { return gemm_set_k_rotation(mode); }
+
+int ace355_gemm_plan(const ace355_gemm_request* r, ace355_gemm_plan_info* out) {
+    ACE_CHECK(r && out, "gemm_plan: null pointer");
+    ACE_CHECK(r->M > 0 && r->N > 0 && r->K > 0 && r->mode >= 0 && r->mode <= 4, "gemm_plan: empty problem or bad epilogue mode");
+    ACE_CHECK(r->fp8 ? gemm_mx_supported(r->M, r->N, r->K, r->mode) : r->K % 64 == 0, "gemm_plan: K must be a multiple of 64 (MXFP8: K % 128, N % 256, modes 0 2 3 4)");
+    ACE_CHECK(r->mode != 3 || r->N % 64 == 0, "gemm_plan: swiglu needs N % 64 == 0");
+    const int head = r->fp8 ? 256 : 128;
+    ACE_CHECK(r->mode != 4 || (r->hn_q_cols % head == 0 && r->hn_qk_cols % head == 0 && r->hn_qk_cols <= r->N), "gemm_plan: head epilogue arguments");
+    const bool process = r->placement == ACE355_GEMM_PLACEMENT_PROCESS;
+    ACE_CHECK(process || (r->placement >= GEMM_PLACEMENT_UNKNOWN && r->placement <= GEMM_PLACEMENT_VERIFIED), "gemm_plan: placement");
+    const GemmRequest rq{r->M, r->N, r->K, r->mode, r->fp8, r->cu_slots, r->aligned, r->counters, r->fold_producer, r->fold_consumer,
+                         r->hn_q_cols, r->hn_qk_cols, r->vt_offered, r->vt_heads, r->pf_x, r->placement};
+    GemmPrefetchRegions pf;
+    const GemmPlan p = gemm_plan_query(rq, process, &pf);
+    *out = ace355_gemm_plan_info{p.mode, p.mt, p.wnw, p.ntw, p.pers, p.ns, p.fp8, p.grid_x, p.grid_y, p.threads, p.tiles_n, p.nwg, p.group_m, p.xcd_m,
+                                 p.ksplit, p.kparts, p.sk_ord, p.krot, p.wide_ok, p.pf_x, p.head_fused, p.vt_epilogue,
+                                 pf.pf_x, pf.pf_xcd_n, pf.pf_chunk16, pf.pf_len16};
+    return ACE355_OK;
+}
 
 int ace355_box_probe_mfma(int iters, double* tflops_out) {
     ACE_CHECK(tflops_out && iters > 0 && iters <= (1 << 22), "box_probe_mfma: bad argument");

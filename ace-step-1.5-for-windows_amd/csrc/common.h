@@ -178,7 +178,7 @@ int launch_gemm_mx(const uint8_t* Aq, const uint32_t* sa, int sa_ld, const uint8
                    int M, int N, int K, const GemmEpilogue& ep, hipStream_t s);
 bool gemm_mx_supported(int M, int N, int K, int mode);
 int gemm_verify_splitk_placement();   // one-time XCD placement check behind the small-M split-K (gemm.hip); handle constructors call it
-bool gemm_fold_supported();   // the folded-RMSNorm epilogue hooks exist in the kernels launch_gemm will use (not the v1 bring-up kernel)
+int env_max_wgs();   // ACE355_MAX_WGS (default 256, 8 .. 256): the CUs launch_gemm and launch_attention plan for when the caller names none
 // x bf16 [M, K] (row stride ld) -> q fp8 e4m3 [M, K] + scales uint32 [K / 128][rows_pad] (rows_pad >= M, multiple of 4)
 int launch_mx_quant(const bf16_t* x, long ld, int M, int K, uint8_t* q, uint32_t* scales, int rows_pad, hipStream_t s);
 // rows of a packed bf16 weight matrix through e4m3 with one scale per row and back (fp8 weight-only semantics; elementwise.hip)

@@ -309,17 +309,23 @@ struct EvScope {
     }
 };
 
+// What gemm() and gemm_mx() share: the event pair and the flop / launch counts of a profiled forward.
+struct GemmScope : EvScope {
+    GemmScope(ace355_dit* h_, hipStream_t s_, int M, int N, int K) : EvScope(h_, &h_->gemm_ev, s_) {
+        if (h->profile) {
+            h->gemm_flops += 2.0 * M * N * K;
+            h->gemm_launches++;
+        }
+    }
+};
+
 int gemm(ace355_dit* h, const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, int M, int N, int K,
          const GemmEpilogue& ep, hipStream_t s) {
-    EvScope ev(h, &h->gemm_ev, s);
-    if (h->profile) {
-        h->gemm_flops += 2.0 * M * N * K;
-        h->gemm_launches++;
-    }
     GemmEpilogue e2 = ep;
+    GemmScope scope(h, s, M, N, K);
+    e2.cu_slots = h->cu_slots;
     const bool side = h->fk.side && s == h->fk.side;
     e2.sk_cnt = side ? h->fk.sk_cnt : h->sk_cnt;
-    e2.cu_slots = h->cu_slots;
     if (h->pf_next.w) {   // the GEMM that follows this one in forward_core's sequence: its weight rows start towards the L2s now (GemmEpilogue::pf_*)
         gemm_prefetch_plan(&e2, h->pf_next.w, h->pf_next.M, h->pf_next.N, h->pf_next.K, h->pf_next.mode, h->cu_slots);
         h->pf_next.w = nullptr;
@@ -338,7 +344,7 @@ int gemm(ace355_dit* h, const bf16_t* A, int lda, const bf16_t* W, int ldw, void
 
 // The same projection on the MXFP8 path: the bf16 activation operand is block-quantised (mx_quant_kernel) into the handle's scratch,
 // then the MX GEMM runs against the layer's fp8 weight copy with the bf16 kernel's epilogue.  Caller checked mx_usable().
-// A == nullptr: the producer already left the operand in the scratch as MXFP8 (launch_rmsnorm_gs_mx).
+// A == nullptr: the producer already left the operand in the scratch as MXFP8 (launch_rmsnorm_gs_mx), or in preq / pres.
 int gemm_mx(ace355_dit* h, const bf16_t* A, int lda, const MxW& W, void* C, int ldc, int M, int N, int K, const GemmEpilogue& ep,
             hipStream_t s, const uint8_t* preq = nullptr, const uint32_t* pres = nullptr) {
     if (A) {
@@ -346,21 +352,9 @@ int gemm_mx(ace355_dit* h, const bf16_t* A, int lda, const MxW& W, void* C, int 
         if (rc) return rc;
     }
     GemmEpilogue epx = ep;
+    GemmScope scope(h, s, M, N, K);
     epx.cu_slots = h->cu_slots;
-    if (preq) {
-        EvScope ev(h, &h->gemm_ev, s);
-        if (h->profile) {
-            h->gemm_flops += 2.0 * M * N * K;
-            h->gemm_launches++;
-        }
-        return launch_gemm_mx(preq, pres, h->xs_pad, W.q, W.sc, W.pad, C, ldc, M, N, K, epx, s);
-    }
-    EvScope ev(h, &h->gemm_ev, s);
-    if (h->profile) {
-        h->gemm_flops += 2.0 * M * N * K;
-        h->gemm_launches++;
-    }
-    return launch_gemm_mx(h->xq, h->xs, h->xs_pad, W.q, W.sc, W.pad, C, ldc, M, N, K, epx, s);
+    return launch_gemm_mx(preq ? preq : h->xq, preq ? pres : h->xs, h->xs_pad, W.q, W.sc, W.pad, C, ldc, M, N, K, epx, s);
 }
 bool mx_usable(const ace355_dit* h, const MxW& W, int M, int N, int K, int mode, int q_cols = 0, int qk_cols = 0) {
     static int mask = -1;  // ACE355_MX_MASK: subset of the projections that run in MXFP8 (error / time trade-offs)
@@ -465,7 +459,7 @@ int time_embed(ace355_dit* h, const float* t, const float* tr, int rows, hipStre
 bool normfold_eligible(const ace355_dit* h, int steps, int M) {
     const int D = h->D, F = h->F, QD = h->QD, QKV = h->QD + 2 * h->KVD;
     const bool mx = h->precision == ACE355_PRECISION_MXFP8 && M >= h->mx_min_rows;
-    return h->nf.enabled && gemm_fold_supported() && !mx && M >= (h->nf.enabled >= 2 ? 64 : h->nf.min_rows) && D % 256 == 0 && QKV % 256 == 0 && QD % 256 == 0 && (2 * F) % 256 == 0 && h->KVD % 128 == 0 &&
+    return h->nf.enabled && !mx && M >= (h->nf.enabled >= 2 ? 64 : h->nf.min_rows) && D % 256 == 0 && QKV % 256 == 0 && QD % 256 == 0 && (2 * F) % 256 == 0 && h->KVD % 128 == 0 &&
            steps <= 1024;
 }
 // (allocation: outside any stream capture, next to ensure_workspace)
@@ -652,7 +646,7 @@ int forward_core(ace355_dit* h, int N, int T, const int* slots, int temb_rows, h
         // the o_proj GEMM reads that half's attention output for both (GemmEpilogue::a_wrap); its epilogue (gate, constant term of the
         // null rows, the two folded norms) is per row as always.  ace355_dit_set_dedup(h, 0) / ACE355_DEDUP0=0 switch it off (A/B, tests).
         const bool dedup0 = li == 0 && h->dup_half && h->dedup_on && temb_rows == 1 && Nc > 0 && N == 2 * Nc && h->precision != ACE355_PRECISION_MXFP8 &&
-                            !h->tap_dst[0] && gemm_fold_supported();
+                            !h->tap_dst[0];
         const int Mq = dedup0 ? Mc : M, Nq = dedup0 ? Nc : N;   // rows / sequences the self-attention half of this layer computes
         if (dedup0) h->dedup_forwards++;
         const bool mx_qkv = mx_usable(h, W.mx_qkv, M, QKV, D, 4, QD, QD + KVD) && D == 2048;

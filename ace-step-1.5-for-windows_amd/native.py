@@ -80,6 +80,22 @@ class VaeStageInfoC(C.Structure):
     ]
 
 
+class GemmRequestC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "M", "N", "K", "mode", "fp8", "cu_slots", "aligned", "counters", "fold_producer", "fold_consumer", "hn_q_cols", "hn_qk_cols",
+        "vt_offered", "vt_heads", "pf_x", "placement")]
+
+
+class GemmPlanInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "mode", "mt", "wnw", "ntw", "pers", "ns", "fp8", "grid_x", "grid_y", "threads", "tiles_n", "nwg", "group_m", "xcd_m",
+        "ksplit", "kparts", "sk_ord", "krot", "wide_ok", "pf_x", "head_fused", "vt_epilogue", "next_pf_x", "next_pf_xcd_n")] + [
+        ("next_pf_chunk16", C.c_uint32), ("next_pf_len16", C.c_uint32)]
+
+
+GEMM_PLACEMENT_PROCESS = -2   # ACE355_GEMM_PLACEMENT_PROCESS
+
+
 # ACE355_VAE_STAGE_* / ACE355_VAE_FLAG_* of include/ace355.h
 VAE_STAGE_INPUT, VAE_STAGE_CONV_IN, VAE_STAGE_CONVT, VAE_STAGE_UNIT, VAE_STAGE_UNIT_K7, VAE_STAGE_UNIT_K1, VAE_STAGE_DOWN, VAE_STAGE_HEAD = range(8)
 VAE_FLAG_IN_SNAKE, VAE_FLAG_OUT_SNAKE, VAE_FLAG_FUSED, VAE_FLAG_F32_NCL = 1, 2, 4, 8
@@ -121,6 +137,7 @@ SIGNATURES = {
     "ace355_dit_set_norm_fold": (C.c_int, [C.c_void_p, C.c_int]),
     "ace355_box_probe_mfma": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "ace355_gemm_set_k_rotation": (C.c_int, [C.c_int]),
+    "ace355_gemm_plan": (C.c_int, [C.POINTER(GemmRequestC), C.POINTER(GemmPlanInfoC)]),
     "ace355_dit_set_dual": (C.c_int, [C.c_void_p, C.c_int]),
     "ace355_dit_dual_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ace355_dit_set_dedup": (C.c_int, [C.c_void_p, C.c_int]),
@@ -245,6 +262,18 @@ def gemm_set_k_rotation(mode: int) -> int:
     """`ace355_gemm_set_k_rotation` (include/ace355.h): 0 off, 1 launches with N <= 2048 (default), 2 every one-round launch; returns the
     previous mode.  Process-wide."""
     return int(lib().ace355_gemm_set_k_rotation(int(mode)))
+
+
+def gemm_plan(M: int, N: int, K: int, mode: int, **fields) -> dict:
+    """`ace355_gemm_plan` (include/ace355.h): the launch the GEMM entry points would make for a request, as a dict of the plan's fields.
+    Fields not given are 0, except aligned operands and this process's placement state."""
+    rq = GemmRequestC(M=M, N=N, K=K, mode=mode, aligned=1, placement=GEMM_PLACEMENT_PROCESS)
+    for k, v in fields.items():
+        assert hasattr(rq, k), k
+        setattr(rq, k, int(v))
+    out = GemmPlanInfoC()
+    check(lib().ace355_gemm_plan(C.byref(rq), C.byref(out)), "gemm_plan")
+    return {n: int(getattr(out, n)) for n, _t in GemmPlanInfoC._fields_}
 
 
 def current_stream_ptr() -> int:

@@ -61,6 +61,33 @@ int ace355_box_probe_mfma(int iters, double* tflops_out);
  * depends on how many sequences share them), so a song computed alone and inside a larger batch agree bit for bit wherever both runs take
  * the GQA kernels (tests/test_metric_shapes_gpu.py::test_120s_forward_vs_reference_golden_and_batch16). */
 int ace355_gemm_set_k_rotation(int mode);
+/* Which launch the bf16 / MXFP8 GEMM entry points would make for a request (no reference counterpart; a test and review aid): the
+ * library's launch decision is one pure function of the request and the process's ACE355_GEMM_* switches, and this call evaluates it.
+ * No GPU is touched.  Fields are the library's GemmRequest / GemmPlan (csrc/gemm_plan.h), where each is described. */
+#define ACE355_GEMM_PLACEMENT_PROCESS (-2) /* placement: what this process found (unknown until a handle or a residual GEMM asked) */
+typedef struct ace355_gemm_request {
+    int32_t M, N, K;
+    int32_t mode;           /* 0 store bf16, 1 store f32, 2 residual into f32, 3 SwiGLU, 4 QKV with head-norm + RoPE */
+    int32_t fp8;            /* 1: MXFP8 operands (modes 0 / 2 / 3 / 4, K % 128 == 0, N % 256 == 0) */
+    int32_t cu_slots;       /* 8 .. 256: plan for that many CUs; 0: ACE355_MAX_WGS */
+    int32_t aligned;        /* output and per-column vectors are 16-byte aligned */
+    int32_t counters;       /* split-K turn counters are lent (the handles and the residual entry points do) */
+    int32_t fold_producer, fold_consumer;
+    int32_t hn_q_cols, hn_qk_cols;
+    int32_t vt_offered, vt_heads;
+    int32_t pf_x;           /* prefetch workgroups per XCD attached for the next launch's weights, 0: none */
+    int32_t placement;      /* -1 unknown, 0 refused, 1 verified, or ACE355_GEMM_PLACEMENT_PROCESS */
+} ace355_gemm_request;
+typedef struct ace355_gemm_plan_info {
+    int32_t mode, mt, wnw, ntw, pers, ns, fp8;                      /* gemm_sp_kernel<mode, mt, wnw, ntw, pers, ns, fp8> */
+    int32_t grid_x, grid_y, threads, tiles_n, nwg, group_m, xcd_m;  /* launch geometry and tile map */
+    int32_t ksplit, kparts, sk_ord, krot, wide_ok, pf_x;            /* epilogue fields the launcher sets */
+    int32_t head_fused, vt_epilogue;
+    /* the XCD column regions a PRECEDING launch would be given to prefetch this request's weights (all 0: none attached) */
+    int32_t next_pf_x, next_pf_xcd_n;
+    uint32_t next_pf_chunk16, next_pf_len16;
+} ace355_gemm_plan_info;
+int ace355_gemm_plan(const ace355_gemm_request* request, ace355_gemm_plan_info* plan_out);
 
 /* ------------------------------------------------------------------------------------------
  * DiT decoder (AceStepDiTModel, base.py:1240-1507) + sampler (generate_audio, base.py:1783-1989)

@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _gemm_plan_cases as _plan_cases
+
 pytestmark = pytest.mark.gpu
 
 
@@ -380,7 +382,10 @@ def test_gemm_tile_forms_give_the_same_bits(gpu_device, tmp_path):
         "native.gemm_set_k_rotation(0)\n"
         "g = torch.Generator().manual_seed(11)\n"
         "outs = []\n"
-        "for M, N, K in ((6000, 2048, 2048), (1536, 2048, 6144)):\n"
+        "want = %r[sys.argv[2]]   # per shape: the (MT, WNW, NTW, PERS, NS, split-K) its launch must take in this process\n"
+        "for (M, N, K), regime in zip(%r, want):\n"
+        "    p = native.gemm_plan(M, N, K, 1, counters=1)\n"
+        "    assert (p['mt'], p['wnw'], p['ntw'], p['pers'], p['ns'], p['ksplit'] > 1) == regime and p['krot'] == 0, (sys.argv[2], p)\n"
         "    A = torch.randn(M, K, generator=g).to(torch.bfloat16).to(dev); W = (torch.randn(N, K, generator=g) * 0.05).to(torch.bfloat16).to(dev)\n"
         "    o = torch.empty(M, N, device=dev)\n"
         "    native.check(lib.ace355_gemm_bf16(P(A), P(W), P(o), M, N, K, 0, None, None)); torch.cuda.synchronize()\n"
@@ -388,11 +393,11 @@ def test_gemm_tile_forms_give_the_same_bits(gpu_device, tmp_path):
         "    assert float((o - ref).norm() / ref.norm()) < 2e-5\n"
         "    outs.append(o.cpu())\n"
         "torch.save(outs, sys.argv[1])\n"
-    ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),)
+    ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), _plan_cases.TILE_FORM_OF_BIG, _plan_cases.TILE_FORMS)
     res = {}
     for flag in ("0", "2", "3"):
         path = str(tmp_path / f"big{flag}.pt")
-        r = subprocess.run([sys.executable, "-c", code, path], env=dict(os.environ, ACE355_GEMM_BIG=flag, ACE355_GEMM_CLK="0"), capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, "-c", code, path, flag], env=dict(os.environ, ACE355_GEMM_BIG=flag, ACE355_GEMM_CLK="0"), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         res[flag] = torch.load(path)
     for flag in ("2", "3"):
@@ -400,20 +405,21 @@ def test_gemm_tile_forms_give_the_same_bits(gpu_device, tmp_path):
             assert torch.equal(a, b), f"ACE355_GEMM_BIG={flag} differs from the 4-wave tiles: max abs {float((a - b).abs().max()):.3e}"
 
 
-@pytest.mark.parametrize("kind,M,N,K,reps", [
-    # the 4-wave two-stage kernels with two workgroups per CU (more tiles than CUs, too few for the 8-wave forms): the regime whose launches were not
-    # reproducible until round 6 (MFMA destination overlapping srcB; consecutive MFMAs sharing srcA beside a co-resident bf16 epilogue)
-    ("swiglu", 400, 12288, 2048, 16), ("swiglu", 288, 12288, 2048, 16), ("store_bf16", 520, 8192, 2048, 16), ("headnorm", 520, 8192, 2048, 16),
-    ("store_f32", 520, 8192, 2048, 8), ("residual", 520, 8192, 2048, 8),
-    # deep-pipeline 4-wave kernels (one workgroup per CU), 64-row tiles, ordered split-K
-    ("swiglu", 48, 12288, 2048, 8), ("headnorm", 400, 4096, 2048, 8), ("residual", 400, 2048, 6144, 8), ("residual", 375, 2048, 2048, 8),
-    # the 8-wave pair loops at the metric batch (persistent 192x256, one-round 192x256, 192x128)
-    ("swiglu", 6000, 12288, 2048, 4), ("headnorm", 6000, 4096, 2048, 4), ("residual", 6000, 2048, 6144, 4), ("store_bf16", 400, 12288, 2048, 8),
-])
+# (kind, M, N, K, reps) and the regime each row was chosen for live in tests/_gemm_plan_cases.py (BIT_REPRODUCIBLE), beside the plan table
+@pytest.mark.parametrize("kind,M,N,K,reps", [row[:5] for row in _plan_cases.BIT_REPRODUCIBLE])
 def test_gemm_launches_are_bit_reproducible(lib, gpu_device, kind, M, N, K, reps):
     """Every epilogue mode in every tile regime of launch_gemm, `reps` launches on the same operands: ONE result (the
     condition encoder's gate|up launch returned different bits on every call and nothing in the suite launched that instantiation with a long K loop),
     and the result is the right one (fp32 torch)."""
+    from ace355 import native
+    regime = {row[:4]: row[5] for row in _plan_cases.BIT_REPRODUCIBLE}[(kind, M, N, K)]
+    if kind == "residual":   # (the entry point lends turn counters and runs the one-time placement check on its first call: plan after it)
+        a0, w0 = torch.zeros(64, 64, device=gpu_device, dtype=torch.bfloat16), torch.zeros(128, 64, device=gpu_device, dtype=torch.bfloat16)
+        h0 = torch.zeros(64, 128, device=gpu_device)
+        _chk(lib.ace355_gemm_bf16_residual(_p(a0), _p(w0), _p(h0), 64, 128, 64, None, None, 0, 64, None, 0, None))
+    p = native.gemm_plan(**_plan_cases.entry_request(kind, M, N, K))
+    assert (p["mt"], p["wnw"], p["ntw"], p["pers"], p["ns"], p["ksplit"] > 1) == regime, f"{kind} M={M} N={N} K={K} no longer launches the instantiation this row is for: {p}"
+    assert kind != "headnorm" or p["head_fused"]
     g = torch.Generator().manual_seed(M + N + K)
     A = _bf(torch.randn(M, K, generator=g)).to(gpu_device)
     W = _bf(torch.randn(N, K, generator=g) * 0.05).to(gpu_device)

@@ -2,7 +2,7 @@
 """Micro-benchmarks of the hot kernels at the DiT/VAE shapes of the metric config (runs on the GPU box).
 
 Within-process interleaved timing (cdna guide 5.4 rule 24), random bf16 data (rule 25).  Prints TF/s per shape.
-Usage: python tools/bench_kernels.py [gemm] [attn] [conv]   (env ACE355_GEMM=v1 selects the register-staged GEMM)
+Usage: python tools/bench_kernels.py [gemm] [attn] [conv]
 """
 import os
 import sys
@@ -94,7 +94,6 @@ def bench_conv():
 
 if __name__ == "__main__":
     which = sys.argv[1:] or ["gemm", "attn", "conv"]
-    print("variant:", os.environ.get("ACE355_GEMM", "v2 (glds)"))
     if "gemm" in which:
         bench_gemm()
     if "attn" in which:

@@ -14,7 +14,7 @@ run ACE355_GEMM_KSPLIT=1
 run ACE355_GEMM_MT1=0
 run ACE355_GEMM_KROT=0
 run ACE355_GEMM_DEEP=0
-run ACE355_GEMM=v1
+run ACE355_GEMM=v1   # (as recorded in profiles/r06_cond_repro.txt; the v1 kernel was deleted since and the switch is no longer read)
 run ACE355_GEMM_HEADEPI=0
 run ACE355_ATTN_GQA=0
 echo "=== dirty memory"
