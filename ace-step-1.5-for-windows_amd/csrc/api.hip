@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/ace355.h"
+#include "attn_plan.h"
 #include "gemm_plan.h"
 #include <dlfcn.h>
 #include <stdlib.h>
@@ -115,6 +116,14 @@ int ace355_gemm_plan(const ace355_gemm_request* r, ace355_gemm_plan_info* out) {
     *out = ace355_gemm_plan_info{p.mode, p.mt, p.wnw, p.ntw, p.pers, p.ns, p.fp8, p.grid_x, p.grid_y, p.threads, p.tiles_n, p.nwg, p.group_m, p.xcd_m,
                                  p.ksplit, p.kparts, p.sk_ord, p.krot, p.wide_ok, p.pf_x, p.head_fused, p.vt_epilogue,
                                  pf.pf_x, pf.pf_xcd_n, pf.pf_chunk16, pf.pf_len16};
+    return ACE355_OK;
+}
+
+int ace355_attn_plan(const ace355_attn_request* r, ace355_attn_plan_info* out) {
+    ACE_CHECK(r && out, "attn_plan: null pointer");
+    ACE_CHECK(r->N > 0 && r->Sq > 0 && r->Skv > 0 && r->Hq > 0 && r->Hkv > 0 && r->Hq % r->Hkv == 0 && r->part_floats >= 0, "attn_plan: empty problem or Hq % Hkv");
+    const AttnPlan p = attn_plan_query(AttnRequest{r->N, r->Sq, r->Skv, r->Hq, r->Hkv, r->window, r->cu_slots, r->has_kv_len, r->mx_out, (long)r->part_floats});
+    *out = ace355_attn_plan_info{p.kernel, p.nw, p.grid_x, p.grid_y, p.grid_z, p.threads, p.kv_split, p.merge_grid, p.mx_out_ok};
     return ACE355_OK;
 }
 
@@ -358,13 +367,7 @@ static int attention_hook(const void* q, const void* k, const void* v, void* out
     bf16_t* vt = (bf16_t*)t.p[2];
     int rc = launch_transpose_v((const bf16_t*)v, Hkv * 128, 0, N, Skv, Hkv, vt, Sp, s);
     if (!rc) {
-        AttnArgs a{};
-        a.q = (const bf16_t*)q; a.q_seq_stride = (long)Sq * Hq * 128; a.q_row_stride = Hq * 128;
-        a.k = (const bf16_t*)k; a.k_seq_stride = (long)Skv * Hkv * 128; a.k_head_stride = 128; a.k_row_stride = Hkv * 128;
-        a.vt = vt; a.vt_seq_stride = (long)Hkv * 128 * Sp; a.vt_head_stride = 128L * Sp; a.vt_ld = Sp;
-        a.use_tab = 0;
-        a.out = (bf16_t*)out; a.o_seq_stride = (long)Sq * Hq * 128; a.o_row_stride = Hq * 128;
-        a.N = N; a.Sq = Sq; a.Skv = Skv; a.Hq = Hq; a.Hkv = Hkv; a.window = window; a.scale = scale;
+        AttnArgs a = attn_args_rows((const bf16_t*)q, Hq * 128, (const bf16_t*)k, Hkv * 128, vt, Sp, (bf16_t*)out, N, Sq, Skv, Hq, Hkv, window, scale);
         a.kv_len = kvl; a.vmean = vmean;
         // the hook lends the split-KV scratch the DiT handle lends (small problems then take the product's split path)
         const long part_floats = 16L << 20;

@@ -8,6 +8,7 @@
 // (register-staged K/V tiles, 8-byte V^T fragment reads, one LDS buffer and two barriers per tile; "attention v2" in DESIGN.md)
 // was replaced by it and removed from the source (git history).
 #include "common.h"
+#include "attn_plan.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1100,21 +1101,44 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
 
 }  // namespace
 
-static int gqa_nwh(const AttnArgs& a) {  // which attn_gqa_kernel instantiation launch_attention picks (0: attn3_kernel)
-    static int gqa_env = -2;
-    if (gqa_env == -2) { const char* e = getenv("ACE355_ATTN_GQA"); gqa_env = e ? atoi(e) : -1; }
-    if (a.Hq != 2 * a.Hkv || gqa_env == 0) return 0;
-    auto units = [&](int nwh) { return (long)a.N * a.Hkv * ((a.Sq + 32 * nwh - 1) / (32 * nwh)); };
-    if (gqa_env == 3 || gqa_env == 4 || gqa_env == 6) return gqa_env;
-    static int cus_env = -1;   // AttnArgs::cu_slots, else ACE355_MAX_WGS (gemm.hip): plan for this many CUs instead of 256
-    if (cus_env < 0) cus_env = env_max_wgs();
-    const int cus = (a.cu_slots >= 8 && a.cu_slots <= 256) ? a.cu_slots : cus_env;
-    if (units(6) >= 224 * cus / 256) return 6;
-    if (units(4) >= 224 * cus / 256) return 4;
-    if (units(3) >= 128 * cus / 256) return 3;
+const AttnKnobs& attn_knobs() {
+    static const AttnKnobs kn = [] {
+        auto env = [](const char* name, const char* dflt) { const char* e = getenv(name); return e ? e : dflt; };
+        return AttnKnobs{atoi(env("ACE355_ATTN_GQA", "-1")), atoi(env("ACE355_ATTN_ROT", "1")), atoi(env("ACE355_ATTN_NW", "0")),
+                         atoi(env("ACE355_ATTN_KVSPLIT", "0")), (float)atof(env("ACE355_ATTN_DEFER", "8")), atoi(env("ACE355_ATTN_CLK", "0")),
+                         env_max_wgs(), 0};
+    }();
+    return kn;
+}
+
+// The six instantiations a plan can name (in the order the code object has always held them).
+using AttnKernel = void (*)(AttnArgs, float, float);
+static const struct { int kernel, nw; AttnKernel fn; const char* tag; } g_attn_kernels[] = {
+    {ATTN_KERNEL_ROT, 3, attn_rot_kernel<3>, "rot<3>"},  {ATTN_KERNEL_GQA, 6, attn_gqa_kernel<6>, "gqa<6>"},
+    {ATTN_KERNEL_GQA, 4, attn_gqa_kernel<4>, "gqa<4>"},  {ATTN_KERNEL_GQA, 3, attn_gqa_kernel<3>, "gqa<3>"},
+    {ATTN_KERNEL_ATTN3, 8, attn3_kernel<8>, "attn3<8>"}, {ATTN_KERNEL_ATTN3, 4, attn3_kernel<4>, "attn3<4>"}};
+
+AttnPlan attn_plan_query(const AttnRequest& rq) {
+    AttnKnobs kn = attn_knobs();
+    kn.one_order = gemm_k_rotation_mode() == 0;   // gemm_knobs().krot, at call time
+    return plan_attention(rq, kn);
+}
+static AttnPlan plan_of(const AttnArgs& a) {
+    return attn_plan_query(AttnRequest{a.N, a.Sq, a.Skv, a.Hq, a.Hkv, a.window, a.cu_slots, a.kv_len != nullptr, a.out_q != nullptr,
+                                       a.part ? a.part_floats : 0});
+}
+bool attention_mx_out_ok(const AttnArgs& a) { return plan_of(a).mx_out_ok != 0; }
+
+// ACE355_ATTN_CLK: what the probed wave of the last launch recorded (the kernels that do not record a column leave it 0)
+static int report_clk(const char* tag, const AttnArgs& a, hipStream_t s) {
+    unsigned long long hh[8] = {0};
+    ACE_HIP(hipStreamSynchronize(s));
+    ACE_HIP(hipMemcpyFromSymbol(hh, HIP_SYMBOL(g_attn_probe), sizeof(hh)));
+    if (hh[1]) fprintf(stderr, "[ace355 attn clk] %s N=%d Sq=%d Skv=%d win=%d flags=%d: %.3f GHz, loop %.0f cycles (%.2f us), %.0f cycles/tile, wait+barrier %.0f cycles/tile; prologue %.0f cycles, whole wave %.0f cycles\n",
+                       tag, a.N, a.Sq, a.Skv, a.window, a.clk_probe, (double)hh[0] / ((double)hh[1] * 10.0), (double)hh[0], (double)hh[1] * 0.01,
+                       (double)hh[0] / (double)hh[3], (double)hh[2] / (double)hh[3], (double)hh[4], (double)hh[5]);
     return 0;
 }
-bool attention_mx_out_ok(const AttnArgs& a) { return gqa_nwh(a) != 0 && !a.kv_len; }
 
 int launch_attention(const AttnArgs& a, hipStream_t s) {
     ACE_CHECK(a.N > 0 && a.Sq > 0 && a.Skv > 0, "attention: empty problem");
@@ -1122,114 +1146,26 @@ int launch_attention(const AttnArgs& a, hipStream_t s) {
     ACE_CHECK(a.Hq % a.Hkv == 0, "attention: Hq % Hkv");
     ACE_CHECK(a.vt_ld % 64 == 0 && a.vt_ld >= ((a.Skv + 63) / 64) * 64, "attention: V^T row stride must be a padded multiple of 64");
     ACE_CHECK(a.q_row_stride % 8 == 0 && a.k_row_stride % 8 == 0 && a.o_row_stride % 4 == 0, "attention: strides");
-    const float scale_log2 = a.scale * 1.4426950408889634f;
     ACE_CHECK(!a.kv_len || a.vmean, "attention: kv_len needs vmean");
     ACE_CHECK((a.o_row_stride % 8) == 0, "attention: output rows must be 16-byte aligned");
-    // 2 waves per SIMD (256-VGPR budget): 4-wave blocks (128 queries, two workgroups per CU) by default; 8-wave blocks
-    // (256 queries, K/V staged once per 256 rows) when the sequence is long enough to fill the chip with them
-    static float thr = -1.f;  // deferred-rescale threshold in log2 units (ACE355_ATTN_DEFER; 0 = rescale whenever a max moves)
-    if (thr < 0.f) { const char* e = getenv("ACE355_ATTN_DEFER"); thr = e ? (float)atof(e) : 8.0f; }
-    static int nw_env = -1, clk = -1;
-    if (nw_env < 0) { const char* e = getenv("ACE355_ATTN_NW"); nw_env = e ? atoi(e) : 0; }
-    if (clk < 0) { const char* e = getenv("ACE355_ATTN_CLK"); clk = e ? atoi(e) : 0; }
-    // GQA-shared kernel (Hq = 2 Hkv): one workgroup per (sequence, KV head, 32*NWH query rows), both q heads off one K / V^T
-    // tile.  NWH = the largest of {6, 4, 3} whose grid still gives every CU a workgroup (ACE355_ATTN_GQA=0: attn3_kernel only,
-    // =3/4/6 pins NWH); attn3_kernel keeps the small problems (fewer than 128 such workgroups) and other group sizes.
-    ACE_CHECK(!a.out_q || (attention_mx_out_ok(a) && a.out_scales && a.o_seq_stride == (long)a.Sq * a.Hq * 128), "attention: MXFP8 output needs the GQA kernel and a dense [N*Sq, Hq*128] output");
-    {
-        auto units = [&](int nwh) { return (long)a.N * a.Hkv * ((a.Sq + 32 * nwh - 1) / (32 * nwh)); };
-        const int nwh = gqa_nwh(a);
-        // rotated key-split kernel (12 waves per 96-row block): where the 6-wave GQA kernel would run (the metric's cross-attention),
-        // ACE355_ATTN_ROT=2 also where the 192- / 128-row kernels would (A/B of the self-attention launches), =0 never
-        static int rot_env = -1;
-        if (rot_env < 0) { const char* e = getenv("ACE355_ATTN_ROT"); rot_env = e ? atoi(e) : 1; }
-        // (the key-split kernel merges two partial softmaxes per row: another fp32 summation order than the one-walk kernels.  Which kernel
-        //  a sequence gets depends on how many sequences share the launch, so with ace355_gemm_set_k_rotation(0) - "one summation order
-        //  whatever the launch shape" - it stays off: a song alone and inside a batch then take the same per-row arithmetic again)
-        if (nwh && !a.out_q && gemm_k_rotation_mode() != 0 && (rot_env >= 2 || (rot_env == 1 && nwh == 3))) {
-            AttnArgs ap = a;
-            ap.clk_probe = clk;
-            const long total = units(3);
-            const dim3 grid((unsigned)((total + 7) / 8 * 8));
-            hipLaunchKernelGGL((attn_rot_kernel<3>), grid, dim3(768), 0, s, ap, scale_log2, thr);
-            ACE_LAUNCH_CHECK();
-            if (clk) {
-                unsigned long long hh[8] = {0};
-                ACE_HIP(hipStreamSynchronize(s));
-                ACE_HIP(hipMemcpyFromSymbol(hh, HIP_SYMBOL(g_attn_probe), sizeof(hh)));
-                if (hh[1]) fprintf(stderr, "[ace355 attn-rot clk] N=%d Sq=%d Skv=%d win=%d: %.3f GHz, loop %.0f cycles (%.2f us), %.0f cycles/tile; prologue %.0f cycles, whole wave %.0f cycles\n",
-                                   a.N, a.Sq, a.Skv, a.window, (double)hh[0] / ((double)hh[1] * 10.0), (double)hh[0], (double)hh[1] * 0.01,
-                                   (double)hh[0] / (double)hh[3], (double)hh[4], (double)hh[5]);
-            }
-            return 0;
-        }
-        if (nwh) {
-            AttnArgs ap = a;
-            ap.clk_probe = clk;  // bit 0: probe + print; bits 1..3: ablations (attn_gqa_kernel)
-            const long total = units(nwh);
-            const dim3 grid((unsigned)((total + 7) / 8 * 8));  // 1-D: the kernel decodes (q-block, KV head, sequence) XCD-aware
-            if (nwh == 6) hipLaunchKernelGGL(attn_gqa_kernel<6>, grid, dim3(768), 0, s, ap, scale_log2, thr);
-            else if (nwh == 4) hipLaunchKernelGGL(attn_gqa_kernel<4>, grid, dim3(512), 0, s, ap, scale_log2, thr);
-            else hipLaunchKernelGGL(attn_gqa_kernel<3>, grid, dim3(384), 0, s, ap, scale_log2, thr);
-            ACE_LAUNCH_CHECK();
-            if (clk) {
-                unsigned long long hh[8] = {0};
-                ACE_HIP(hipStreamSynchronize(s));
-                ACE_HIP(hipMemcpyFromSymbol(hh, HIP_SYMBOL(g_attn_probe), sizeof(hh)));
-                if (hh[1]) fprintf(stderr, "[ace355 attn-gqa clk] NWH=%d N=%d Sq=%d Skv=%d win=%d flags=%d: %.3f GHz, loop %.0f cycles (%.2f us), %.0f cycles/tile, wait+barrier %.0f cycles/tile; prologue %.0f cycles\n",
-                                   nwh, a.N, a.Sq, a.Skv, a.window, clk, (double)hh[0] / ((double)hh[1] * 10.0), (double)hh[0], (double)hh[1] * 0.01,
-                                   (double)hh[0] / (double)hh[3], (double)hh[2] / (double)hh[3], (double)hh[4]);
-            }
-            return 0;
-        }
-    }
-    const long heads = (long)a.Hq * a.N;
-    int nw = (a.Sq >= 1024 && heads * ((a.Sq + 255) / 256) >= 512) ? 8 : 4;
-    if (nw_env == 4 || nw_env == 8) nw = nw_env;
-    const int qbk = nw * 32;
-    const int nqb = (a.Sq + qbk - 1) / qbk;
+    const AttnPlan p = plan_of(a);
+    ACE_CHECK(!a.out_q || (p.mx_out_ok && a.out_scales && a.o_seq_stride == (long)a.Sq * a.Hq * 128), "attention: MXFP8 output needs the GQA kernel and a dense [N*Sq, Hq*128] output");
+    AttnKernel fn = nullptr;
+    const char* tag = "";
+    for (const auto& r : g_attn_kernels)
+        if (r.kernel == p.kernel && r.nw == p.nw) fn = r.fn, tag = r.tag;
+    ACE_CHECK(fn, "attention: the plan names no kernel instantiation");
+    const AttnKnobs& kn = attn_knobs();
     AttnArgs ap = a;
-    ap.clk_probe = clk;
-    // split-KV: few workgroups, each with a long serial walk over the key tiles (batch-1 requests) -> up to 8 workgroups per
-    // (q-block, head, sequence), at least two tiles each, about one workgroup per CU in total; needs the caller's scratch and no
-    // key-padding mask (the all-masked-row rule of the encoders lives in the one-pass epilogue)
-    ap.kv_split = 1;
-    {
-        static int split_env = -1;
-        if (split_env < 0) { const char* e = getenv("ACE355_ATTN_KVSPLIT"); split_env = e ? atoi(e) : 0; }  // 0 heuristic, 1 off, n forced
-        const long wgs = (long)nqb * heads;
-        int tiles = (a.Skv + KB - 1) / KB;
-        if (a.window >= 0) tiles = std::min(tiles, (qbk + 2 * a.window + KB - 1) / KB + 1);
-        int sp = 1;
-        // (measured at batch 1, S = 375: the 13-tile cross-attention walk 22.2 -> 13.9 + 5.2 us in 4 parts; the 6-tile self-attention
-        //  14.1 -> 12.9 + 5.1 us in 2 parts, a loss: the fp32 partials and the merge launch cost ~8 us, so only long walks split)
-        // (K rotation mode 0, "one summation order whatever the launch shape": no split either - the merge of partial softmaxes is another order)
-        if (nw == 4 && a.part && !a.kv_len && !a.out_q && wgs < 128 && tiles >= 8 && gemm_k_rotation_mode() != 0) {
-            while (sp < 8 && wgs * sp * 2 <= 256 && tiles / (sp * 2) >= 2) sp *= 2;
-            if (split_env >= 1) sp = split_env;
-            if ((long)sp * a.N * a.Hq * a.Sq * 132 > a.part_floats) sp = 1;
-        }
-        ap.kv_split = sp;
-    }
-    dim3 grid(nqb * ap.kv_split, a.Hq, a.N);
-    if (nw == 8) hipLaunchKernelGGL(attn3_kernel<8>, grid, dim3(512), 0, s, ap, scale_log2, thr);
-    else hipLaunchKernelGGL(attn3_kernel<4>, grid, dim3(256), 0, s, ap, scale_log2, thr);
+    ap.clk_probe = kn.clk;
+    ap.kv_split = p.kv_split;
+    hipLaunchKernelGGL(fn, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(p.threads), 0, s, ap, a.scale * 1.4426950408889634f, kn.defer);
     ACE_LAUNCH_CHECK();
-    if (ap.kv_split > 1) {
-        const long units = (long)a.N * a.Hq * a.Sq;
-        hipLaunchKernelGGL(attn_merge_kernel, dim3((unsigned)((units + 7) / 8)), dim3(256), 0, s, a.part, ap.kv_split, a.N, a.Hq, a.Sq, a.out,
-                           a.o_seq_stride, a.o_row_stride);
+    if (p.merge_grid) {
+        hipLaunchKernelGGL(attn_merge_kernel, dim3(p.merge_grid), dim3(256), 0, s, a.part, p.kv_split, a.N, a.Hq, a.Sq, a.out, a.o_seq_stride, a.o_row_stride);
         ACE_LAUNCH_CHECK();
     }
-    if (clk) {
-        unsigned long long hh[8] = {0};
-        ACE_HIP(hipStreamSynchronize(s));
-        ACE_HIP(hipMemcpyFromSymbol(hh, HIP_SYMBOL(g_attn_probe), sizeof(hh)));
-        if (hh[1]) fprintf(stderr, "[ace355 attn clk] N=%d Sq=%d Skv=%d win=%d: %.3f GHz, loop %.0f cycles (%.2f us), %.0f cycles/tile, wait+barrier %.0f cycles/tile; prologue %.0f cycles, whole wave %.0f cycles\n",
-                           a.N, a.Sq, a.Skv, a.window, (double)hh[0] / ((double)hh[1] * 10.0), (double)hh[0], (double)hh[1] * 0.01,
-                           (double)hh[0] / (double)hh[3], (double)hh[2] / (double)hh[3], (double)hh[4], (double)hh[5]);
-    }
-    return 0;
+    return kn.clk ? report_clk(tag, ap, s) : 0;
 }
 
 }  // namespace ace355

@@ -220,7 +220,24 @@ struct AttnArgs {
     int cu_slots;   // host-side hint, as GemmEpilogue::cu_slots: 0 = plan for the whole chip
 };
 int launch_attention(const AttnArgs& a, hipStream_t s);
-bool attention_mx_out_ok(const AttnArgs& a);  // will launch_attention take the kernel that can write MXFP8?
+bool attention_mx_out_ok(const AttnArgs& a);  // AttnPlan::mx_out_ok of a's request: will launch_attention take a kernel that can write MXFP8?
+// The q and output half of the layout every caller shares: q rows of a row-major matrix (row stride q_ld, a head's 128 columns side by side
+// from the pointer given) and a dense output [N * Sq, Hq * 128].  K, V^T and every other field are zero, for the caller to set.
+inline AttnArgs attn_args_q_out(const bf16_t* q, int q_ld, bf16_t* out, int N, int Sq, int Skv, int Hq, int Hkv, int window, float scale) {
+    AttnArgs a{};
+    a.q = q; a.q_seq_stride = (long)Sq * q_ld; a.q_row_stride = q_ld;
+    a.out = out; a.o_seq_stride = (long)Sq * Hq * 128; a.o_row_stride = Hq * 128;
+    a.N = N; a.Sq = Sq; a.Skv = Skv; a.Hq = Hq; a.Hkv = Hkv; a.window = window; a.scale = scale;
+    return a;
+}
+// ... with k rows of a row-major matrix (row stride k_ld) and V^T [N][Hkv][128][Sp]: the self-attention callers and the unit hooks
+inline AttnArgs attn_args_rows(const bf16_t* q, int q_ld, const bf16_t* k, int k_ld, const bf16_t* vt, int Sp, bf16_t* out, int N, int Sq,
+                               int Skv, int Hq, int Hkv, int window, float scale) {
+    AttnArgs a = attn_args_q_out(q, q_ld, out, N, Sq, Skv, Hq, Hkv, window, scale);
+    a.k = k; a.k_seq_stride = (long)Skv * k_ld; a.k_head_stride = 128; a.k_row_stride = k_ld;
+    a.vt = vt; a.vt_seq_stride = (long)Hkv * 128 * Sp; a.vt_head_stride = 128L * Sp; a.vt_ld = Sp;
+    return a;
+}
 
 struct ModEntry {  // one modulated norm: g = w * (1 + sc1 + tproj[sc2_off..]), sft = sh1 + tproj[sh2_off..]
     const float *w, *sc1, *sh1;

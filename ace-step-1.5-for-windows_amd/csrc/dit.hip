@@ -680,15 +680,8 @@ int forward_core(ace355_dit* h, int N, int T, const int* slots, int temb_rows, h
         }
         bool ao_is_mx = false;
         {
-            AttnArgs a{};
-            a.q = h->qkv; a.q_seq_stride = (long)S * QKV; a.q_row_stride = QKV;
-            a.k = h->qkv + QD; a.k_seq_stride = (long)S * QKV; a.k_head_stride = 128; a.k_row_stride = QKV;
-            a.vt = h->vt; a.vt_seq_stride = (long)h->KVH * 128 * Sp; a.vt_head_stride = 128L * Sp; a.vt_ld = Sp;
-            a.use_tab = 0;
-            a.out = h->ao; a.o_seq_stride = (long)S * QD; a.o_row_stride = QD;
-            a.N = Nq; a.Sq = S; a.Skv = S; a.Hq = h->HQ; a.Hkv = h->KVH;
-            a.window = sliding ? h->cfg.sliding_window : -1;
-            a.scale = scale;
+            AttnArgs a = attn_args_rows(h->qkv, QKV, h->qkv + QD, QKV, h->vt, Sp, h->ao, Nq, S, S, h->HQ, h->KVH,
+                                        sliding ? h->cfg.sliding_window : -1, scale);
             a.part = h->attn_part; a.part_floats = h->attn_part_floats;
             a.cu_slots = h->cu_slots;
             if (mx_usable(h, W.mx_o, M, D, QD, 2) && attention_mx_out_ok(a)) {  // the o_proj MX GEMM's operand straight from the attention epilogue
@@ -756,18 +749,15 @@ int forward_core(ace355_dit* h, int N, int T, const int* slots, int temb_rows, h
         }
         bool cao_is_mx = false;
         {
-            AttnArgs a{};
-            a.q = h->qkv; a.q_seq_stride = (long)S * QD; a.q_row_stride = QD;
-            a.use_tab = 1;
+            AttnArgs a = attn_args_q_out(h->qkv, QD, h->ao, Nc, S, L, h->HQ, h->KVH, -1, scale);
+            a.use_tab = 1;   // K and V^T of a sequence: its condition slot's, by absolute address
+            a.k_head_stride = 128; a.k_row_stride = 2 * KVD;
+            a.vt_head_stride = 128L * Lpad; a.vt_ld = Lpad;
             for (int i = 0; i < Nc; ++i) {
                 const CondSlot& cs = h->slots[slots[i]];
                 a.k_tab[i] = (unsigned long long)(cs.kv + (size_t)li * cs.L * 2 * KVD);
                 a.vt_tab[i] = (unsigned long long)(cs.vt + (size_t)li * h->KVH * 128 * cs.Lpad);
             }
-            a.k_head_stride = 128; a.k_row_stride = 2 * KVD;
-            a.vt_head_stride = 128L * Lpad; a.vt_ld = Lpad;
-            a.out = h->ao; a.o_seq_stride = (long)S * QD; a.o_row_stride = QD;
-            a.N = Nc; a.Sq = S; a.Skv = L; a.Hq = h->HQ; a.Hkv = h->KVH; a.window = -1; a.scale = scale;
             a.part = h->attn_part; a.part_floats = h->attn_part_floats;
             a.cu_slots = h->cu_slots;
             if (mx_cross && mx_usable(h, W.mx_oc, Mc, D, QD, 2) && attention_mx_out_ok(a)) {

@@ -208,15 +208,8 @@ int encoder_layers(EncBase* h, const EncoderW& E, int N, int S, const int* kv_le
                 rc = launch_vmean(h->qkv, QKV, QD + KVD, N, S, h->KVH, h->vmean, s);
                 if (rc) return rc;
             }
-            AttnArgs a{};
-            a.q = h->qkv; a.q_seq_stride = (long)S * QKV; a.q_row_stride = QKV;
-            a.k = h->qkv + QD; a.k_seq_stride = (long)S * QKV; a.k_head_stride = 128; a.k_row_stride = QKV;
-            a.vt = h->vt; a.vt_seq_stride = (long)h->KVH * 128 * Sp; a.vt_head_stride = 128L * Sp; a.vt_ld = Sp;
-            a.use_tab = 0;
-            a.out = h->ao; a.o_seq_stride = (long)S * QD; a.o_row_stride = QD;
-            a.N = N; a.Sq = S; a.Skv = S; a.Hq = h->HQ; a.Hkv = h->KVH;
-            a.window = sliding ? h->sliding_window : -1;
-            a.scale = scale;
+            AttnArgs a = attn_args_rows(h->qkv, QKV, h->qkv + QD, QKV, h->vt, Sp, h->ao, N, S, S, h->HQ, h->KVH,
+                                        sliding ? h->sliding_window : -1, scale);
             a.kv_len = kv_len_dev;
             a.vmean = kv_len_dev ? h->vmean : nullptr;
             rc = launch_attention(a, s);

@@ -96,6 +96,19 @@ class GemmPlanInfoC(C.Structure):
 GEMM_PLACEMENT_PROCESS = -2   # ACE355_GEMM_PLACEMENT_PROCESS
 
 
+class AttnRequestC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("N", "Sq", "Skv", "Hq", "Hkv", "window", "cu_slots", "has_kv_len", "mx_out", "reserved")] + [
+        ("part_floats", C.c_int64)]
+
+
+class AttnPlanInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "nw", "grid_x", "grid_y", "grid_z", "threads", "kv_split", "merge_grid", "mx_out_ok")]
+
+
+ATTN_KERNELS = ("attn3", "gqa", "rot")   # ACE355_ATTN_KERNEL_*
+ATTN_HOOK_PART_FLOATS = 16 << 20         # the split-KV scratch ace355_attention / ace355_attention_masked lend (csrc/api.hip)
+
+
 # ACE355_VAE_STAGE_* / ACE355_VAE_FLAG_* of include/ace355.h
 VAE_STAGE_INPUT, VAE_STAGE_CONV_IN, VAE_STAGE_CONVT, VAE_STAGE_UNIT, VAE_STAGE_UNIT_K7, VAE_STAGE_UNIT_K1, VAE_STAGE_DOWN, VAE_STAGE_HEAD = range(8)
 VAE_FLAG_IN_SNAKE, VAE_FLAG_OUT_SNAKE, VAE_FLAG_FUSED, VAE_FLAG_F32_NCL = 1, 2, 4, 8
@@ -138,6 +151,7 @@ SIGNATURES = {
     "ace355_box_probe_mfma": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "ace355_gemm_set_k_rotation": (C.c_int, [C.c_int]),
     "ace355_gemm_plan": (C.c_int, [C.POINTER(GemmRequestC), C.POINTER(GemmPlanInfoC)]),
+    "ace355_attn_plan": (C.c_int, [C.POINTER(AttnRequestC), C.POINTER(AttnPlanInfoC)]),
     "ace355_dit_set_dual": (C.c_int, [C.c_void_p, C.c_int]),
     "ace355_dit_dual_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ace355_dit_set_dedup": (C.c_int, [C.c_void_p, C.c_int]),
@@ -274,6 +288,18 @@ def gemm_plan(M: int, N: int, K: int, mode: int, **fields) -> dict:
     out = GemmPlanInfoC()
     check(lib().ace355_gemm_plan(C.byref(rq), C.byref(out)), "gemm_plan")
     return {n: int(getattr(out, n)) for n, _t in GemmPlanInfoC._fields_}
+
+
+def attn_plan(N: int, Sq: int, Skv: int, Hq: int, Hkv: int, window: int = -1, **fields) -> dict:
+    """`ace355_attn_plan` (include/ace355.h): the launch the attention launcher would make for a request, as a dict of the plan's fields
+    with `kernel` as its name in ATTN_KERNELS.  Fields not given are 0: no scratch, no mask, the whole chip."""
+    rq = AttnRequestC(N=N, Sq=Sq, Skv=Skv, Hq=Hq, Hkv=Hkv, window=window)
+    for k, v in fields.items():
+        assert hasattr(rq, k), k
+        setattr(rq, k, int(v))
+    out = AttnPlanInfoC()
+    check(lib().ace355_attn_plan(C.byref(rq), C.byref(out)), "attn_plan")
+    return {**{n: int(getattr(out, n)) for n, _t in AttnPlanInfoC._fields_}, "kernel": ATTN_KERNELS[out.kernel]}
 
 
 def current_stream_ptr() -> int:

@@ -88,6 +88,29 @@ typedef struct ace355_gemm_plan_info {
     uint32_t next_pf_chunk16, next_pf_len16;
 } ace355_gemm_plan_info;
 int ace355_gemm_plan(const ace355_gemm_request* request, ace355_gemm_plan_info* plan_out);
+/* The same for the attention entry points and the attention launches of the handles: the launch decision is one pure function of the
+ * request, the process's ACE355_ATTN_* switches and whether K rotation mode 0 is set at the time of the call.  No GPU is touched.  Fields
+ * are the library's AttnRequest / AttnPlan (csrc/attn_plan.h), where each is described. */
+#define ACE355_ATTN_KERNEL_ATTN3 0 /* attn3_kernel<nw = 4 | 8>: one q head per workgroup, 32 nw query rows; the only one that splits KV */
+#define ACE355_ATTN_KERNEL_GQA 1   /* attn_gqa_kernel<nw = 3 | 4 | 6>: both q heads of a KV head per workgroup, 32 nw query rows */
+#define ACE355_ATTN_KERNEL_ROT 2   /* attn_rot_kernel<nw = 3>: 96 query rows, the key range split between two wave groups */
+typedef struct ace355_attn_request {
+    int32_t N, Sq, Skv, Hq, Hkv;
+    int32_t window;         /* sliding band |i - j| <= window, -1: full attention */
+    int32_t cu_slots;       /* 8 .. 256: plan for that many CUs; 0: ACE355_MAX_WGS */
+    int32_t has_kv_len;     /* a key-padding mask is set (ace355_attention_masked, the condition encoders) */
+    int32_t mx_out;         /* MXFP8 output is asked for */
+    int32_t reserved;
+    int64_t part_floats;    /* floats of split-KV scratch lent, 0: none (ace355_attention lends 16 Mi) */
+} ace355_attn_request;
+typedef struct ace355_attn_plan_info {
+    int32_t kernel, nw;                          /* ACE355_ATTN_KERNEL_* and its template argument */
+    int32_t grid_x, grid_y, grid_z, threads;
+    int32_t kv_split;                            /* 1: one pass */
+    int32_t merge_grid;                          /* workgroups of the merge launch that follows a split, 0: none */
+    int32_t mx_out_ok;                           /* the kernel of this request can write MXFP8 */
+} ace355_attn_plan_info;
+int ace355_attn_plan(const ace355_attn_request* request, ace355_attn_plan_info* plan_out);
 
 /* ------------------------------------------------------------------------------------------
  * DiT decoder (AceStepDiTModel, base.py:1240-1507) + sampler (generate_audio, base.py:1783-1989)

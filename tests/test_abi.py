@@ -38,7 +38,8 @@ def test_struct_layouts_match_header(tmp_path):
     structs = {"ace355_dit_config": native.DitConfigC, "ace355_vae_config": native.VaeConfigC,
                "ace355_sample_params": native.SampleParamsC, "ace355_cond_config": native.CondConfigC,
                "ace355_detok_config": native.DetokConfigC, "ace355_vae_stage_info": native.VaeStageInfoC,
-               "ace355_gemm_request": native.GemmRequestC, "ace355_gemm_plan_info": native.GemmPlanInfoC}
+               "ace355_gemm_request": native.GemmRequestC, "ace355_gemm_plan_info": native.GemmPlanInfoC,
+               "ace355_attn_request": native.AttnRequestC, "ace355_attn_plan_info": native.AttnPlanInfoC}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ace355.h"', "int main(void) {"]
     for cname, ct in structs.items():
         lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _attn_plan_cases as _attn_cases
 import _gemm_plan_cases as _plan_cases
 
 pytestmark = pytest.mark.gpu
@@ -237,23 +238,14 @@ def test_headnorm_rope(lib, gpu_device, N, S, heads, rope):
     assert torch.equal(xd.cpu()[:, :128], x[:, :128]) and torch.equal(xd.cpu()[:, 128 + heads * 128:], x[:, 128 + heads * 128:])
 
 
-@pytest.mark.parametrize("N,Sq,Skv,Hq,Hkv,window", [
-    (2, 375, 375, 16, 8, -1), (2, 375, 375, 16, 8, 128), (1, 300, 300, 2, 1, 16), (2, 375, 769, 16, 8, -1),
-    (1, 20, 33, 2, 1, -1), (1, 1500, 1500, 4, 2, 128), (1, 129, 129, 2, 2, 128), (1, 64, 1, 2, 1, -1),
-    # Hq = 2 Hkv takes attn_gqa_kernel<NWH> once its grid fills the chip (launch_attention): NWH = 6 (12 waves, 192-row blocks:
-    # configs[2]'s self-attention, full and banded, with a ragged last block 1500 = 7 x 192 + 156, and its cross-attention
-    # shape), the metric's launches at N = 16 (NWH = 6: 375 = 192 + 183) and the metric's cross-attention at Nc = 8 (NWH = 3)
-    (6, 1500, 1500, 16, 8, -1), (6, 1500, 1500, 16, 8, 128), (6, 1500, 769, 16, 8, -1),
-    (16, 375, 375, 16, 8, -1), (16, 375, 375, 16, 8, 128), (8, 375, 769, 16, 8, -1), (16, 375, 769, 16, 8, -1),
-    (12, 375, 375, 16, 8, 128),   # NWH = 4 (8 waves, 128-row blocks)
-    # other group sizes stay on attn3_kernel: <8> (256-query blocks; Sq >= 1024 and heads x ceil(Sq / 256) >= 512) and <4>
-    (6, 1500, 1500, 16, 16, -1), (6, 1500, 1500, 16, 16, 128), (4, 375, 375, 8, 8, 128),
-    # batch-1 requests: few workgroups with long key walks (>= 8 tiles) take the split-KV path of attn3_kernel<4> + attn_merge_kernel
-    # ((2, 375, 769) above: 2 parts): the cross-attention of one conditional sequence (48 workgroups x 13 tiles -> 4 parts),
-    # configs[0]'s shapes (Sq = 125: 16 workgroups -> 4 parts; banded self-attention, not split), a ragged split (9 tiles in 4 parts)
-    (1, 375, 769, 16, 8, -1), (1, 125, 769, 16, 8, -1), (2, 125, 125, 16, 8, 16), (1, 200, 550, 4, 2, -1)])
-def test_attention(lib, gpu_device, N, Sq, Skv, Hq, Hkv, window):
+def _attention_vs_oracle(lib, gpu_device, shape, form):
+    """One launch of ace355_attention against the oracle, after asserting that the shape takes the launch it was chosen for:
+    `form` = (kernel, its template argument, kv_split) of ace355_attn_plan under the scratch the hook lends."""
+    from ace355 import native
     from oracle import dit as o_dit
+    N, Sq, Skv, Hq, Hkv, window = shape
+    p = native.attn_plan(N, Sq, Skv, Hq, Hkv, window, part_floats=native.ATTN_HOOK_PART_FLOATS)
+    assert (p["kernel"], p["nw"], p["kv_split"]) == form, p
     g = torch.Generator().manual_seed(Sq + Skv + Hq)
     q = _bf(torch.randn(N, Sq, Hq * 128, generator=g))
     k = _bf(torch.randn(N, Skv, Hkv * 128, generator=g))
@@ -269,6 +261,25 @@ def test_attention(lib, gpu_device, N, Sq, Skv, Hq, Hkv, window):
     _chk(lib.ace355_attention(_p(qd), _p(kd), _p(vd), _p(out), N, Sq, Skv, Hq, Hkv, window, scale, None))
     # P is rounded to bf16 before PV (like every flash kernel) and O to bf16: 1e-2 relative L2
     assert _rel(out.cpu(), ref) < 1e-2, _rel(out.cpu(), ref)
+
+
+# the rows, and the kernel form and split-KV part count each was chosen for, live in tests/_attn_plan_cases.py (ATTENTION_ROWS), beside the
+# plan table; tests/test_attn_plan_cpu.py checks that together they reach every form and part count
+@pytest.mark.parametrize("N,Sq,Skv,Hq,Hkv,window", [shape for shape, _form in _attn_cases.ATTENTION_ROWS])
+def test_attention(lib, gpu_device, N, Sq, Skv, Hq, Hkv, window):
+    _attention_vs_oracle(lib, gpu_device, (N, Sq, Skv, Hq, Hkv, window), dict(_attn_cases.ATTENTION_ROWS)[(N, Sq, Skv, Hq, Hkv, window)])
+
+
+def test_attention_one_order(lib, gpu_device):
+    """ace355_gemm_set_k_rotation(0), "one summation order whatever the launch shape", keeps the key-split kernel off: the 96-row launches
+    take attn_gqa_kernel<3>, which no default launch of this file reaches."""
+    from ace355 import native
+    shape, form = _attn_cases.ONE_ORDER_ROW
+    prev = native.gemm_set_k_rotation(0)
+    try:
+        _attention_vs_oracle(lib, gpu_device, shape, form)
+    finally:
+        native.gemm_set_k_rotation(prev)
 
 
 def test_attention_rescale_branch(lib, gpu_device):
