@@ -72,12 +72,12 @@ class NativeDitMixin:
         network (the reference loads adapters there after ``initialize_service``, H/lora/lifecycle.py:164-283), read by duck typing.  Hosts with a registry of their
         own override this (``NativeHandler``)."""
         from .lora import terms_from_decoder
-        return terms_from_decoder(self.model.decoder, getattr(self.native_dit, "cfg", None))
+        return terms_from_decoder(self.model.decoder, getattr(self.native_dit, "cfg", None), allow_dora=True)
 
     def _sync_native_adapters(self) -> None:
         """Bring the native DiT's merged adapters in line with the host's: nothing at all while ``use_lora`` is off and nothing is
         applied; a re-merge when the terms' fingerprint (names, scales, tensors, in-place versions) changed; the base back when
-        ``use_lora`` turned off.  ``UnsupportedAdapter`` (DoRA, Tucker LoKr, ...) propagates."""
+        ``use_lora`` turned off.  ``UnsupportedAdapter`` (Tucker LoKr, trained biases, ...) propagates."""
         applied = getattr(self, "_native_adapter_key", None)
         if not getattr(self, "use_lora", False):
             if applied is not None:
@@ -524,6 +524,7 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
         """Load the PEFT LoRA directory or LoKr artefact ``lora_path`` as ``adapter_name`` (default: the path's last component) and make
         it the active adapter (lifecycle.py:164-286).  The native DiT merges it at the next request (``_sync_native_adapters``)."""
         import os
+        from .dora import DoraTerm
         from .lokr import read_lokr_adapter, resolve_lokr_weights_path
         from .lora import read_peft_adapter
         if self.model is None:
@@ -550,12 +551,17 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
             dev = torch.device(self.device)
             if lokr_path is not None:
                 logger.info("Loading LoKr adapter from %s as '%s'", lokr_path, name)
-                terms = read_lokr_adapter(lokr_path, self.model.config)
-                self._lora_registry[name] = [t._replace(**{f: getattr(t, f).to(dev, self.dtype) for f in t._fields[1:7]
+                terms = read_lokr_adapter(lokr_path, self.model.config, allow_dora=True, dtype=self.dtype)
+                self._lora_registry[name] = [t if isinstance(t, DoraTerm) else
+                                             t._replace(**{f: getattr(t, f).to(dev, self.dtype) for f in t._fields[1:7]
                                                            if getattr(t, f) is not None}) for t in terms]
             else:
-                terms = read_peft_adapter(lora_path, self.model.config)
-                self._lora_registry[name] = [t._replace(A=t.A.to(dev, self.dtype), B=t.B.to(dev, self.dtype)) for t in terms]
+                terms = read_peft_adapter(lora_path, self.model.config, allow_dora=True)
+                self._lora_registry[name] = [t if isinstance(t, DoraTerm) else
+                                             t._replace(A=t.A.to(dev, self.dtype), B=t.B.to(dev, self.dtype)) for t in terms]
+            # DoRA magnitudes: the values the reference holds after its cast to the model dtype, as the fp32 the merge reads
+            self._lora_registry[name] = [t._replace(g=t.g.to(dev, self.dtype).float().reshape(-1).contiguous())
+                                         if isinstance(t, DoraTerm) else t for t in self._lora_registry[name]]
         except Exception as exc:
             logger.exception("Failed to load LoRA adapter")
             return f"❌ Failed to load LoRA: {exc!s}"
@@ -660,7 +666,10 @@ class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
         if not name or name not in self._lora_registry:
             return []
         s = float(self._active_loras.get(name, 1.0))
-        return [t._replace(scale=t.scale * s) for t in self._lora_registry[name]]
+        # a DoRA term's scale is the m of its interpolation: LyCORIS' multiplier (the user's scale, controls.py:12-32) enters it, PEFT's
+        # scaling does not
+        return [t if hasattr(t, "per_input") and self._adapter_type != "lokr" else t._replace(scale=t.scale * s)
+                for t in self._lora_registry[name]]
 
     # ------------------------------------------------------------------ service_generate
     def service_generate(self, encoder_hidden_states: torch.Tensor, context_latents: torch.Tensor,

@@ -376,7 +376,22 @@ struct LoraTargetDev {
     int tile0, tiles_n;  // first tile of this target in the launch, column tiles per row tile
     int term0, nterms;   // terms [term0, term0 + nterms) of the term table; 0: copy the pristine rows back
 };
-int launch_lora_merge(const LoraTargetDev* targets_dev, int n_targets, int total_tiles, const LoraTermDev* terms_dev, hipStream_t s);
+// DoRA (dora.h, dora.hip, ace355_dit_set_adapters_dora): W' = bf16_rne(V f), V the fp32 value the plain merge would round and
+// f = 1 + m (g / (||V|| + eps) - 1) per row (per_input 0) or per column (per_input 1).  A DoRA target's tiles run twice through its
+// merge kernel (`pass` 1: fp64 partial sums of squares into `part`; `pass` 2: V f), launch_dora_factors in between forms f.  One
+// DoraDev per target of a DoRA launch, at the target's index.
+struct DoraDev {
+    double* part;        // per_input 0: [tiles_n][rows], per_input 1: [tiles_m][cols] (scratch of the handle)
+    float* f;            // [n]
+    const float* g;      // [n]: dora_scale / lora_magnitude_vector in reference order
+    int per_input;
+    int n, ntiles;       // rows and column tiles per row, or columns and row tiles per column
+    float eps, m;
+};
+int launch_dora_factors(const DoraDev* dora_dev, int n_targets, int max_n, hipStream_t s);
+// `pass` 0: the plain merge (dora_dev unused)
+int launch_lora_merge(const LoraTargetDev* targets_dev, int n_targets, int total_tiles, const LoraTermDev* terms_dev, hipStream_t s,
+                      const DoraDev* dora_dev = nullptr, int pass = 0);
 int launch_lora_read(const bf16_t* w, long ld, int mode, long row0, int p0, long rows, long cols, void* dst, int dst_is_bf16,
                      hipStream_t s);
 
@@ -410,7 +425,7 @@ struct KronTermDev {
 int lokr_lds_floats(int out_k, int in_n);   // worst case over the tiles of a term (<= LOKR_LDS_FLOATS for every split)
 int launch_lokr_factors(const KronFactorDev* jobs_dev, int n_jobs, int total_tiles, hipStream_t s);
 int launch_lokr_merge(const LoraTargetDev* targets_dev, int n_targets, int total_tiles, const KronTermDev* terms_dev, int lds_floats,
-                      hipStream_t s);
+                      hipStream_t s, const DoraDev* dora_dev = nullptr, int pass = 0);   // `pass` as launch_lora_merge
 
 // Cross-attention probabilities (xattn_probs.hip, ace355_dit_cross_attention_maps / ace355_cross_attention_probs): for query heads
 // heads[p], out[p][n][j][s] = softmax_j(scale q[n][s] . k[n][j]) in fp32, j < Skv, s < Sq

@@ -173,6 +173,8 @@ struct ace355_dit : LoadBase {
         size_t tab_bytes = 0;
         float* kscratch = nullptr;      // fp32 products of the decomposed Kronecker factors of the last call (lokr.hip)
         size_t kscratch_floats = 0;
+        void* dscratch = nullptr;       // fp64 partial sums of squares and fp32 factors of the last call's DoRA targets (dora.hip)
+        size_t dscratch_bytes = 0;
     } lora;
 
     // profiling
@@ -1125,6 +1127,7 @@ void ace355_dit_destroy(ace355_dit* h) {
     lora_free_pristine(h);
     if (h->lora.tab) hipFree(h->lora.tab);
     if (h->lora.kscratch) hipFree(h->lora.kscratch);
+    if (h->lora.dscratch) hipFree(h->lora.dscratch);
     if (h->rope_cos) hipFree(h->rope_cos);
     if (h->rope_sin) hipFree(h->rope_sin);
     if (h->enc_bf) hipFree(h->enc_bf);
@@ -1692,11 +1695,14 @@ int ace355_dit_graph_stats(ace355_dit* h, int64_t* captures, int64_t* replays) {
     return ACE355_OK;
 }
 
-// ace355_dit_set_adapters (n_kron 0: its launches are those of the LoRA merge alone) and ace355_dit_set_adapters_mixed
-static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n_terms, const ace355_kron_term* kron, int n_kron, void* stream) {
+// ace355_dit_set_adapters (n_kron 0: its launches are those of the LoRA merge alone), ace355_dit_set_adapters_mixed (n_dora 0: nothing
+// below adds to its launches or tables) and ace355_dit_set_adapters_dora
+static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n_terms, const ace355_kron_term* kron, int n_kron,
+                             const ace355_dora_term* dora, int n_dora, void* stream) {
     ACE_CHECK(h, "set_adapters: null handle");
     ACE_CHECK(n_terms >= 0 && (n_terms == 0 || terms), "set_adapters: terms");
     ACE_CHECK(n_kron >= 0 && (n_kron == 0 || kron), "set_adapters: kron terms");
+    ACE_CHECK(n_dora >= 0 && (n_dora == 0 || dora), "set_adapters: dora terms");
     if (!h->finalized) { set_error("set_adapters: call ace355_dit_finalize first"); return ACE355_ERR_STATE; }
     if (h->precision != ACE355_PRECISION_BF16 || h->weights_fp8wo) {   // H/lora/lifecycle.py:173-178
         set_error(std::string("set_adapters: LoRA loading is not supported on quantized models. Current precision: ") +
@@ -1708,6 +1714,7 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
     std::vector<std::string> order;
     std::vector<std::vector<const ace355_lora_term*>> by;
     std::vector<std::vector<const ace355_kron_term*>> kby;
+    std::vector<const ace355_dora_term*> dby;   // at most one DoRA term per target
     std::vector<PackDest> dests;
     auto index_of = [&](const std::string& n) { for (size_t i = 0; i < order.size(); ++i) if (order[i] == n) return (int)i; return -1; };
     auto not_a_target = [&](const char* name) {
@@ -1715,7 +1722,7 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
                   "layers.{i}.mlp.{gate,up,down}_proj.weight)");
         return ACE355_ERR_INVALID;
     };
-    std::set<std::string> lora_named;
+    std::set<std::string> lora_named, add_named, dora_named;
     for (int i = 0; i < n_terms; ++i) {
         const ace355_lora_term& t = terms[i];
         ACE_CHECK(t.name && t.A_dev && t.B_dev, "set_adapters: null name / A / B");
@@ -1723,9 +1730,10 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
         if (!lora_target(h, t.name, &d)) return not_a_target(t.name);
         ACE_CHECK(t.rank >= 1 && std::isfinite(t.scale), "set_adapters: rank must be >= 1 and scale finite");
         if (n_kron) lora_named.insert(t.name);
+        if (n_dora) add_named.insert(t.name);
         if (t.scale == 0.f) continue;
         int k = index_of(t.name);
-        if (k < 0) { order.push_back(t.name); by.emplace_back(); kby.emplace_back(); dests.push_back(d); k = (int)order.size() - 1; }
+        if (k < 0) { order.push_back(t.name); by.emplace_back(); kby.emplace_back(); dby.push_back(nullptr); dests.push_back(d); k = (int)order.size() - 1; }
         by[k].push_back(&t);
     }
     for (int i = 0; i < n_kron; ++i) {
@@ -1746,17 +1754,39 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
             set_error(std::string("set_adapters: '") + t.name + "' is named by a LoRA term and by a Kronecker term");
             return ACE355_ERR_INVALID;
         }
+        if (n_dora) add_named.insert(t.name);
         if (t.scale == 0.f) continue;
         int k = index_of(t.name);
-        if (k < 0) { order.push_back(t.name); by.emplace_back(); kby.emplace_back(); dests.push_back(d); k = (int)order.size() - 1; }
+        if (k < 0) { order.push_back(t.name); by.emplace_back(); kby.emplace_back(); dby.push_back(nullptr); dests.push_back(d); k = (int)order.size() - 1; }
         kby[k].push_back(&t);
+    }
+    for (int i = 0; i < n_dora; ++i) {
+        const ace355_dora_term& t = dora[i];
+        ACE_CHECK(t.name && t.g_dev, "set_adapters: null name / g in a DoRA term");
+        PackDest d;
+        if (!lora_target(h, t.name, &d)) return not_a_target(t.name);
+        ACE_CHECK(t.per_input == 0 || t.per_input == 1, "set_adapters: a DoRA term's per_input must be 0 or 1");
+        ACE_CHECK(std::isfinite(t.eps) && t.eps >= 0.f && std::isfinite(t.multiplier),
+                  "set_adapters: a DoRA term's eps must be finite and >= 0 and its multiplier finite");
+        if (!dora_named.insert(t.name).second) {
+            set_error(std::string("set_adapters: two DoRA terms name '") + t.name + "'");
+            return ACE355_ERR_INVALID;
+        }
+        if (t.multiplier == 0.f) continue;   // f = 1
+        if (!add_named.count(t.name)) {
+            set_error(std::string("set_adapters: the DoRA term on '") + t.name + "' has no LoRA / Kronecker term beside it in this call");
+            return ACE355_ERR_INVALID;
+        }
+        int k = index_of(t.name);   // (every additive term of the target at scale 0: V = W0, still rescaled)
+        if (k < 0) { order.push_back(t.name); by.emplace_back(); kby.emplace_back(); dby.push_back(nullptr); dests.push_back(d); k = (int)order.size() - 1; }
+        dby[k] = &t;
     }
     const size_t n_merge = order.size();
     for (const std::string& n : h->lora.applied) {   // merged before, no term now: its rows go back to the base
         if (index_of(n) >= 0) continue;
         PackDest d;
         lora_target(h, n, &d);
-        order.push_back(n); by.emplace_back(); kby.emplace_back(); dests.push_back(d);
+        order.push_back(n); by.emplace_back(); kby.emplace_back(); dby.push_back(nullptr); dests.push_back(d);
     }
     if (order.empty()) return ACE355_OK;
     ACE_HIP(hipStreamSynchronize(s));   // (the previous call's merge may still read the tables)
@@ -1787,9 +1817,30 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
         ACE_HIP(hipMalloc((void**)&h->lora.kscratch, scratch_floats * sizeof(float)));
         h->lora.kscratch_floats = scratch_floats;
     }
+    // the scratch of the DoRA targets: per target its fp64 partials, then its fp32 factors
+    auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
+    size_t dscratch_bytes = 0;
+    bool any_dora = false;
+    for (size_t i = 0; i < n_merge; ++i) {
+        if (!dby[i]) continue;
+        any_dora = true;
+        const PackDest& d = dests[i];
+        const size_t n = dby[i]->per_input ? d.cols : d.rows;
+        const size_t nt = dby[i]->per_input ? (d.rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS : (d.cols + LORA_TILE_COLS - 1) / LORA_TILE_COLS;
+        dscratch_bytes += up16(n * nt * sizeof(double)) + up16(n * sizeof(float));
+    }
+    if (dscratch_bytes > h->lora.dscratch_bytes) {
+        if (h->lora.dscratch) hipFree(h->lora.dscratch);
+        h->lora.dscratch = nullptr; h->lora.dscratch_bytes = 0;
+        ACE_HIP(hipMalloc(&h->lora.dscratch, dscratch_bytes));
+        h->lora.dscratch_bytes = dscratch_bytes;
+    }
     // LoRA targets (and, in a call without Kronecker terms, the restored ones) go to the LoRA launch, Kronecker targets (and, beside
     // them, the restored ones) to the LoKr launch
-    std::vector<LoraTargetDev> tg, ktg;
+    std::vector<LoraTargetDev> tg, ktg, dtg, dktg;   // d*: the targets with a DoRA term, by the kernel that forms their V
+    std::vector<DoraDev> ddv, dkdv;
+    int dtiles = 0, dktiles = 0, dmax_n = 0;
+    size_t dscratch_at = 0;
     std::vector<LoraTermDev> tm;
     std::vector<KronTermDev> ktm;
     std::vector<KronFactorDev> jobs;
@@ -1813,10 +1864,26 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
         LoraTargetDev x{};
         x.dst = (bf16_t*)d.dst; x.src = pristine_of(d.dst); x.ld = d.dst_ld; x.row0 = d.dst_row0; x.mode = d.mode; x.p0 = d.p0;
         x.rows = (int)d.rows; x.cols = (int)d.cols;
+        static_assert(LORA_TILE_ROWS == LOKR_TILE_ROWS && LORA_TILE_COLS == LOKR_TILE_COLS, "dora.h: one tile shape for both merge kernels");
+        const bool dk = dby[i] && to_kron;   // a DoRA target goes to launches of its own
+        if (dby[i]) {
+            const ace355_dora_term* t = dby[i];
+            DoraDev v{};
+            v.per_input = t->per_input; v.eps = t->eps; v.m = t->multiplier; v.g = t->g_dev;
+            v.n = t->per_input ? x.cols : x.rows;
+            v.ntiles = t->per_input ? (x.rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS : (x.cols + LORA_TILE_COLS - 1) / LORA_TILE_COLS;
+            v.part = (double*)((char*)h->lora.dscratch + dscratch_at);
+            dscratch_at += up16((size_t)v.n * v.ntiles * sizeof(double));
+            v.f = (float*)((char*)h->lora.dscratch + dscratch_at);
+            dscratch_at += up16((size_t)v.n * sizeof(float));
+            dmax_n = std::max(dmax_n, v.n);
+            (dk ? dkdv : ddv).push_back(v);
+        }
         if (to_kron) {
+            int& at = dk ? dktiles : ktiles;
             x.tiles_n = (x.cols + LOKR_TILE_COLS - 1) / LOKR_TILE_COLS;
-            x.tile0 = ktiles;
-            ktiles += (x.rows + LOKR_TILE_ROWS - 1) / LOKR_TILE_ROWS * x.tiles_n;
+            x.tile0 = at;
+            at += (x.rows + LOKR_TILE_ROWS - 1) / LOKR_TILE_ROWS * x.tiles_n;
             x.term0 = (int)ktm.size();
             for (const ace355_kron_term* t : kby[i]) {
                 KronTermDev u{};
@@ -1828,15 +1895,16 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
                 ktm.push_back(u);
             }
             x.nterms = (int)ktm.size() - x.term0;
-            ktg.push_back(x);
+            (dk ? dktg : ktg).push_back(x);
         } else {
+            int& at = dby[i] ? dtiles : tiles;
             x.tiles_n = (x.cols + LORA_TILE_COLS - 1) / LORA_TILE_COLS;
-            x.tile0 = tiles;
-            tiles += (x.rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS * x.tiles_n;
+            x.tile0 = at;
+            at += (x.rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS * x.tiles_n;
             x.term0 = (int)tm.size();
             for (const ace355_lora_term* t : by[i]) tm.push_back(LoraTermDev{(const bf16_t*)t->A_dev, (const bf16_t*)t->B_dev, t->rank, t->scale});
             x.nterms = (int)tm.size() - x.term0;
-            tg.push_back(x);
+            (dby[i] ? dtg : tg).push_back(x);
         }
         const std::string& n = order[i];
         kv = kv || n.find(".cross_attn.k_proj.") != std::string::npos || n.find(".cross_attn.v_proj.") != std::string::npos;
@@ -1846,7 +1914,11 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
     const size_t tg_bytes = pad(tg.size() * sizeof(LoraTargetDev)), tm_bytes = std::max<size_t>(tm.size(), 1) * sizeof(LoraTermDev);
     const size_t ktg_at = any_kron ? pad(tg_bytes + tm_bytes) : tg_bytes + tm_bytes, ktm_at = ktg_at + pad(ktg.size() * sizeof(LoraTargetDev));
     const size_t job_at = ktm_at + pad(ktm.size() * sizeof(KronTermDev));
-    const size_t bytes = any_kron ? job_at + std::max<size_t>(jobs.size(), 1) * sizeof(KronFactorDev) : tg_bytes + tm_bytes;
+    const size_t bytes0 = any_kron ? job_at + std::max<size_t>(jobs.size(), 1) * sizeof(KronFactorDev) : tg_bytes + tm_bytes;
+    // DoRA tables behind those of the plain merges: LoRA-formed targets and their DoraDev, Kronecker-formed targets and theirs
+    const size_t dtg_at = pad(bytes0), ddv_at = dtg_at + pad(dtg.size() * sizeof(LoraTargetDev));
+    const size_t dktg_at = ddv_at + pad(ddv.size() * sizeof(DoraDev)), dkdv_at = dktg_at + pad(dktg.size() * sizeof(LoraTargetDev));
+    const size_t bytes = any_dora ? dkdv_at + std::max<size_t>(dkdv.size(), 1) * sizeof(DoraDev) : bytes0;
     if (bytes > h->lora.tab_bytes) {
         if (h->lora.tab) hipFree(h->lora.tab);
         h->lora.tab = nullptr; h->lora.tab_bytes = 0;
@@ -1859,12 +1931,28 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
     if (!ktg.empty()) memcpy(host.data() + ktg_at, ktg.data(), ktg.size() * sizeof(LoraTargetDev));
     if (!ktm.empty()) memcpy(host.data() + ktm_at, ktm.data(), ktm.size() * sizeof(KronTermDev));
     if (!jobs.empty()) memcpy(host.data() + job_at, jobs.data(), jobs.size() * sizeof(KronFactorDev));
+    if (!dtg.empty()) memcpy(host.data() + dtg_at, dtg.data(), dtg.size() * sizeof(LoraTargetDev));
+    if (!ddv.empty()) memcpy(host.data() + ddv_at, ddv.data(), ddv.size() * sizeof(DoraDev));
+    if (!dktg.empty()) memcpy(host.data() + dktg_at, dktg.data(), dktg.size() * sizeof(LoraTargetDev));
+    if (!dkdv.empty()) memcpy(host.data() + dkdv_at, dkdv.data(), dkdv.size() * sizeof(DoraDev));
     ACE_HIP(hipMemcpyAsync(h->lora.tab, host.data(), bytes, hipMemcpyHostToDevice, s));
     char* tab = (char*)h->lora.tab;
     int rc = launch_lora_merge((const LoraTargetDev*)tab, (int)tg.size(), tiles, (const LoraTermDev*)(tab + tg_bytes), s);
     if (!rc && any_kron) {
         rc = launch_lokr_factors((const KronFactorDev*)(tab + job_at), (int)jobs.size(), jtiles, s);
         if (!rc) rc = launch_lokr_merge((const LoraTargetDev*)(tab + ktg_at), (int)ktg.size(), ktiles, (const KronTermDev*)(tab + ktm_at), klds, s);
+    }
+    if (!rc && any_dora) {   // pass 1 of both kernels, the factors, pass 2 of both: in order on the one stream
+        const LoraTargetDev *a = (const LoraTargetDev*)(tab + dtg_at), *b = (const LoraTargetDev*)(tab + dktg_at);
+        const DoraDev *av = (const DoraDev*)(tab + ddv_at), *bv = (const DoraDev*)(tab + dkdv_at);
+        const LoraTermDev* tmd = (const LoraTermDev*)(tab + tg_bytes);
+        const KronTermDev* ktmd = (const KronTermDev*)(tab + ktm_at);
+        rc = launch_lora_merge(a, (int)dtg.size(), dtiles, tmd, s, av, 1);
+        if (!rc) rc = launch_lokr_merge(b, (int)dktg.size(), dktiles, ktmd, klds, s, bv, 1);
+        if (!rc) rc = launch_dora_factors(av, (int)ddv.size(), dmax_n, s);
+        if (!rc) rc = launch_dora_factors(bv, (int)dkdv.size(), dmax_n, s);
+        if (!rc) rc = launch_lora_merge(a, (int)dtg.size(), dtiles, tmd, s, av, 2);
+        if (!rc) rc = launch_lokr_merge(b, (int)dktg.size(), dktiles, ktmd, klds, s, bv, 2);
     }
     ACE_HIP(hipStreamSynchronize(s));   // (pageable source of the table copy; a merge is rare next to the requests it serves)
     if (rc) return rc;
@@ -1878,12 +1966,17 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
 }
 
 int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_terms, void* stream) {
-    return set_adapters_impl(h, terms, n_terms, nullptr, 0, stream);
+    return set_adapters_impl(h, terms, n_terms, nullptr, 0, nullptr, 0, stream);
 }
 
 int ace355_dit_set_adapters_mixed(ace355_dit* h, const ace355_lora_term* lora, int n_lora, const ace355_kron_term* kron, int n_kron,
                                   void* stream) {
-    return set_adapters_impl(h, lora, n_lora, kron, n_kron, stream);
+    return set_adapters_impl(h, lora, n_lora, kron, n_kron, nullptr, 0, stream);
+}
+
+int ace355_dit_set_adapters_dora(ace355_dit* h, const ace355_lora_term* lora, int n_lora, const ace355_kron_term* kron, int n_kron,
+                                 const ace355_dora_term* dora, int n_dora, void* stream) {
+    return set_adapters_impl(h, lora, n_lora, kron, n_kron, dora, n_dora, stream);
 }
 
 int ace355_dit_read_weight(ace355_dit* h, const char* name, void* dst_dev, int dtype, void* stream) {

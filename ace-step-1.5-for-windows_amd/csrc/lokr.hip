@@ -5,6 +5,7 @@
 // two LDS reads and one multiply-add.
 #include "../../include/ace355.h"
 #include "common.h"
+#include "dora.h"
 
 namespace ace355 {
 
@@ -71,8 +72,10 @@ __device__ __forceinline__ float factor_at(const void* p, int is_f32, long i) {
 // row / column otherwise (W2 larger than a tile: k = (n0 + r) mod out_k wraps at most once).  Every read is inside its factor.
 // A term with in_n % 8 == 0, in_n <= TN and a 16-byte aligned W2 (KronTermDev::wide) takes 16-byte paths: an 8-column group then lies
 // inside one m, W2 is staged 8 columns per load and read back as two float4.  Both paths form the same fp32 values.
+// PASS 0 is that merge.  PASS 1 / 2 are the two passes of a DoRA target (dora.h): the same fp32 values, reduced resp. rescaled.
+template <int PASS>
 __global__ __launch_bounds__(256) void lokr_merge_kernel(const LoraTargetDev* __restrict__ tg, int n_targets,
-                                                         const KronTermDev* __restrict__ terms) {
+                                                         const KronTermDev* __restrict__ terms, const DoraDev* __restrict__ dora) {
     extern __shared__ __attribute__((aligned(16))) float pool[];
     const int bid = blockIdx.x;
     int lo = 0, hi = n_targets - 1;   // last target whose first tile is <= bid (targets are in tile order)
@@ -172,6 +175,19 @@ __global__ __launch_bounds__(256) void lokr_merge_kernel(const LoraTargetDev* __
         }
         __syncthreads();
     }
+    if constexpr (PASS != 0) {
+        __shared__ double sQ[DORA_LDS_DOUBLES];
+        float v[G][8];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            v[i][0] = bf_lo(w[i].x) + sum[i][0]; v[i][1] = bf_hi(w[i].x) + sum[i][1];
+            v[i][2] = bf_lo(w[i].y) + sum[i][2]; v[i][3] = bf_hi(w[i].y) + sum[i][3];
+            v[i][4] = bf_lo(w[i].z) + sum[i][4]; v[i][5] = bf_hi(w[i].z) + sum[i][5];
+            v[i][6] = bf_lo(w[i].w) + sum[i][6]; v[i][7] = bf_hi(w[i].w) + sum[i][7];
+        }
+        dora_epilogue<PASS>(t, dora[lo], n0, c0, tid, v, live, off, sQ);
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < G; ++i) {
         if (!live[i]) continue;
@@ -202,11 +218,13 @@ int launch_lokr_factors(const KronFactorDev* jobs_dev, int n_jobs, int total_til
 }
 
 int launch_lokr_merge(const LoraTargetDev* targets_dev, int n_targets, int total_tiles, const KronTermDev* terms_dev, int lds_floats,
-                      hipStream_t s) {
+                      hipStream_t s, const DoraDev* dora_dev, int pass) {
     if (n_targets <= 0 || total_tiles <= 0) return 0;
     if (lds_floats < 4 || lds_floats > LOKR_LDS_FLOATS) { set_error("lokr merge: LDS size out of range"); return ACE355_ERR_INVALID; }
-    hipLaunchKernelGGL(lokr_merge_kernel, dim3(total_tiles), dim3(256), (size_t)lds_floats * sizeof(float), s, targets_dev, n_targets,
-                       terms_dev);
+    if (pass < 0 || pass > 2 || (pass != 0 && !dora_dev)) { set_error("lokr merge: pass"); return ACE355_ERR_INVALID; }
+    auto* k = pass == 0 ? lokr_merge_kernel<0> : pass == 1 ? lokr_merge_kernel<1> : lokr_merge_kernel<2>;
+    hipLaunchKernelGGL(k, dim3(total_tiles), dim3(256), (size_t)lds_floats * sizeof(float), s, targets_dev, n_targets, terms_dev,
+                       dora_dev);
     ACE_LAUNCH_CHECK();
     return 0;
 }

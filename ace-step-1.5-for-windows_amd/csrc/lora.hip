@@ -4,6 +4,7 @@
 // kernels and every result without an adapter stay as they are.
 #include "../../include/ace355.h"
 #include "common.h"
+#include "dora.h"
 
 namespace ace355 {
 
@@ -19,8 +20,10 @@ constexpr int SP = TN + 4;           // LDS row pitch of the fp32 sum tile
 // TN / 16 accumulators of 16 x 16.  Per term: B rows and A columns staged in LDS 32 ranks at a time (zero beyond the rank: any rank
 // works), B.A into the term's own fp32 accumulators, then sum += scale x acc in fp32.  Epilogue: the sum tile goes through LDS so
 // that the pristine read and the live write are 16-byte accesses along a packed row, at the row the pack row map gives.
+// PASS 0 is that merge.  PASS 1 / 2 are the two passes of a DoRA target (dora.h): the same fp32 values, reduced resp. rescaled.
+template <int PASS>
 __global__ __launch_bounds__(256) void lora_merge_kernel(const LoraTargetDev* __restrict__ tg, int n_targets,
-                                                         const LoraTermDev* __restrict__ terms) {
+                                                         const LoraTermDev* __restrict__ terms, const DoraDev* __restrict__ dora) {
     __shared__ __attribute__((aligned(16))) bf16_t sB[TM][KP];
     __shared__ __attribute__((aligned(16))) bf16_t sAt[TN][KP];
     __shared__ __attribute__((aligned(16))) float sS[TM][SP];
@@ -67,6 +70,28 @@ __global__ __launch_bounds__(256) void lora_merge_kernel(const LoraTargetDev* __
             for (int i = 0; i < 4; ++i) sS[wave * 16 + (lane >> 4) * 4 + i][b * 16 + (lane & 15)] = sum[b][i];
         __syncthreads();
     }
+    if constexpr (PASS != 0) {
+        __shared__ double sQ[DORA_LDS_DOUBLES];
+        float v[4][8];
+        long off[4];
+        bool live[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {   // (the groups the loop below gives this thread)
+            const int r = (tid >> 4) + 16 * i, c8 = (tid & 15) * 8, n = n0 + r, c = c0 + c8;
+            live[i] = n < t.rows && c < t.cols;
+            off[i] = live[i] ? pack_row(t.mode, n, t.row0, t.p0) * t.ld + c : 0;
+            const uint4 w = live[i] ? *reinterpret_cast<const uint4*>(t.src + off[i]) : uint4{0u, 0u, 0u, 0u};
+            float4 s0 = float4{0.f, 0.f, 0.f, 0.f}, s1 = s0;
+            if (t.nterms) {
+                s0 = *reinterpret_cast<const float4*>(&sS[r][c8]);
+                s1 = *reinterpret_cast<const float4*>(&sS[r][c8 + 4]);
+            }
+            v[i][0] = bf_lo(w.x) + s0.x; v[i][1] = bf_hi(w.x) + s0.y; v[i][2] = bf_lo(w.y) + s0.z; v[i][3] = bf_hi(w.y) + s0.w;
+            v[i][4] = bf_lo(w.z) + s1.x; v[i][5] = bf_hi(w.z) + s1.y; v[i][6] = bf_lo(w.w) + s1.z; v[i][7] = bf_hi(w.w) + s1.w;
+        }
+        dora_epilogue<PASS>(t, dora[lo], n0, c0, tid, v, live, off, sQ);
+        return;
+    }
     for (int e = tid; e < TM * TN / 8; e += 256) {
         const int r = e / (TN / 8), c8 = (e % (TN / 8)) * 8, n = n0 + r, c = c0 + c8;
         if (n >= t.rows || c >= t.cols) continue;
@@ -97,9 +122,12 @@ __global__ void lora_read_kernel(const bf16_t* __restrict__ w, long ld, int mode
 
 }  // namespace
 
-int launch_lora_merge(const LoraTargetDev* targets_dev, int n_targets, int total_tiles, const LoraTermDev* terms_dev, hipStream_t s) {
+int launch_lora_merge(const LoraTargetDev* targets_dev, int n_targets, int total_tiles, const LoraTermDev* terms_dev, hipStream_t s,
+                      const DoraDev* dora_dev, int pass) {
     if (n_targets <= 0 || total_tiles <= 0) return 0;
-    hipLaunchKernelGGL(lora_merge_kernel, dim3(total_tiles), dim3(256), 0, s, targets_dev, n_targets, terms_dev);
+    if (pass < 0 || pass > 2 || (pass != 0 && !dora_dev)) { set_error("lora merge: pass"); return ACE355_ERR_INVALID; }
+    auto* k = pass == 0 ? lora_merge_kernel<0> : pass == 1 ? lora_merge_kernel<1> : lora_merge_kernel<2>;
+    hipLaunchKernelGGL(k, dim3(total_tiles), dim3(256), 0, s, targets_dev, n_targets, terms_dev, dora_dev);
     ACE_LAUNCH_CHECK();
     return 0;
 }

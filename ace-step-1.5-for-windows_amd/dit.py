@@ -208,11 +208,14 @@ class NativeDit(native.Owner):
         scale)`` tuples and ``ace355.lokr.KronTerm`` / 8-tuples, mixed freely.  Every target weight becomes bf16(W0 + sum of scale x
         B @ A) resp. bf16(W0 + sum of scale x kron(W1, W2)), whatever the earlier calls were (include/ace355.h
         ``ace355_dit_set_adapters`` / ``ace355_dit_set_adapters_mixed``; the latter is called only when a Kronecker term is present).
-        The tensors are converted to bf16 on this device, as the reference's ``.to(self.dtype)`` does.  Synchronous: the merge has run
-        on the current stream when this returns.  bf16 precision only."""
+        An ``ace355.dora.DoraTerm`` / 5-tuple ``(name, g, per_input, eps, scale)`` rescales the merged weight of its target by
+        1 + scale (g / (norm + eps) - 1) per row or per column (``ace355_dit_set_adapters_dora``, called only when one is present).
+        The factor tensors are converted to bf16 on this device, as the reference's ``.to(self.dtype)`` does, and ``g`` to fp32 as
+        given.  Synchronous: the merge has run on the current stream when this returns.  bf16 precision only."""
+        from .dora import DoraTerm, check_g
         from .lokr import KronTerm, term_dims
         shapes = self.cfg.weight_shapes()
-        keep, rows, krows = [], [], []   # (alive until the synchronous native call has returned)
+        keep, rows, krows, drows = [], [], [], []   # (alive until the synchronous native call has returned)
         with torch.cuda.device(self.device):
             def dev(x):
                 if x is None:
@@ -226,6 +229,16 @@ class NativeDit(native.Owner):
             for term in terms:
                 nm = term[0].encode()
                 keep.append(nm)
+                if len(term) == 5:
+                    dt = DoraTerm(*term)
+                    if not isinstance(dt.g, torch.Tensor):
+                        raise ValueError(f"set_adapters: the DoRA term on {dt.name} needs a tensor g")
+                    if dt.name in shapes:
+                        check_g(dt, *shapes[dt.name])
+                    g = dt.g.detach().to(self.device, torch.float32).reshape(-1).contiguous()
+                    keep.append(g)
+                    drows.append((nm, native.ptr(g), int(bool(dt.per_input)), float(dt.eps), float(dt.scale)))
+                    continue
                 if len(term) == 8:
                     kt = KronTerm(*term)
                     out_l, out_k, in_m, in_n, r1, r2 = term_dims(kt)
@@ -242,13 +255,19 @@ class NativeDit(native.Owner):
                         raise ValueError(f"set_adapters: A {tuple(A.shape)} / B {tuple(B.shape)} do not fit {name} [{out_f}, {in_f}]")
                 rows.append((nm, dev(A), dev(B), int(A.shape[0]), float(scale)))
             arr = (native.LoraTermC * max(len(rows), 1))(*[native.LoraTermC(*r) for r in rows])
-            if krows:
+            if drows:
+                karr = (native.KronTermC * max(len(krows), 1))(*[native.KronTermC(*r) for r in krows])
+                darr = (native.DoraTermC * len(drows))(*[native.DoraTermC(*r) for r in drows])
+                native.check(self._lib.ace355_dit_set_adapters_dora(self._h, arr, len(rows), karr, len(krows), darr, len(drows),
+                                                                    native.current_stream_ptr()), "dit_set_adapters_dora")
+            elif krows:
                 karr = (native.KronTermC * len(krows))(*[native.KronTermC(*r) for r in krows])
                 native.check(self._lib.ace355_dit_set_adapters_mixed(self._h, arr, len(rows), karr, len(krows), native.current_stream_ptr()),
                              "dit_set_adapters_mixed")
             else:
                 native.check(self._lib.ace355_dit_set_adapters(self._h, arr, len(rows), native.current_stream_ptr()), "dit_set_adapters")
-        self._adapters_applied = any(float(r[-1]) != 0.0 for r in rows + krows)
+        # (a DoRA term rescales only where its multiplier is not 0, and then even a target whose additive terms are all at scale 0)
+        self._adapters_applied = any(float(r[-1]) != 0.0 for r in rows + krows + drows)
 
     def clear_adapters(self) -> None:
         """Restore the base weights (``set_adapters([])``)."""

@@ -10,8 +10,10 @@ toggles / scales it with ``set_multiplier`` (controls.py:12-32, 49-55, 121-129).
 The LyCORIS conventions used here - the ``lycoris_<path with underscores>`` module names, the attribute and state-dict names, the scale
 rules (``alpha / dim``, ``alpha / sqrt(dim)`` with rs_lora, 1 for a module whose two factors are both full) - are restated from its
 published ``LokrModule``; ``lycoris`` is neither imported here nor part of the reference tree, so they are unpinned.  What the merge
-does not cover raises ``UnsupportedAdapter``: Tucker (``lokr_t2``), DoRA (``weight_decompose`` / ``dora_scale``), other LyCORIS
-algorithms, and targets outside the ten projection kinds.
+does not cover raises ``UnsupportedAdapter``: Tucker (``lokr_t2``), other LyCORIS algorithms, and targets outside the ten projection
+kinds.  DoRA (``weight_decompose`` / ``dora_scale``, on by default in the reference's training API) is merged too, but it is not an
+additive term: the readers return it as ``ace355.dora.DoraTerm`` only to a caller that asks with ``allow_dora=True`` and refuse it
+otherwise, so that a caller that sums ``dense_delta`` is never silently wrong.
 """
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
+from .dora import DoraTerm, axis_of, dora_eps
 from .lora import LOKR_WEIGHTS_FILENAME, TARGET_KINDS, UnsupportedAdapter
 
 logger = logging.getLogger(__name__)
@@ -170,15 +173,18 @@ def lokr_scale(cfg: dict, both_full: bool) -> float:
     return alpha / (math.sqrt(dim) if cfg["rs_lora"] else dim)
 
 
-def read_lokr_adapter(path: str, cfg=None) -> List[KronTerm]:
+def read_lokr_adapter(path: str, cfg=None, allow_dora: bool = False, dtype: torch.dtype = torch.bfloat16) -> list:
     """Terms (CPU tensors) of the LoKr artefact ``path`` (a directory or a file, resolved as the reference resolves it).  ``cfg`` (a
-    ``DitConfig``) checks every target's shape."""
+    ``DitConfig``) checks every target's shape.  A weight-decomposed adapter (``weight_decompose`` metadata with a ``dora_scale``
+    tensor per module; one without the other is refused) needs ``allow_dora=True`` and adds one ``DoraTerm`` per module behind the
+    ``KronTerm`` list: the axis from the tensor's shape, the magnitudes cast to ``dtype`` and ``eps = finfo(dtype).eps``, ``dtype``
+    being what the reference casts its decoder to."""
     wp = resolve_lokr_weights_path(path)
     if wp is None:
         raise ValueError(f"expected a LoKr artefact ({LOKR_WEIGHTS_FILENAME}, or a safetensors file with lokr_config metadata): {path}")
     from safetensors.torch import load_file
     lc = load_lokr_config(wp)
-    if lc["weight_decompose"]:
+    if lc["weight_decompose"] and not allow_dora:
         raise UnsupportedAdapter("LoKr adapter with weight_decompose (DoRA): not merged natively")
     if lc["use_tucker"]:
         raise UnsupportedAdapter("LoKr adapter with use_tucker: not merged natively")
@@ -190,16 +196,19 @@ def read_lokr_adapter(path: str, cfg=None) -> List[KronTerm]:
         mod, _, suffix = key.rpartition(".")
         if suffix == "lokr_t2":
             raise UnsupportedAdapter(f"LoKr tensor '{key}' (Tucker): not merged natively")
-        if suffix == "dora_scale":
+        if suffix == "dora_scale" and not allow_dora:
             raise UnsupportedAdapter(f"LoKr tensor '{key}' (DoRA): not merged natively")
-        if suffix not in _SUFFIXES or not mod:
+        if (suffix not in _SUFFIXES and suffix != "dora_scale") or not mod:
             raise UnsupportedAdapter(f"LoKr adapter tensor '{key}' is not a LoKr factor, alpha or scalar")
         if mod not in names:
             raise UnsupportedAdapter(f"LoKr target '{mod}' is outside the projections the native DiT merges "
                                      "(lycoris_layers_{i}_{self_attn,cross_attn}_{q,k,v,o}_proj, lycoris_layers_{i}_mlp_{gate,up,down}_proj)")
         parts.setdefault(mod, {})[suffix] = t
-    terms = []
+    terms, dora = [], []
     for mod, p in parts.items():
+        if ("dora_scale" in p) != bool(lc["weight_decompose"]):
+            raise UnsupportedAdapter(f"LoKr module {mod}: weight_decompose metadata and a dora_scale tensor belong together; "
+                                     f"{'the tensor is missing' if lc['weight_decompose'] else 'the metadata does not set it'}")
         f = {s: p.get("lokr_" + s) for s in ("w1", "w1_a", "w1_b", "w2", "w2_a", "w2_b")}
         t = KronTerm(names[mod], f["w1"], f["w1_a"], f["w1_b"], f["w2"], f["w2_a"], f["w2_b"], 1.0)
         try:
@@ -213,8 +222,13 @@ def read_lokr_adapter(path: str, cfg=None) -> List[KronTerm]:
         if "scalar" in p:
             scale *= float(p["scalar"].float().reshape(-1)[0])
         terms.append(t._replace(scale=scale))
+        if "dora_scale" in p:
+            out_l, out_k, in_m, in_n, _, _ = term_dims(t)
+            ds = p["dora_scale"]
+            dora.append(DoraTerm(t.name, ds.to(dtype), axis_of(ds.shape, out_l * out_k, in_m * in_n, f"LoKr module {mod}"),
+                                 dora_eps(dtype), 1.0))
     check_shapes(terms, cfg)
-    return terms
+    return terms + dora
 
 
 # ---------------------------------------------------------------- the live path
@@ -222,23 +236,30 @@ def _num(x) -> float:
     return float(x.detach().float().reshape(-1)[0]) if isinstance(x, torch.Tensor) else float(x)
 
 
-def terms_from_lycoris(net, cfg=None) -> List[KronTerm]:
+def terms_from_lycoris(net, cfg=None, allow_dora: bool = False) -> list:
     """Terms of a decoder's ``_lycoris_net``, by duck typing (no ``lycoris`` import): every module of ``net.loras`` is read as a
     LokrModule - ``lora_name``, ``lokr_w1`` or ``lokr_w1_a`` / ``lokr_w1_b``, ``lokr_w2`` or ``lokr_w2_a`` / ``lokr_w2_b``, and the
     term scale ``scale x multiplier x scalar`` (``set_multiplier``, the reference's toggle and scale control, writes ``multiplier``).
-    ``bypass_mode`` computes the same linear map and is accepted."""
+    ``bypass_mode`` computes the same linear map and is accepted.  A module with ``wd`` and a ``dora_scale`` needs
+    ``allow_dora=True`` and adds a ``DoraTerm`` behind the ``KronTerm`` list: ``g`` the ``dora_scale`` tensor itself, ``eps`` of its
+    dtype, ``scale = multiplier``.  Weight decomposition happens in the module's forward and not in bypass: both set is refused."""
     loras = getattr(net, "loras", None)
     if loras is None or isinstance(loras, (str, bytes)) or not hasattr(loras, "__iter__"):
         raise UnsupportedAdapter("LoKr / LyCORIS network on the decoder without a readable `loras` list: not merged natively")
     num_layers = getattr(cfg, "num_hidden_layers", None)
     names = lycoris_names(num_layers if num_layers is not None else 100)
-    terms = []
+    terms, dora = [], []
     for mod in loras:
         lname = getattr(mod, "lora_name", None)
         if getattr(mod, "lokr_t2", None) is not None or getattr(mod, "tucker", False):
             raise UnsupportedAdapter(f"LoKr module {lname} uses Tucker decomposition (lokr_t2): not merged natively")
-        if getattr(mod, "wd", False) or getattr(mod, "dora_scale", None) is not None:
+        wd, ds = bool(getattr(mod, "wd", False)), getattr(mod, "dora_scale", None)
+        if (wd or ds is not None) and not allow_dora:
             raise UnsupportedAdapter(f"LoKr module {lname} uses weight decomposition (DoRA): not merged natively")
+        if wd != (ds is not None):
+            raise UnsupportedAdapter(f"LoKr module {lname}: wd and dora_scale belong together: not merged natively")
+        if wd and getattr(mod, "bypass_mode", False):
+            raise UnsupportedAdapter(f"LoKr module {lname} sets both wd (DoRA) and bypass_mode: not merged natively")
         f = {s: getattr(mod, "lokr_" + s, None) for s in ("w1", "w1_a", "w1_b", "w2", "w2_a", "w2_b")}
         if not isinstance(lname, str) or (f["w1"] is None and f["w1_a"] is None) or (f["w2"] is None and f["w2_a"] is None):
             raise UnsupportedAdapter(f"LyCORIS module {lname or type(mod).__name__} is not a LoKr module: not merged natively")
@@ -246,7 +267,10 @@ def terms_from_lycoris(net, cfg=None) -> List[KronTerm]:
             raise UnsupportedAdapter(f"LoKr target '{lname}' is outside the projections the native DiT merges")
         scale = _num(getattr(mod, "scale", 1.0)) * _num(getattr(mod, "multiplier", 1.0)) * _num(getattr(mod, "scalar", 1.0))
         t = KronTerm(names[lname], f["w1"], f["w1_a"], f["w1_b"], f["w2"], f["w2_a"], f["w2_b"], scale)
-        term_dims(t)
+        out_l, out_k, in_m, in_n, _, _ = term_dims(t)
         terms.append(t)
+        if wd:
+            dora.append(DoraTerm(t.name, ds.detach(), axis_of(ds.shape, out_l * out_k, in_m * in_n, f"LoKr module {lname}"),
+                                 dora_eps(ds.dtype), _num(getattr(mod, "multiplier", 1.0))))
     check_shapes(terms, cfg)
-    return terms
+    return terms + dora

@@ -7,8 +7,10 @@ packed bf16 weights (``NativeDit.set_adapters``, include/ace355.h ``ace355_dit_s
 one adapter on one target weight, ``name`` the reference key of the target (``layers.3.cross_attn.k_proj.weight``).
 
 LoKr (LyCORIS) adapters are the other family the handle merges: ``ace355.lokr``.
-What the merge does not cover raises ``UnsupportedAdapter``, which the seam turns into the PyTorch path: DoRA, adapters
+What the merge does not cover raises ``UnsupportedAdapter``, which the seam turns into the PyTorch path: adapters
 with trained biases, ``modules_to_save``, ``fan_in_fan_out``, already merged PEFT modules, and targets outside the ten projection kinds.
+DoRA (``use_dora``) is merged too, but it is not an additive term: the readers return it as ``ace355.dora.DoraTerm`` only to a caller
+that asks with ``allow_dora=True`` and refuse it otherwise.
 This module needs neither ``peft`` nor ``lycoris`` (it reads the attributes the reference itself reads,
 core/lora/introspection.py:77-90).
 """
@@ -21,6 +23,8 @@ import re
 from typing import Dict, List, NamedTuple, Optional
 
 import torch
+
+from .dora import DoraTerm, check_g
 
 TARGET_KINDS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj",
                 "cross_attn.q_proj", "cross_attn.k_proj", "cross_attn.v_proj", "cross_attn.o_proj",
@@ -81,9 +85,11 @@ def peft_scaling(alpha: float, r: int, use_rslora: bool) -> float:
     return float(alpha) / (math.sqrt(r) if use_rslora else float(r))
 
 
-def read_peft_adapter(path: str, cfg=None) -> List[LoraTerm]:
+def read_peft_adapter(path: str, cfg=None, allow_dora: bool = False) -> list:
     """Terms (CPU tensors) of the PEFT LoRA directory ``path``: ``adapter_config.json`` + ``adapter_model.safetensors`` (or
-    ``adapter_model.bin``).  ``cfg`` (a ``DitConfig``) checks every target's shape."""
+    ``adapter_model.bin``).  ``cfg`` (a ``DitConfig``) checks every target's shape.  A ``use_dora`` adapter (the flag with a
+    ``lora_magnitude_vector`` per module; one without the other is refused) needs ``allow_dora=True`` and adds one ``DoraTerm`` per
+    module behind the ``LoraTerm`` list: the output axis, ``eps`` 0, ``scale`` 1."""
     if os.path.exists(os.path.join(path, LOKR_WEIGHTS_FILENAME)):
         raise UnsupportedAdapter("LoKr adapter (lokr_weights.safetensors): not merged natively")
     cfg_file = os.path.join(path, "adapter_config.json")
@@ -93,7 +99,7 @@ def read_peft_adapter(path: str, cfg=None) -> List[LoraTerm]:
         ac = json.load(f)
     if str(ac.get("peft_type", "LORA")).upper() != "LORA":
         raise UnsupportedAdapter(f"PEFT adapter type {ac.get('peft_type')}: only LoRA is merged natively")
-    if ac.get("use_dora"):
+    if ac.get("use_dora") and not allow_dora:
         raise UnsupportedAdapter("DoRA adapter: not merged natively")
     if ac.get("bias", "none") != "none" or ac.get("lora_bias"):
         raise UnsupportedAdapter("adapter with trained biases: not merged natively")
@@ -117,18 +123,30 @@ def read_peft_adapter(path: str, cfg=None) -> List[LoraTerm]:
     r0, a0, rs = int(ac.get("r", 8)), float(ac.get("lora_alpha", 8)), bool(ac.get("use_rslora", False))
     parts: Dict[str, Dict[str, torch.Tensor]] = {}
     key_re = re.compile(r"^(.*)\.lora_([AB])(?:\.([^.]+))?\.weight$")
+    mag_re = re.compile(r"^(.*)\.lora_magnitude_vector(?:\.([^.]+))?$")   # a parameter (older PEFT) or a module's .weight (newer)
     for key, t in sd.items():
         if "lora_magnitude_vector" in key:
-            raise UnsupportedAdapter("DoRA adapter (lora_magnitude_vector): not merged natively")
+            if not allow_dora:
+                raise UnsupportedAdapter("DoRA adapter (lora_magnitude_vector): not merged natively")
+            m = mag_re.match(key[:-len(".weight")] if key.endswith(".weight") else key)
+            if m is None:
+                raise UnsupportedAdapter(f"adapter tensor '{key}' is not a DoRA magnitude vector")
+            parts.setdefault(_module_path(m.group(1)), {})["g"] = t
+            continue
         m = key_re.match(key)
         if m is None:
             raise UnsupportedAdapter(f"adapter tensor '{key}' is not a LoRA A / B weight")
         module = _module_path(m.group(1))
         slot = parts.setdefault(module, {})
         slot[m.group(2)] = t
-    terms = []
+    terms, dora = [], []
     for module, ab in parts.items():
-        if set(ab) != {"A", "B"}:
+        if "A" not in ab and "B" not in ab:
+            raise UnsupportedAdapter(f"DoRA magnitude vector for {module}, which has no lora_A / lora_B pair: not merged natively")
+        if ("g" in ab) != bool(ac.get("use_dora")):
+            raise UnsupportedAdapter(f"LoRA module {module}: use_dora and a lora_magnitude_vector belong together; "
+                                     f"{'the vector is missing' if ac.get('use_dora') else 'adapter_config.json does not set use_dora'}")
+        if not {"A", "B"} <= set(ab):
             raise ValueError(f"LoRA module {module} lacks its lora_{'A' if 'A' not in ab else 'B'} weight")
         name = _target_name(module, getattr(cfg, "num_hidden_layers", None))
         r = int(_pattern_value(ac.get("rank_pattern"), module, r0))
@@ -136,8 +154,11 @@ def read_peft_adapter(path: str, cfg=None) -> List[LoraTerm]:
         if ab["A"].shape[0] != r:
             raise ValueError(f"LoRA module {module}: rank {ab['A'].shape[0]} in the weights, {r} in adapter_config.json")
         terms.append(LoraTerm(name, ab["A"], ab["B"], peft_scaling(alpha, r, rs)))
+        if "g" in ab:
+            dora.append(DoraTerm(name, ab["g"], False, 0.0, 1.0))
+            check_g(dora[-1], int(ab["B"].shape[0]), int(ab["A"].shape[1]))
     _check_shapes(terms, cfg)
-    return terms
+    return terms + dora
 
 
 def _active(mod) -> List[str]:
@@ -149,15 +170,28 @@ def _active(mod) -> List[str]:
     return [act] if isinstance(act, str) else list(act)
 
 
-def terms_from_decoder(decoder, cfg=None) -> list:
+def _magnitude(mod, a):
+    """``lora_magnitude_vector[a]`` of a PEFT module: a module with a ``.weight`` (newer PEFT) or the parameter itself (older)."""
+    mv = getattr(mod, "lora_magnitude_vector", None)
+    if mv is None or a not in mv:
+        return None
+    g = mv[a]
+    return getattr(g, "weight", g)
+
+
+def terms_from_decoder(decoder, cfg=None, allow_dora: bool = False) -> list:
     """Terms of a PEFT-wrapped decoder, by duck typing (no ``peft`` import): every module with ``lora_A`` / ``lora_B`` / ``scaling``
     whose adapters are enabled contributes ``scaling[a]``, ``lora_A[a].weight``, ``lora_B[a].weight`` for each active adapter ``a``.
-    A LyCORIS network on the decoder (``_lycoris_net``) contributes its LoKr modules as ``ace355.lokr.KronTerm``, ahead of them."""
+    A LyCORIS network on the decoder (``_lycoris_net``) contributes its LoKr modules as ``ace355.lokr.KronTerm``, ahead of them.
+    Weight-decomposed modules (LyCORIS ``wd``, PEFT ``use_dora``) need ``allow_dora=True`` and add their ``DoraTerm`` at the end."""
     terms: list = []
+    dora: list = []
     net = getattr(decoder, "_lycoris_net", None)
     if net is not None:   # LoKr (H/lora/lifecycle.py:101-155): its modules as Kronecker terms (lokr.py)
         from .lokr import terms_from_lycoris
-        terms += terms_from_lycoris(net, cfg)
+        lyc = terms_from_lycoris(net, cfg, allow_dora=allow_dora)
+        terms += [t for t in lyc if not isinstance(t, DoraTerm)]
+        dora += [t for t in lyc if isinstance(t, DoraTerm)]
     n_kron = len(terms)
     for mname, mod in decoder.named_modules():
         if hasattr(mod, "modules_to_save") and hasattr(mod, "original_module"):
@@ -170,26 +204,36 @@ def terms_from_decoder(decoder, cfg=None) -> list:
             raise UnsupportedAdapter(f"PEFT module {mname} has its adapters merged into the weight already")
         if getattr(mod, "fan_in_fan_out", False):
             raise UnsupportedAdapter(f"fan_in_fan_out LoRA at {mname}: not merged natively")
-        for a in _active(mod):
-            if a not in mod.lora_A:
-                continue
-            if (getattr(mod, "use_dora", None) or {}).get(a) or a in (getattr(mod, "lora_magnitude_vector", None) or {}):
+        live = [a for a in _active(mod) if a in mod.lora_A]
+        for a in live:
+            flag, g = bool((getattr(mod, "use_dora", None) or {}).get(a)), _magnitude(mod, a)
+            if (flag or g is not None) and not allow_dora:
                 raise UnsupportedAdapter(f"DoRA adapter '{a}' at {mname}: not merged natively")
+            if flag != (g is not None):
+                raise UnsupportedAdapter(f"adapter '{a}' at {mname}: use_dora and lora_magnitude_vector belong together: not merged natively")
+            if flag and len(live) > 1:
+                raise UnsupportedAdapter(f"DoRA adapter '{a}' at {mname} beside {len(live) - 1} more active adapter(s): not merged natively")
             if (getattr(mod, "lora_bias", None) or {}).get(a) or getattr(mod.lora_B[a], "bias", None) is not None:
                 raise UnsupportedAdapter(f"adapter '{a}' at {mname} trains a bias: not merged natively")
             name = _target_name(_module_path(mname), getattr(cfg, "num_hidden_layers", None))
             terms.append(LoraTerm(name, mod.lora_A[a].weight, mod.lora_B[a].weight, float(mod.scaling[a])))
+            if flag:
+                dora.append(DoraTerm(name, g.detach(), False, 0.0, 1.0))
+                check_g(dora[-1], int(mod.lora_B[a].weight.shape[0]), int(mod.lora_A[a].weight.shape[1]))
     _check_shapes(terms[n_kron:], cfg)
-    return terms
+    return terms + dora
 
 
 def fingerprint(terms) -> tuple:
     """A cheap key of a term list: names, scales, the A / B (for a ``KronTerm``: the factor) storages and their in-place version
-    counters."""
+    counters; for a ``DoraTerm`` its name, axis, eps, scale and the storage and version of ``g``."""
     def ident(x):
         return None if x is None else (x.data_ptr(), x._version, tuple(x.shape), str(x.device))
     key = []
     for t in terms:
+        if hasattr(t, "per_input"):   # ace355.dora.DoraTerm
+            key.append(("dora", t.name, bool(t.per_input), float(t.eps), float(t.scale), ident(t.g)))
+            continue
         if hasattr(t, "w1_a"):   # ace355.lokr.KronTerm
             key.append(("kron", t.name, float(t.scale)) + tuple(ident(x) for x in t[1:7]))
             continue

@@ -125,6 +125,10 @@ class KronTermC(C.Structure):
                 ("scale", C.c_float)]
 
 
+class DoraTermC(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("g_dev", C.c_void_p), ("per_input", C.c_int32), ("eps", C.c_float), ("multiplier", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/ace355.h declares
 SIGNATURES = {
     "ace355_last_error": (C.c_char_p, []),
@@ -144,6 +148,8 @@ SIGNATURES = {
     "ace355_dit_set_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ace355_dit_set_adapters": (C.c_int, [C.c_void_p, C.POINTER(LoraTermC), C.c_int, C.c_void_p]),
     "ace355_dit_set_adapters_mixed": (C.c_int, [C.c_void_p, C.POINTER(LoraTermC), C.c_int, C.POINTER(KronTermC), C.c_int, C.c_void_p]),
+    "ace355_dit_set_adapters_dora": (C.c_int, [C.c_void_p, C.POINTER(LoraTermC), C.c_int, C.POINTER(KronTermC), C.c_int,
+                                               C.POINTER(DoraTermC), C.c_int, C.c_void_p]),
     "ace355_dit_read_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ace355_dit_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "ace355_dit_set_graph": (C.c_int, [C.c_void_p, C.c_int]),

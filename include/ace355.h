@@ -320,6 +320,38 @@ typedef struct ace355_kron_term {
  * factor pointer (a full factor has rank 0, a decomposed one rank >= 1), a rank below 0, a non-finite scale, an unknown name. */
 int ace355_dit_set_adapters_mixed(ace355_dit* h, const ace355_lora_term* lora, int n_lora, const ace355_kron_term* kron, int n_kron,
                                   void* stream);
+/* DoRA (weight decomposition) on top of the additive terms of one target: LyCORIS LokrModule with `wd` (forward, not bypass:
+ * apply_weight_decompose) and PEFT LoRA with use_dora.  Neither library is part of the reference tree; the semantics are restated from
+ * their published modules and are unpinned.  With V = float(W0) + sum_j dW_j, the fp32 value ace355_dit_set_adapters_mixed forms
+ * before its single rounding (the terms in call order, their scales holding the multiplier),
+ *     n  = ||V||_2 over the row (per_input 0: one n, one g per output row) or over the column (per_input 1: per input column),
+ *     f  = 1 + m (g / (n + eps) - 1),        W' = bf16_rne(V f).
+ * LyCORIS: g = dora_scale ([out, 1]: per_input 0, [1, in]: per_input 1), m = multiplier, eps = finfo(dora_scale.dtype).eps (2^-7 for
+ * the bf16 the reference casts its decoder to).  PEFT: g = lora_magnitude_vector [out], per_input 0, eps 0, m 1.  Where n + eps == 0
+ * (PEFT, an all-zero row) f = 1: a documented deviation, PEFT would produce NaN.
+ * Arithmetic: V in fp32 exactly as the plain merge forms it.  The sum of squares accumulates in fp64 from the fp32 values of V, in a
+ * fixed order and without atomics: inside a 64 x 128 merge tile a thread's 8 columns (axis "out") or 4 rows (axis "in") in index order,
+ * then the lanes and waves of the tile in a fixed tree, then the tiles of the row or column in tile order.  n = sqrt(sum) and f are
+ * formed in fp64 and f is rounded to fp32 once; V f is one fp32 product followed by one bf16 rounding.  g_dev holds fp32 values on the
+ * device, n = out (per_input 0) or in (per_input 1) of them, indexed by the reference row / column whatever the packed layout; the
+ * caller converts them from the values the reference holds (after its cast to the model dtype).  Bit-reproducible call to call. */
+typedef struct ace355_dora_term {
+    const char*  name;       /* same ten target kinds as ace355_lora_term */
+    const float* g_dev;      /* out (per_input 0) or in (per_input 1) fp32 values on the device */
+    int32_t      per_input;  /* 0 | 1 */
+    float        eps;        /* >= 0 */
+    float        multiplier; /* m; 0 drops the term (f = 1: the additive terms alone, which the reference gives scale 0 then too) */
+} ace355_dora_term;
+/* ace355_dit_set_adapters_mixed plus at most one DoRA term per target: replaces the WHOLE adapter state, with the same synchrony,
+ * pristine-copy lifetime, stale-slot marking, precision refusals and invalidation of the folded-norm tables.  A target with a DoRA
+ * term runs twice through its merge kernel on `stream` (partial sums of squares into a scratch of the handle that grows on demand and
+ * is freed with it, then the rescaled write); targets without one keep the single-pass launches and the bits of
+ * ace355_dit_set_adapters_mixed.  n_dora 0 IS ace355_dit_set_adapters_mixed (the same launches, the same bits).  g_dev may be released
+ * when the call returns.  ERR_INVALID, nothing changed: two DoRA terms on one target, a DoRA term with multiplier != 0 on a target
+ * that no LoRA / Kronecker term of the call names, a null g_dev, per_input outside {0, 1}, a non-finite or negative eps, a non-finite
+ * multiplier, an unknown name, and everything ace355_dit_set_adapters_mixed refuses. */
+int ace355_dit_set_adapters_dora(ace355_dit* h, const ace355_lora_term* lora, int n_lora, const ace355_kron_term* kron, int n_kron,
+                                 const ace355_dora_term* dora, int n_dora, void* stream);
 /* Copy the live (merged) weight of one of the ten target kinds above to dst_dev in the reference layout [out, in] (the inverse of the
  * packing's row map), as ACE355_DTYPE_F32 or ACE355_DTYPE_BF16; enqueued on `stream`.  Tests, and export of merged weights. */
 int ace355_dit_read_weight(ace355_dit* h, const char* name, void* dst_dev, int dtype, void* stream);
