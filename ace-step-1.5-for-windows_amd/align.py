@@ -93,13 +93,13 @@ def stack(maps: torch.Tensor, prs: Sequence[Tuple[int, int]], bsz: int, H: int, 
     raise ValueError(f"maps of {N} rows do not fit a batch of {bsz}")
 
 
-def lyric_attention(dit, pred_latent: torch.Tensor, encoder_hidden_states: torch.Tensor, context_latents: torch.Tensor,
-                    inference_steps: int = 8, seed: Optional[int] = 42, layers_heads: Optional[Dict[int, Sequence[int]]] = None,
-                    kind: str = "timestamp", dtype: torch.dtype = torch.bfloat16):
-    """The maps of one ``get_lyric_timestamp`` (``kind="timestamp"``) or ``get_lyric_score`` (``"score"``, a (lm, dit) pair) call on the
-    native DiT ``dit``, in the handlers' layout and ``dtype``.  The inputs move to the DiT's device in ``dtype``, as the reference moves
-    them to ``self.device`` / ``self.dtype`` (H/lyric_alignment_common.py:19-34).  Item b's condition goes to slot b (slots [0, bsz)); the
-    next request sets its slots again."""
+def lyric_maps(dit, pred_latent: torch.Tensor, encoder_hidden_states: torch.Tensor, context_latents: torch.Tensor,
+               inference_steps: int = 8, seed: Optional[int] = 42, layers_heads: Optional[Dict[int, Sequence[int]]] = None,
+               kind: str = "timestamp", dtype: torch.dtype = torch.bfloat16) -> Tuple[torch.Tensor, List[Tuple[int, int]], int]:
+    """The fp32 maps [n_pairs, N, L, S] of one alignment call as ``NativeDit.cross_attention_maps`` returns them, with the sorted pairs
+    and the batch size: N == bsz for ``"timestamp"``, 2 bsz for ``"score"`` (the lm rows, then the dit rows).  The inputs move to the
+    DiT's device in ``dtype``, as the reference moves them to ``self.device`` / ``self.dtype`` (H/lyric_alignment_common.py:19-34).
+    Item b's condition goes to slot b (slots [0, bsz)); the next request sets its slots again."""
     prs = pairs(layers_heads if layers_heads is not None else DEFAULT_LAYERS_HEADS, dit.cfg)
     if kind not in KINDS:
         raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
@@ -118,5 +118,13 @@ def lyric_attention(dit, pred_latent: torch.Tensor, encoder_hidden_states: torch
         slots = slots * 2
         ctx = torch.cat([ctx, ctx], 0)
     tl = t.float().tolist()
-    maps = dit.cross_attention_maps(x.float(), ctx.float(), tl, tl, slots, prs)
+    return dit.cross_attention_maps(x.float(), ctx.float(), tl, tl, slots, prs), prs, bsz
+
+
+def lyric_attention(dit, pred_latent: torch.Tensor, encoder_hidden_states: torch.Tensor, context_latents: torch.Tensor,
+                    inference_steps: int = 8, seed: Optional[int] = 42, layers_heads: Optional[Dict[int, Sequence[int]]] = None,
+                    kind: str = "timestamp", dtype: torch.dtype = torch.bfloat16):
+    """The maps of one ``get_lyric_timestamp`` (``kind="timestamp"``) or ``get_lyric_score`` (``"score"``, a (lm, dit) pair) call on the
+    native DiT ``dit`` (``lyric_maps``), in the handlers' layout and ``dtype``."""
+    maps, prs, bsz = lyric_maps(dit, pred_latent, encoder_hidden_states, context_latents, inference_steps, seed, layers_heads, kind, dtype)
     return stack(maps, prs, bsz, dit.cfg.num_attention_heads, dtype)

@@ -22,6 +22,7 @@ from __future__ import annotations
 import contextlib
 import inspect
 import logging
+import os
 import time
 import traceback
 from typing import Any, Dict, List, Optional, Sequence, Union
@@ -33,6 +34,7 @@ from .config import DitConfig, TextEncoderConfig, VaeConfig
 logger = logging.getLogger("ace355")
 
 MAX_BATCH_SIZE = 8  # handler/service_generate_request.py:12
+_ALIGN_POST_ENV = os.environ.get("ACE355_ALIGN_POST", "") == "1"   # read once: the default of NativeDitMixin.native_lyric_post
 
 
 class NativeDitMixin:
@@ -40,6 +42,9 @@ class NativeDitMixin:
 
     use_native_dit: bool = False
     native_dit = None
+    # opt-in: get_lyric_timestamp / get_lyric_score run the stage after the maps on the GPU too (ace355.align_post) instead of handing a
+    # [layers, 16, L, S] stack to the host's aligners; ACE355_ALIGN_POST=1 turns it on for every host
+    native_lyric_post: bool = _ALIGN_POST_ENV
 
     def _init_native_dit(self) -> bool:
         """Counterpart of ``_init_mlx_dit``: convert weights from the already-loaded PyTorch module. Never raises."""
@@ -219,6 +224,48 @@ class NativeDitMixin:
         end = ids.index(151643) if 151643 in ids else len(ids)
         return ids[start:end], start, end
 
+    def _lyric_maps(self, pred_latent, encoder_hidden_states, context_latents, inference_steps, seed, layers, kind):
+        """The fp32 maps [n_pairs, N, L, S] of the alignment forward, where the native DiT wrote them (``ace355.align.lyric_maps``)."""
+        self._sync_native_adapters()
+        from .align import lyric_maps
+        maps, _prs, bsz = lyric_maps(self.native_dit, pred_latent, encoder_hidden_states, context_latents, inference_steps, seed, layers,
+                                     kind, getattr(self, "dtype", torch.bfloat16))
+        if bsz != 1:
+            raise ValueError("the native lyric stage takes one item per call, as the aligners do")
+        return maps
+
+    def _native_lyric_timestamp(self, pred_latent, encoder_hidden_states, context_latents, lyric_token_ids, total_duration_seconds,
+                                vocal_language, inference_steps, seed, layers) -> Optional[Dict[str, Any]]:
+        """``get_lyric_timestamp`` with the whole stage native (``native_lyric_post``): maps -> consensus matrix -> DTW on the GPU, one
+        synchronisation for the token spans, text on the host.  None when anything raises: the caller goes on with the host aligners."""
+        try:
+            from . import align_post
+            maps = self._lyric_maps(pred_latent, encoder_hidden_states, context_latents, inference_steps, seed, layers, "timestamp")
+            ids, start, end = self._lyric_segment(lyric_token_ids, vocal_language)
+            res = align_post.lyric_timestamps(maps, 0, start, end, self.text_tokenizer, ids, total_duration_seconds,
+                                              dtype=getattr(self, "dtype", torch.bfloat16), violence_level=2.0, medfilt_width=1)
+            return {"lrc_text": res["lrc_text"], "sentence_timestamps": res["sentence_timestamps"],
+                    "token_timestamps": res["token_timestamps"], "success": True, "error": None}
+        except Exception as exc:
+            logger.warning("[get_lyric_timestamp] native alignment stage failed (%s: %s); using the host aligner", type(exc).__name__, exc)
+            return None
+
+    def _native_lyric_score(self, pred_latent, encoder_hidden_states, context_latents, lyric_token_ids, vocal_language, inference_steps,
+                            seed, layers) -> Optional[Dict[str, Any]]:
+        """``get_lyric_score`` with the whole stage native: the lm and dit matrices go through the DTW and the metrics as one batch."""
+        try:
+            from . import align_post
+            maps = self._lyric_maps(pred_latent, encoder_hidden_states, context_latents, inference_steps, seed, layers, "score")
+            ids, start, end = self._lyric_segment(lyric_token_ids, vocal_language)
+            if start >= maps.shape[-2]:
+                return self._score_error("Lyrics indices out of bounds")
+            lm, dit = align_post.lyric_scores(maps, (0, 1), start, end, self.text_tokenizer, ids,
+                                              dtype=getattr(self, "dtype", torch.bfloat16), medfilt_width=1)
+            return {"lm_score": lm, "dit_score": dit, "success": True, "error": None}
+        except Exception as exc:
+            logger.warning("[get_lyric_score] native alignment stage failed (%s: %s); using the host aligner", type(exc).__name__, exc)
+            return None
+
     @staticmethod
     def _timestamp_error(message: str) -> Dict[str, Any]:
         return {"lrc_text": "", "sentence_timestamps": [], "token_timestamps": [], "success": False, "error": message}
@@ -246,6 +293,11 @@ class NativeDitMixin:
         if not isinstance(inference_steps, int) or inference_steps <= 0:
             return self._timestamp_error(f"inference_steps must be a positive non-zero integer, got {inference_steps!r}")
         layers = self._lyric_layers_config(custom_layers_config)
+        if self.native_lyric_post:
+            res = self._native_lyric_timestamp(pred_latent, encoder_hidden_states, context_latents, lyric_token_ids, total_duration_seconds,
+                                               vocal_language, inference_steps, seed, layers)
+            if res is not None:
+                return res
         try:
             matrix = self.lyric_attention(pred_latent, encoder_hidden_states, context_latents, inference_steps, seed, layers, "timestamp")
         except Exception as exc:
@@ -284,6 +336,11 @@ class NativeDitMixin:
         if not isinstance(inference_steps, int) or inference_steps <= 0:
             return self._score_error(f"Error generating score: inference_steps must be a positive non-zero integer, got {inference_steps!r}")
         layers = self._lyric_layers_config(custom_layers_config)
+        if self.native_lyric_post:
+            res = self._native_lyric_score(pred_latent, encoder_hidden_states, context_latents, lyric_token_ids, vocal_language,
+                                           inference_steps, seed, layers)
+            if res is not None:
+                return res
         try:
             lm, dit = self.lyric_attention(pred_latent, encoder_hidden_states, context_latents, inference_steps, seed, layers, "score")
         except Exception as exc:

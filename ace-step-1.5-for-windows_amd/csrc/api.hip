@@ -339,6 +339,64 @@ int ace355_cross_attention_probs(const void* q, const void* k, float* out, int N
     return launch_xattn_probs(a, (hipStream_t)stream);
 }
 
+size_t ace355_align_workspace_bytes(int n_pairs, int rows, int S, int batch) {
+    if (n_pairs < 1 || rows < 1 || S < 1 || batch < 1) return 0;
+    return align_workspace_bytes(n_pairs, rows, S, batch);
+}
+
+static int align_matrix_check(const char* who, const float* maps, int n_pairs, int N, int L, int S, int n, int row0, int rows, int w,
+                              const float* calc, const float* energy, const void* ws, size_t ws_bytes) {
+    const std::string p = std::string(who) + ": ";
+    ACE_CHECK(maps && calc && energy && ws, p + "null pointer");
+    ACE_CHECK(n_pairs >= 1 && n_pairs <= 64 && N >= 1 && L >= 1, p + "n_pairs / N / L");
+    ACE_CHECK(rows >= 1 && S >= 1 && rows <= 8192 && S <= 16384, p + "rows in [1, 8192] and S in [1, 16384]");
+    ACE_CHECK(n >= 0 && n < N, p + "n outside [0, N)");
+    ACE_CHECK(row0 >= 0 && row0 <= L - rows, p + "row range outside [0, L)");
+    ACE_CHECK(w >= 1 && w <= 31 && (w & 1), p + "medfilt_width must be odd and <= 31");
+    ACE_CHECK(ws_bytes >= align_workspace_bytes(n_pairs, rows, S, 1), p + "workspace too small");
+    return 0;
+}
+
+int ace355_align_timestamp_matrix(const float* maps, int n_pairs, int N, int L, int S, int n, int row0, int rows, float violence, int w,
+                                  int round_bf16, float* calc, float* energy, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = align_matrix_check("align_timestamp_matrix", maps, n_pairs, N, L, S, n, row0, rows, w, calc, energy, ws, ws_bytes)) return rc;
+    return launch_align_timestamp_matrix(maps + ((size_t)n * L + row0) * S, (size_t)N * L * S, n_pairs, rows, S, violence, w, round_bf16,
+                                         calc, energy, ws, (hipStream_t)stream);
+}
+
+int ace355_align_score_matrix(const float* maps, int n_pairs, int N, int L, int S, int n, int row0, int rows, int w, int round_bf16,
+                              float* calc, float* energy, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = align_matrix_check("align_score_matrix", maps, n_pairs, N, L, S, n, row0, rows, w, calc, energy, ws, ws_bytes)) return rc;
+    return launch_align_score_matrix(maps + ((size_t)n * L + row0) * S, (size_t)N * L * S, n_pairs, rows, S, w, round_bf16, calc, energy,
+                                     ws, (hipStream_t)stream);
+}
+
+int ace355_align_dtw(const float* m, int batch, int rows, int S, float sign, int32_t* path, int32_t* path_len, int32_t* token_frames,
+                     void* ws, size_t ws_bytes, void* stream) {
+    ACE_CHECK(m && path && path_len && token_frames && ws, "align_dtw: null pointer");
+    ACE_CHECK(batch >= 1 && batch <= 64, "align_dtw: batch in [1, 64]");
+    ACE_CHECK(rows >= 1 && S >= 1 && rows <= 8192 && S <= 16384, "align_dtw: rows in [1, 8192] and S in [1, 16384]");
+    ACE_CHECK(ws_bytes >= align_workspace_bytes(1, rows, S, batch), "align_dtw: workspace too small");
+    return launch_align_dtw(m, batch, rows, S, sign, path, path_len, token_frames, ws, (hipStream_t)stream);
+}
+
+int ace355_align_score_metrics(const float* energy, const int32_t* path, const int32_t* path_len, const int32_t* type_mask, int batch,
+                               int rows, int S, double time_weight, double overlap_frames, double instrumental_weight, double* out,
+                               void* ws, size_t ws_bytes, void* stream) {
+    ACE_CHECK(energy && path && path_len && type_mask && out && ws, "align_score_metrics: null pointer");
+    ACE_CHECK(batch >= 1 && batch <= 64, "align_score_metrics: batch in [1, 64]");
+    ACE_CHECK(rows >= 1 && S >= 1 && rows <= 8192 && S <= 16384, "align_score_metrics: rows in [1, 8192] and S in [1, 16384]");
+    ACE_CHECK(ws_bytes >= align_workspace_bytes(1, rows, S, batch), "align_score_metrics: workspace too small");
+    return launch_align_score_metrics(energy, path, path_len, type_mask, batch, rows, S, time_weight, overlap_frames, instrumental_weight,
+                                      out, ws, (hipStream_t)stream);
+}
+
+int ace355_align_median(const float* x, int outer, int n, int inner, float* out, void* stream) {
+    ACE_CHECK(x && out, "align_median: null pointer");
+    ACE_CHECK(n >= 1 && outer >= 1 && outer <= 65535 && inner >= 1 && inner <= 65535, "align_median: n >= 1, outer and inner in [1, 65535]");
+    return launch_align_median(x, outer, n, inner, out, (hipStream_t)stream);
+}
+
 int ace355_attention_masked(const void* q, const void* k, const void* v, void* out, int N, int Sq, int Skv, int Hq, int Hkv,
                             int window, float scale, const int32_t* kv_len_host, void* stream) {
     ACE_CHECK(kv_len_host, "attention_masked: null kv_len");

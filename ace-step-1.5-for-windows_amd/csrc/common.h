@@ -440,4 +440,16 @@ struct XattnArgs {
 };
 int launch_xattn_probs(const XattnArgs& a, hipStream_t s);
 
+// Lyric alignment stage after the maps (align_post.hip, ace355_align_*): maps point at item n, row row0 of [n_pairs][N][L][S]; pstride = N L S
+size_t align_workspace_bytes(int n_pairs, int rows, int S, int batch);
+int launch_align_median(const float* x, int outer, int n, int inner, float* out, hipStream_t s);
+int launch_align_timestamp_matrix(const float* maps, size_t pstride, int H, int R, int S, float violence, int w, int round_bf16, float* calc,
+                                  float* energy, void* ws, hipStream_t s);
+int launch_align_score_matrix(const float* maps, size_t pstride, int H, int R, int S, int w, int round_bf16, float* calc, float* energy,
+                              void* ws, hipStream_t s);
+int launch_align_dtw(const float* m, int batch, int R, int S, float sign, int32_t* path, int32_t* path_len, int32_t* frames, void* ws,
+                     hipStream_t s);
+int launch_align_score_metrics(const float* energy, const int32_t* path, const int32_t* path_len, const int32_t* mask, int batch, int R,
+                               int S, double time_weight, double overlap, double inst_weight, double* out, void* ws, hipStream_t s);
+
 }  // namespace ace355

@@ -714,6 +714,42 @@ int ace355_conv1d_nlc(const void* x_dev, const void* w_dev, const float* bias_de
                       const float* beta_dev, const void* res_dev, void* y_dev, int B, int L, int Cin, int Cout,
                       int taps, int dilation, void* stream);
 
+/* ---- Lyric alignment after the maps (align_post.hip): what MusicStampsAligner / MusicLyricScorer do on the host, on the maps as
+ * ace355_dit_cross_attention_maps wrote them: maps dev f32 [n_pairs][N][L][S]; item n; lyric rows [row0, row0 + rows).  round_bf16 != 0
+ * rounds every map value to bf16 and back on load (the handlers' cast to the host dtype).  Everything is enqueued on `stream`; nothing is
+ * allocated: `ws` is a device workspace of at least ace355_align_workspace_bytes(n_pairs, rows, S, batch) bytes (the largest need of the
+ * four calls below for those sizes; pass 1 for a size a call does not take).  The same call gives the same bits.
+ * Limits: n_pairs <= 64, rows <= 8192, S <= 16384, batch <= 64, medfilt_width odd and <= 31.  ERR_INVALID, nothing enqueued: a null
+ * pointer, rows < 1, S < 1, a row range outside [0, L), n outside [0, N), an even or oversized medfilt_width, a shape over the limits, a
+ * workspace that is too small. */
+size_t ace355_align_workspace_bytes(int n_pairs, int rows, int S, int batch);
+/* MusicStampsAligner._apply_bidirectional_consensus: p = softmax_S * softmax_rows; relu(p - v median_S p); relu(p - v median_rows p);
+ * p^2; energy = mean over pairs; z-score with the population mean / std of the whole block; median filter of width w along S (reflect
+ * padding; the identity when S <= w / 2); calc = mean over pairs.  Medians are torch.quantile(q = 0.5) exactly; means and the std
+ * accumulate in fp64.  calc, energy dev f32 [rows][S]. */
+int ace355_align_timestamp_matrix(const float* maps_dev, int n_pairs, int N, int L, int S, int n, int row0, int rows, float violence_level,
+                                  int medfilt_width, int round_bf16, float* calc_dev, float* energy_dev, void* ws, size_t ws_bytes,
+                                  void* stream);
+/* MusicLyricScorer._preprocess_attention: mean over pairs, median filter, min-max normalisation (zeros when max - min <= 1e-9) ->
+ * energy; calc = energy^2. */
+int ace355_align_score_matrix(const float* maps_dev, int n_pairs, int N, int L, int S, int n, int row0, int rows, int medfilt_width,
+                              int round_bf16, float* calc_dev, float* energy_dev, void* ws, size_t ws_bytes, void* stream);
+/* dtw_cpu + _backtrace on x = sign * m for `batch` matrices m dev f32 [batch][rows][S]: fp32 cost table, predecessor diagonal if
+ * c0 < c1 && c0 < c2, else up if c1 < c0 && c1 < c2, else left; one workgroup per matrix on anti-diagonals, each cell the sequential
+ * code's arithmetic.  path dev i32 [batch][2][rows + S] (row 0 lyric rows, row 1 frames), right-aligned: the last path_len[b] entries;
+ * token_frames dev i32 [batch][rows][2]: the first and last frame of each lyric row on the path, -1 for a row the path skips. */
+int ace355_align_dtw(const float* m_dev, int batch, int rows, int S, float sign, int32_t* path_dev, int32_t* path_len_dev,
+                     int32_t* token_frames_dev, void* ws, size_t ws_bytes, void* stream);
+/* MusicLyricScorer._compute_alignment_metrics in fp64 for `batch` matrices: energy dev f32 [batch][rows][S], path / path_len as
+ * ace355_align_dtw wrote them, type_mask dev i32 [rows] (1 lyric, 0 tag; shared by the batch).  out dev f64 [batch][3]: coverage,
+ * monotonicity, path confidence (1, 1, 0 in the empty cases). */
+int ace355_align_score_metrics(const float* energy_dev, const int32_t* path_dev, const int32_t* path_len_dev, const int32_t* type_mask_dev,
+                               int batch, int rows, int S, double time_weight, double overlap_frames, double instrumental_weight,
+                               double* out_dev, void* ws, size_t ws_bytes, void* stream);
+/* Test hook of the selection behind the medians: x dev f32 [outer][n][inner] -> out dev f32 [outer][inner], torch.quantile(x, 0.5, dim=1)
+ * bit for bit.  n >= 1, inner and outer in [1, 65535]. */
+int ace355_align_median(const float* x_dev, int outer, int n, int inner, float* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
