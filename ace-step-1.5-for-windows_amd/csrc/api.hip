@@ -4,8 +4,10 @@
 
 #include <algorithm>
 #include <string>
+#include <vector>
 
 #include "../../include/ace355.h"
+#include "adapter_plan.h"
 #include "attn_plan.h"
 #include "gemm_plan.h"
 #include <dlfcn.h>
@@ -124,6 +126,65 @@ int ace355_attn_plan(const ace355_attn_request* r, ace355_attn_plan_info* out) {
     ACE_CHECK(r->N > 0 && r->Sq > 0 && r->Skv > 0 && r->Hq > 0 && r->Hkv > 0 && r->Hq % r->Hkv == 0 && r->part_floats >= 0, "attn_plan: empty problem or Hq % Hkv");
     const AttnPlan p = attn_plan_query(AttnRequest{r->N, r->Sq, r->Skv, r->Hq, r->Hkv, r->window, r->cu_slots, r->has_kv_len, r->mx_out, (long)r->part_floats});
     *out = ace355_attn_plan_info{p.kernel, p.nw, p.grid_x, p.grid_y, p.grid_z, p.threads, p.kv_split, p.merge_grid, p.mx_out_ok};
+    return ACE355_OK;
+}
+
+int ace355_adapter_plan(const ace355_dit_config* cfg, const ace355_lora_term* lora, int n_lora, const ace355_kron_term* kron, int n_kron,
+                        const ace355_dora_term* dora, int n_dora, const char* const* applied, int n_applied,
+                        const ace355_adapter_plan_rows* rows, ace355_adapter_plan_info* info) {
+    ACE_CHECK(cfg && rows && info, "adapter_plan: null pointer");
+    ACE_CHECK(cfg->hidden_size > 0 && cfg->intermediate_size > 0 && cfg->num_layers > 0 && cfg->num_heads > 0 && cfg->num_kv_heads > 0,
+              "adapter_plan: configuration");
+    ACE_CHECK(n_applied >= 0 && (n_applied == 0 || applied), "adapter_plan: applied names");
+    AdapterCall call{lora, n_lora, kron, n_kron, dora, n_dora, nullptr, nullptr, nullptr, nullptr, 0};
+    std::vector<AdapterRef> lref, kref, dref, aref;
+    if (!adapter_arrays_error(call)) {   // (else plan_adapters refuses before it reads a reference)
+        for (int i = 0; i < n_lora; ++i) lref.push_back(adapter_ref_of(*cfg, lora[i].name));
+        for (int i = 0; i < n_kron; ++i) kref.push_back(adapter_ref_of(*cfg, kron[i].name));
+        for (int i = 0; i < n_dora; ++i) dref.push_back(adapter_ref_of(*cfg, dora[i].name));
+    }
+    for (int i = 0; i < n_applied; ++i) ACE_CHECK(applied[i] && adapter_ref_of(*cfg, applied[i]).id >= 0, "adapter_plan: an applied name is not a target");
+    std::vector<const char*> names(applied, applied + n_applied);   // each once, in the order a handle keeps its applied set in
+    std::sort(names.begin(), names.end(), [](const char* x, const char* y) { return strcmp(x, y) < 0; });
+    names.erase(std::unique(names.begin(), names.end(), [](const char* x, const char* y) { return strcmp(x, y) == 0; }), names.end());
+    for (const char* n : names) aref.push_back(adapter_ref_of(*cfg, n));
+    call.lora_ref = lref.data(); call.kron_ref = kref.data(); call.dora_ref = dref.data();
+    call.applied = aref.data(); call.n_applied = (int)aref.size();
+    const AdapterPlan p = plan_adapters(call);
+    if (p.code) { set_error(p.error); return p.code; }
+    using adapter_detail::row_at;
+    *info = ace355_adapter_plan_info{};
+    info->n_targets = (int)p.targets.size(); info->n_merged = p.n_merged; info->n_launches = (int)p.launches.size();
+    info->n_lora_terms = (int)(p.bytes[SEC_LORA_TERMS] / sizeof(LoraTermDev)); info->n_kron_terms = (int)(p.bytes[SEC_KRON_TERMS] / sizeof(KronTermDev));
+    info->n_factors = (int)(p.bytes[SEC_KRON_FACTORS] / sizeof(KronFactorDev));
+    const int n_dl = (int)(p.bytes[SEC_DORA_LORA_ROWS] / sizeof(DoraDev)), n_dk = (int)(p.bytes[SEC_DORA_KRON_ROWS] / sizeof(DoraDev));
+    info->n_dora = n_dl + n_dk;
+    info->stale_kv = p.stale_kv; info->stale_o = p.stale_o;
+    info->table_bytes = (int64_t)p.table.size(); info->kscratch_floats = (int64_t)p.kscratch_floats; info->dscratch_bytes = (int64_t)p.dscratch_bytes;
+    for (int s = 0; s < ADAPTER_SECTIONS; ++s) { info->section_at[s] = (int64_t)p.at[s]; info->section_bytes[s] = (int64_t)p.bytes[s]; }
+    for (int i = 0; rows->targets && i < info->n_targets && i < rows->cap_targets; ++i) {
+        const AdapterTarget& t = p.targets[i];
+        rows->targets[i] = ace355_adapter_target_info{t.name, t.cls, t.row, t.rows, t.cols, t.tile0, t.tiles_n, t.term0, t.nterms, t.restored};
+    }
+    for (int i = 0; rows->launches && i < info->n_launches && i < rows->cap_launches; ++i) {
+        const AdapterLaunch& l = p.launches[i];
+        rows->launches[i] = ace355_adapter_launch_info{l.kernel, l.pass, l.n, l.grid_x, l.grid_y, l.lds_bytes, {l.sec[0], l.sec[1], l.sec[2]}};
+    }
+    for (int i = 0; rows->kron && i < info->n_kron_terms && i < rows->cap_kron; ++i) {
+        const KronTermDev u = row_at<KronTermDev>(p, SEC_KRON_TERMS, i);
+        rows->kron[i] = ace355_adapter_kron_info{u.out_l, u.out_k, u.in_m, u.in_n, u.wide, u.w1_f32, u.w2_f32, u.scale,
+                                                 u.w1_f32 ? (int64_t)(uintptr_t)u.w1 : -1, u.w2_f32 ? (int64_t)(uintptr_t)u.w2 : -1};
+    }
+    for (int i = 0; rows->factors && i < info->n_factors && i < rows->cap_factors; ++i) {
+        const KronFactorDev f = row_at<KronFactorDev>(p, SEC_KRON_FACTORS, i);
+        rows->factors[i] = ace355_adapter_factor_info{f.rows, f.cols, f.rank, f.tile0, f.tiles_n, 0, (int64_t)(uintptr_t)f.dst};
+    }
+    for (int i = 0; rows->dora && i < info->n_dora && i < rows->cap_dora; ++i) {
+        const bool k = i >= n_dl;
+        const DoraDev v = row_at<DoraDev>(p, k ? SEC_DORA_KRON_ROWS : SEC_DORA_LORA_ROWS, k ? i - n_dl : i);
+        rows->dora[i] = ace355_adapter_dora_info{k ? ADAPTER_DORA_KRON : ADAPTER_DORA_LORA, v.per_input, v.n, v.ntiles, v.eps, v.m,
+                                                 (int64_t)(uintptr_t)v.part, (int64_t)(uintptr_t)v.f};
+    }
     return ACE355_OK;
 }
 

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <string>
 
+#include "adapter_plan.h"
+
 namespace ace355 {
 
 // ------------------------------------------------------------------ error plumbing (host)
@@ -39,7 +41,7 @@ struct RoctxRange {
 };
 
 // ------------------------------------------------------------------ device types
-typedef uint16_t bf16_t;  // raw bf16 bits
+// (bf16_t, raw bf16 bits: adapter_plan.h)
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -358,74 +360,17 @@ struct ConvArgs {
 int launch_conv(const ConvArgs& a, hipStream_t s);
 int launch_ncl_to_nlc(const float* z, bf16_t* out, int B, int C, int T, hipStream_t s);
 
-// LoRA merge (lora.hip, ace355_dit_set_adapters): one launch over the tiles of every target weight the call rewrites
-constexpr int LORA_TILE_ROWS = 64, LORA_TILE_COLS = 128;
-struct LoraTermDev {
-    const bf16_t* A;   // lora_A.weight [rank, cols]
-    const bf16_t* B;   // lora_B.weight [rows, rank]
-    int rank;
-    float scale;
-};
-struct LoraTargetDev {
-    bf16_t* dst;         // live packed buffer
-    const bf16_t* src;   // its pristine copy (same layout)
-    long ld;             // packed row pitch (= cols)
-    long row0;           // pack_row arguments of the target
-    int mode, p0;
-    int rows, cols;      // reference shape [out, in]; cols % 8 == 0
-    int tile0, tiles_n;  // first tile of this target in the launch, column tiles per row tile
-    int term0, nterms;   // terms [term0, term0 + nterms) of the term table; 0: copy the pristine rows back
-};
-// DoRA (dora.h, dora.hip, ace355_dit_set_adapters_dora): W' = bf16_rne(V f), V the fp32 value the plain merge would round and
-// f = 1 + m (g / (||V|| + eps) - 1) per row (per_input 0) or per column (per_input 1).  A DoRA target's tiles run twice through its
-// merge kernel (`pass` 1: fp64 partial sums of squares into `part`; `pass` 2: V f), launch_dora_factors in between forms f.  One
-// DoraDev per target of a DoRA launch, at the target's index.
-struct DoraDev {
-    double* part;        // per_input 0: [tiles_n][rows], per_input 1: [tiles_m][cols] (scratch of the handle)
-    float* f;            // [n]
-    const float* g;      // [n]: dora_scale / lora_magnitude_vector in reference order
-    int per_input;
-    int n, ntiles;       // rows and column tiles per row, or columns and row tiles per column
-    float eps, m;
-};
-int launch_dora_factors(const DoraDev* dora_dev, int n_targets, int max_n, hipStream_t s);
-// `pass` 0: the plain merge (dora_dev unused)
+// Adapter merges (lora.hip, lokr.hip, dora.hip; ace355_dit_set_adapters / _mixed / _dora).  The tables they read and the plan that fills
+// them: adapter_plan.h.  `pass` 0: the plain merge (dora_dev unused); 1 / 2: the two passes of a DoRA target.  launch_dora_factors runs
+// between them: `chunks` blocks of 256 indices (the longest target's) x n_targets.
+int launch_dora_factors(const DoraDev* dora_dev, int n_targets, int chunks, hipStream_t s);
 int launch_lora_merge(const LoraTargetDev* targets_dev, int n_targets, int total_tiles, const LoraTermDev* terms_dev, hipStream_t s,
                       const DoraDev* dora_dev = nullptr, int pass = 0);
 int launch_lora_read(const bf16_t* w, long ld, int mode, long row0, int p0, long rows, long cols, void* dst, int dst_is_bf16,
                      hipStream_t s);
-
-// LoKr merge (lokr.hip, ace355_dit_set_adapters_mixed): W' = bf16_rne(float(W0) + sum_j s_j (W1_j kron W2_j)).  A pre-pass writes the
-// fp32 product a @ b of every decomposed factor into a scratch table of the handle; one merge launch then covers the tiles of every
-// Kronecker target (LoraTargetDev, as the LoRA merge: nterms 0 copies the pristine rows back).
-constexpr int LOKR_TILE_ROWS = 64, LOKR_TILE_COLS = 128;
-// LDS floats of the merge kernel: the W1 and W2 sub-blocks of one (tile, term).  With a = min(out_k, 64), b = min(in_n, 128) a tile
-// meets at most (63 / a + 2)(127 / b + 2) entries of W1 (exactly 64 / a resp. 128 / b where a | 64 resp. b | 128, tiles being aligned)
-// and a x b of W2 (row pitch lokr_w2_pitch(b)): the sum peaks at a = b = 1 (a dense W1) with 64 x 128 + 1 and at a = 64, b = 128 with
-// 4 + 64 x 132.  A launch asks for the largest need among its terms (lokr_lds_floats), so the usual splits leave room for more
-// workgroups per CU.
-constexpr int LOKR_LDS_FLOATS = 64 * 132 + 64;
-// LDS row pitch of a staged W2 block of nn columns: a multiple of 4 floats where the 16-byte paths need it, odd otherwise
-__host__ __device__ __forceinline__ int lokr_w2_pitch(int nn) { return nn % 4 == 0 ? nn + 4 : nn | 1; }
-struct KronFactorDev {   // one decomposed factor: dst [rows, cols] fp32 = a [rows, rank] @ b [rank, cols]
-    const bf16_t* a;
-    const bf16_t* b;
-    float* dst;
-    int rows, cols, rank;
-    int tile0, tiles_n;  // first tile of this factor in the pre-pass launch, column tiles per row tile
-};
-struct KronTermDev {
-    const void* w1;      // [out_l, in_m]: bf16 as given (w1_f32 0) or the fp32 product in the scratch table (w1_f32 1)
-    const void* w2;      // [out_k, in_n], likewise
-    int w1_f32, w2_f32;
-    int out_l, out_k, in_m, in_n;
-    float scale;
-    int wide;            // in_n % 8 == 0, in_n <= LOKR_TILE_COLS and w2 16-byte aligned: W2 is staged and read 16 bytes at a time
-};
-int lokr_lds_floats(int out_k, int in_n);   // worst case over the tiles of a term (<= LOKR_LDS_FLOATS for every split)
 int launch_lokr_factors(const KronFactorDev* jobs_dev, int n_jobs, int total_tiles, hipStream_t s);
 int launch_lokr_merge(const LoraTargetDev* targets_dev, int n_targets, int total_tiles, const KronTermDev* terms_dev, int lds_floats,
-                      hipStream_t s, const DoraDev* dora_dev = nullptr, int pass = 0);   // `pass` as launch_lora_merge
+                      hipStream_t s, const DoraDev* dora_dev = nullptr, int pass = 0);
 
 // Cross-attention probabilities (xattn_probs.hip, ace355_dit_cross_attention_maps / ace355_cross_attention_probs): for query heads
 // heads[p], out[p][n][j][s] = softmax_j(scale q[n][s] . k[n][j]) in fp32, j < Skv, s < Sq

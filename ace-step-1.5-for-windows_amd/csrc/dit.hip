@@ -184,11 +184,39 @@ struct ace355_dit : LoadBase {
     long gemm_launches = 0;
 };
 
+AdapterRef ace355::adapter_ref_of(const ace355_dit_config& c, const char* name) {
+    int li;
+    std::string r;
+    const int kind = name && parse_layer_index(name, 0, c.num_layers, &li, &r) ? proj_kind(r) : -1;
+    return kind < 0 ? AdapterRef{name, -1, 0, 0, 0} : adapter_ref(c, name, li, kind);
+}
+
 namespace {
+
+// Packed destination of projection `kind` (adapter_plan.h ProjKind) of a layer; the shapes are proj_shape's
+PackDest proj_dest(const ace355_dit* h, const LayerW& L, int kind) {
+    auto out = [&](int k) { return proj_shape(h->cfg, k).rows; };
+    const ProjShape p = proj_shape(h->cfg, kind);
+    auto rows = [&](bf16_t* dst, long row0) { return pack_rows(dst, 1, p.rows, p.cols, p.cols, row0); };
+    switch (kind) {
+    // self-attention q / k rows in the head-pair order (common.h PackMode): RoPE partners adjacent
+    case PROJ_SELF_Q: return PackDest{L.wqkv, 1, PACK_ROWS_HEADPAIR, p.rows, p.cols, p.cols, 0, 0, 0};
+    case PROJ_SELF_K: return PackDest{L.wqkv, 1, PACK_ROWS_HEADPAIR, p.rows, p.cols, p.cols, out(PROJ_SELF_Q), 0, 0};
+    case PROJ_SELF_V: return rows(L.wqkv, out(PROJ_SELF_Q) + out(PROJ_SELF_K));
+    case PROJ_SELF_O: return rows(L.wo, 0);
+    case PROJ_CROSS_Q: return rows(L.wq_c, 0);
+    case PROJ_CROSS_K: return rows(L.wkv_c, 0);
+    case PROJ_CROSS_V: return rows(L.wkv_c, out(PROJ_CROSS_K));
+    case PROJ_CROSS_O: return rows(L.wo_c, 0);
+    case PROJ_GATE: return PackDest{L.wgu, 1, PACK_ROWS_IL32, p.rows, p.cols, p.cols, 0, 0, 0};
+    case PROJ_UP: return PackDest{L.wgu, 1, PACK_ROWS_IL32, p.rows, p.cols, p.cols, 0, 1, 0};
+    default: return rows(L.wdown, 0);
+    }
+}
 
 // Map a reference state_dict key to its packed destination.
 bool resolve(ace355_dit* h, const std::string& name, PackDest* d) {
-    const long D = h->D, F = h->F, QD = h->QD, KVD = h->KVD;
+    const long D = h->D;
     auto rows = [&](void* dst, int bf, long r, long c, long ld, long row0) {
         *d = PackDest{dst, bf, PACK_ROWS, r, c, ld, row0, 0, 0};
         return true;
@@ -202,22 +230,12 @@ bool resolve(ace355_dit* h, const std::string& name, PackDest* d) {
         if (r == "self_attn_norm.weight") return rows(L.n_sa, 0, 1, D, D, 0);
         if (r == "cross_attn_norm.weight") return rows(L.n_ca, 0, 1, D, D, 0);
         if (r == "mlp_norm.weight") return rows(L.n_mlp, 0, 1, D, D, 0);
-        // self-attention q / k rows in the head-pair order (common.h PackMode): RoPE partners adjacent
-        if (r == "self_attn.q_proj.weight") { *d = PackDest{L.wqkv, 1, PACK_ROWS_HEADPAIR, QD, D, D, 0, 0, 0}; return true; }
-        if (r == "self_attn.k_proj.weight") { *d = PackDest{L.wqkv, 1, PACK_ROWS_HEADPAIR, KVD, D, D, QD, 0, 0}; return true; }
-        if (r == "self_attn.v_proj.weight") return rows(L.wqkv, 1, KVD, D, D, QD + KVD);
-        if (r == "self_attn.o_proj.weight") return rows(L.wo, 1, D, QD, QD, 0);
         if (r == "self_attn.q_norm.weight") return rows(L.qn_s, 0, 1, 128, 128, 0);
         if (r == "self_attn.k_norm.weight") return rows(L.kn_s, 0, 1, 128, 128, 0);
-        if (r == "cross_attn.q_proj.weight") return rows(L.wq_c, 1, QD, D, D, 0);
-        if (r == "cross_attn.k_proj.weight") return rows(L.wkv_c, 1, KVD, D, D, 0);
-        if (r == "cross_attn.v_proj.weight") return rows(L.wkv_c, 1, KVD, D, D, KVD);
-        if (r == "cross_attn.o_proj.weight") return rows(L.wo_c, 1, D, QD, QD, 0);
         if (r == "cross_attn.q_norm.weight") return rows(L.qn_c, 0, 1, 128, 128, 0);
         if (r == "cross_attn.k_norm.weight") return rows(L.kn_c, 0, 1, 128, 128, 0);
-        if (r == "mlp.gate_proj.weight") { *d = PackDest{L.wgu, 1, PACK_ROWS_IL32, F, D, D, 0, 0, 0}; return true; }
-        if (r == "mlp.up_proj.weight") { *d = PackDest{L.wgu, 1, PACK_ROWS_IL32, F, D, D, 0, 1, 0}; return true; }
-        if (r == "mlp.down_proj.weight") return rows(L.wdown, 1, D, F, F, 0);
+        const int kind = proj_kind(r);
+        if (kind >= 0) { *d = proj_dest(h, L, kind); return true; }
         return false;
     }
     const int C = h->cfg.in_channels, P = h->cfg.patch_size, OC = h->OUTC;
@@ -245,31 +263,23 @@ bool resolve(ace355_dit* h, const std::string& name, PackDest* d) {
     return false;
 }
 
-// The ten LoRA target kinds of a layer (ace355_dit_set_adapters / ace355_dit_read_weight): the Linear projections of resolve(), by
+// The adapter target kinds of a layer (ace355_dit_set_adapters / ace355_dit_read_weight): the Linear projections of resolve(), by
 // their canonical reference key only
 bool lora_target(ace355_dit* h, const std::string& name, PackDest* d) {
-    static const char* kinds[] = {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
-                                  "cross_attn.q_proj.weight", "cross_attn.k_proj.weight", "cross_attn.v_proj.weight", "cross_attn.o_proj.weight",
-                                  "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight"};
-    int li;
-    std::string r;
-    if (!parse_layer_index(name, 0, h->NL, &li, &r)) return false;
-    bool kind = false;
-    for (const char* k : kinds) kind = kind || r == k;
-    return kind && resolve(h, name, d);
+    const AdapterRef r = adapter_ref_of(h->cfg, name.c_str());
+    if (r.id < 0) return false;
+    *d = proj_dest(h, h->layers[r.id / PROJ_KINDS], r.id % PROJ_KINDS);
+    return true;
 }
-// elements of the packed projection buffer `buf` (one of a layer's seven)
+// elements of the packed projection buffer `buf` (one of a layer's seven): those of the projections packed into it
 size_t packed_elems(const ace355_dit* h, const void* buf) {
-    const size_t D = h->D, F = h->F, QD = h->QD, KVD = h->KVD;
-    for (const LayerW& L : h->layers) {
-        if (buf == L.wqkv) return (QD + 2 * KVD) * D;
-        if (buf == L.wo || buf == L.wo_c) return D * QD;
-        if (buf == L.wq_c) return QD * D;
-        if (buf == L.wkv_c) return 2 * KVD * D;
-        if (buf == L.wgu) return 2 * F * D;
-        if (buf == L.wdown) return D * F;
-    }
-    return 0;
+    size_t n = 0;
+    for (const LayerW& L : h->layers)
+        for (int k = 0; k < PROJ_KINDS; ++k) {
+            const PackDest d = proj_dest(h, L, k);
+            if (d.dst == buf) n += (size_t)(d.rows * d.cols);
+        }
+    return n;
 }
 void lora_free_pristine(ace355_dit* h) {
     for (auto& pr : h->lora.pristine) hipFree(pr.second);
@@ -1695,14 +1705,24 @@ int ace355_dit_graph_stats(ace355_dit* h, int64_t* captures, int64_t* replays) {
     return ACE355_OK;
 }
 
-// ace355_dit_set_adapters (n_kron 0: its launches are those of the LoRA merge alone), ace355_dit_set_adapters_mixed (n_dora 0: nothing
-// below adds to its launches or tables) and ace355_dit_set_adapters_dora
+// (Re)allocates a device buffer of the handle that only grows: *have is its size in `unit`s
+static int grow(void** buf, size_t* have, size_t need, size_t unit) {
+    if (need <= *have) return 0;
+    if (*buf) hipFree(*buf);
+    *buf = nullptr; *have = 0;
+    ACE_HIP(hipMalloc(buf, need * unit));
+    *have = need;
+    return 0;
+}
+
+// ace355_dit_set_adapters (n_kron 0), ace355_dit_set_adapters_mixed (n_dora 0) and ace355_dit_set_adapters_dora: the handle's part.
+// Which targets, tables, scratch regions and launches the call comes to is plan_adapters' answer (adapter_plan.h; ace355_adapter_plan
+// gives it without a handle).
 static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n_terms, const ace355_kron_term* kron, int n_kron,
                              const ace355_dora_term* dora, int n_dora, void* stream) {
     ACE_CHECK(h, "set_adapters: null handle");
-    ACE_CHECK(n_terms >= 0 && (n_terms == 0 || terms), "set_adapters: terms");
-    ACE_CHECK(n_kron >= 0 && (n_kron == 0 || kron), "set_adapters: kron terms");
-    ACE_CHECK(n_dora >= 0 && (n_dora == 0 || dora), "set_adapters: dora terms");
+    AdapterCall call{terms, n_terms, kron, n_kron, dora, n_dora, nullptr, nullptr, nullptr, nullptr, 0};
+    if (const char* m = adapter_arrays_error(call)) ACE_CHECK(false, m);
     if (!h->finalized) { set_error("set_adapters: call ace355_dit_finalize first"); return ACE355_ERR_STATE; }
     if (h->precision != ACE355_PRECISION_BF16 || h->weights_fp8wo) {   // H/lora/lifecycle.py:173-178
         set_error(std::string("set_adapters: LoRA loading is not supported on quantized models. Current precision: ") +
@@ -1710,255 +1730,57 @@ static int set_adapters_impl(ace355_dit* h, const ace355_lora_term* terms, int n
         return ACE355_ERR_STATE;
     }
     hipStream_t s = (hipStream_t)stream;
-    // the terms per target, in call order; scale 0 drops a term
-    std::vector<std::string> order;
-    std::vector<std::vector<const ace355_lora_term*>> by;
-    std::vector<std::vector<const ace355_kron_term*>> kby;
-    std::vector<const ace355_dora_term*> dby;   // at most one DoRA term per target
-    std::vector<PackDest> dests;
-    auto index_of = [&](const std::string& n) { for (size_t i = 0; i < order.size(); ++i) if (order[i] == n) return (int)i; return -1; };
-    auto not_a_target = [&](const char* name) {
-        set_error(std::string("set_adapters: '") + name + "' is not a LoRA target (layers.{i}.{self_attn,cross_attn}.{q,k,v,o}_proj.weight, "
-                  "layers.{i}.mlp.{gate,up,down}_proj.weight)");
-        return ACE355_ERR_INVALID;
-    };
-    std::set<std::string> lora_named, add_named, dora_named;
-    for (int i = 0; i < n_terms; ++i) {
-        const ace355_lora_term& t = terms[i];
-        ACE_CHECK(t.name && t.A_dev && t.B_dev, "set_adapters: null name / A / B");
-        PackDest d;
-        if (!lora_target(h, t.name, &d)) return not_a_target(t.name);
-        ACE_CHECK(t.rank >= 1 && std::isfinite(t.scale), "set_adapters: rank must be >= 1 and scale finite");
-        if (n_kron) lora_named.insert(t.name);
-        if (n_dora) add_named.insert(t.name);
-        if (t.scale == 0.f) continue;
-        int k = index_of(t.name);
-        if (k < 0) { order.push_back(t.name); by.emplace_back(); kby.emplace_back(); dby.push_back(nullptr); dests.push_back(d); k = (int)order.size() - 1; }
-        by[k].push_back(&t);
-    }
-    for (int i = 0; i < n_kron; ++i) {
-        const ace355_kron_term& t = kron[i];
-        ACE_CHECK(t.name, "set_adapters: null name in a Kronecker term");
-        PackDest d;
-        if (!lora_target(h, t.name, &d)) return not_a_target(t.name);
-        // exactly one of {w} / {w_a, w_b} per factor; r = 0 for a full factor, >= 1 for a decomposed one
-        const bool f1 = t.w1_dev && !t.w1a_dev && !t.w1b_dev && t.r1 == 0, d1 = !t.w1_dev && t.w1a_dev && t.w1b_dev && t.r1 >= 1;
-        const bool f2 = t.w2_dev && !t.w2a_dev && !t.w2b_dev && t.r2 == 0, d2 = !t.w2_dev && t.w2a_dev && t.w2b_dev && t.r2 >= 1;
-        ACE_CHECK(t.r1 >= 0 && t.r2 >= 0, "set_adapters: a Kronecker factor's rank must be >= 0");
-        ACE_CHECK((f1 || d1) && (f2 || d2), "set_adapters: each Kronecker factor needs exactly one of {w} (rank 0) / {w_a, w_b} (rank >= 1)");
-        ACE_CHECK(t.out_l >= 1 && t.out_k >= 1 && t.in_m >= 1 && t.in_n >= 1 && (long)t.out_l * t.out_k == d.rows &&
-                  (long)t.in_m * t.in_n == d.cols, "set_adapters: out_l x out_k / in_m x in_n do not give the target's [out, in]");
-        ACE_CHECK(std::isfinite(t.scale), "set_adapters: scale must be finite");
-        ACE_CHECK(lokr_lds_floats(t.out_k, t.in_n) <= LOKR_LDS_FLOATS, "set_adapters: Kronecker split exceeds the merge tile's LDS");
-        if (lora_named.count(t.name)) {   // the reference never has both (H/lora/lifecycle.py:244-246)
-            set_error(std::string("set_adapters: '") + t.name + "' is named by a LoRA term and by a Kronecker term");
-            return ACE355_ERR_INVALID;
-        }
-        if (n_dora) add_named.insert(t.name);
-        if (t.scale == 0.f) continue;
-        int k = index_of(t.name);
-        if (k < 0) { order.push_back(t.name); by.emplace_back(); kby.emplace_back(); dby.push_back(nullptr); dests.push_back(d); k = (int)order.size() - 1; }
-        kby[k].push_back(&t);
-    }
-    for (int i = 0; i < n_dora; ++i) {
-        const ace355_dora_term& t = dora[i];
-        ACE_CHECK(t.name && t.g_dev, "set_adapters: null name / g in a DoRA term");
-        PackDest d;
-        if (!lora_target(h, t.name, &d)) return not_a_target(t.name);
-        ACE_CHECK(t.per_input == 0 || t.per_input == 1, "set_adapters: a DoRA term's per_input must be 0 or 1");
-        ACE_CHECK(std::isfinite(t.eps) && t.eps >= 0.f && std::isfinite(t.multiplier),
-                  "set_adapters: a DoRA term's eps must be finite and >= 0 and its multiplier finite");
-        if (!dora_named.insert(t.name).second) {
-            set_error(std::string("set_adapters: two DoRA terms name '") + t.name + "'");
-            return ACE355_ERR_INVALID;
-        }
-        if (t.multiplier == 0.f) continue;   // f = 1
-        if (!add_named.count(t.name)) {
-            set_error(std::string("set_adapters: the DoRA term on '") + t.name + "' has no LoRA / Kronecker term beside it in this call");
-            return ACE355_ERR_INVALID;
-        }
-        int k = index_of(t.name);   // (every additive term of the target at scale 0: V = W0, still rescaled)
-        if (k < 0) { order.push_back(t.name); by.emplace_back(); kby.emplace_back(); dby.push_back(nullptr); dests.push_back(d); k = (int)order.size() - 1; }
-        dby[k] = &t;
-    }
-    const size_t n_merge = order.size();
-    for (const std::string& n : h->lora.applied) {   // merged before, no term now: its rows go back to the base
-        if (index_of(n) >= 0) continue;
-        PackDest d;
-        lora_target(h, n, &d);
-        order.push_back(n); by.emplace_back(); kby.emplace_back(); dby.push_back(nullptr); dests.push_back(d);
-    }
-    if (order.empty()) return ACE355_OK;
+    std::vector<AdapterRef> lref, kref, dref, applied;
+    for (int i = 0; i < n_terms; ++i) lref.push_back(adapter_ref_of(h->cfg, terms[i].name));
+    for (int i = 0; i < n_kron; ++i) kref.push_back(adapter_ref_of(h->cfg, kron[i].name));
+    for (int i = 0; i < n_dora; ++i) dref.push_back(adapter_ref_of(h->cfg, dora[i].name));
+    for (const std::string& n : h->lora.applied) applied.push_back(adapter_ref_of(h->cfg, n.c_str()));
+    call.lora_ref = lref.data(); call.kron_ref = kref.data(); call.dora_ref = dref.data();
+    call.applied = applied.data(); call.n_applied = (int)applied.size();
+    AdapterPlan plan = plan_adapters(call);
+    if (plan.code) { set_error(plan.error); return plan.code; }
+    if (plan.targets.empty()) return ACE355_OK;
     ACE_HIP(hipStreamSynchronize(s));   // (the previous call's merge may still read the tables)
-    auto pristine_of = [&](const void* buf) -> bf16_t* {
-        for (auto& pr : h->lora.pristine) if (pr.first == buf) return pr.second;
-        return nullptr;
-    };
-    for (const PackDest& d : dests) {   // first touch of a packed buffer: its base copy
-        if (pristine_of(d.dst)) continue;
-        const size_t n = packed_elems(h, d.dst);
-        void* q = nullptr;
-        ACE_HIP(hipMalloc(&q, n * sizeof(bf16_t)));
-        h->lora.pristine.push_back({(bf16_t*)d.dst, (bf16_t*)q});
-        ACE_HIP(hipMemcpyAsync(q, d.dst, n * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
-    }
-    // the scratch table of the decomposed Kronecker factors' fp32 products
-    size_t scratch_floats = 0;
-    bool any_kron = false;
-    for (size_t i = 0; i < n_merge; ++i)
-        for (const ace355_kron_term* t : kby[i]) {
-            any_kron = true;
-            if (t->r1) scratch_floats += ((size_t)t->out_l * t->in_m + 3) / 4 * 4;
-            if (t->r2) scratch_floats += ((size_t)t->out_k * t->in_n + 3) / 4 * 4;
+    std::vector<AdapterWhere> where;
+    for (const AdapterTarget& t : plan.targets) {
+        PackDest d;
+        lora_target(h, t.name, &d);
+        bf16_t* base = nullptr;
+        for (auto& pr : h->lora.pristine) if (pr.first == d.dst) base = pr.second;
+        if (!base) {   // first touch of a packed buffer: its base copy
+            const size_t n = packed_elems(h, d.dst);
+            ACE_HIP(hipMalloc((void**)&base, n * sizeof(bf16_t)));
+            h->lora.pristine.push_back({(bf16_t*)d.dst, base});
+            ACE_HIP(hipMemcpyAsync(base, d.dst, n * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
         }
-    if (scratch_floats > h->lora.kscratch_floats) {
-        if (h->lora.kscratch) hipFree(h->lora.kscratch);
-        h->lora.kscratch = nullptr; h->lora.kscratch_floats = 0;
-        ACE_HIP(hipMalloc((void**)&h->lora.kscratch, scratch_floats * sizeof(float)));
-        h->lora.kscratch_floats = scratch_floats;
+        where.push_back(AdapterWhere{(bf16_t*)d.dst, base, d.dst_ld, d.dst_row0, d.mode, d.p0});
     }
-    // the scratch of the DoRA targets: per target its fp64 partials, then its fp32 factors
-    auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
-    size_t dscratch_bytes = 0;
-    bool any_dora = false;
-    for (size_t i = 0; i < n_merge; ++i) {
-        if (!dby[i]) continue;
-        any_dora = true;
-        const PackDest& d = dests[i];
-        const size_t n = dby[i]->per_input ? d.cols : d.rows;
-        const size_t nt = dby[i]->per_input ? (d.rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS : (d.cols + LORA_TILE_COLS - 1) / LORA_TILE_COLS;
-        dscratch_bytes += up16(n * nt * sizeof(double)) + up16(n * sizeof(float));
-    }
-    if (dscratch_bytes > h->lora.dscratch_bytes) {
-        if (h->lora.dscratch) hipFree(h->lora.dscratch);
-        h->lora.dscratch = nullptr; h->lora.dscratch_bytes = 0;
-        ACE_HIP(hipMalloc(&h->lora.dscratch, dscratch_bytes));
-        h->lora.dscratch_bytes = dscratch_bytes;
-    }
-    // LoRA targets (and, in a call without Kronecker terms, the restored ones) go to the LoRA launch, Kronecker targets (and, beside
-    // them, the restored ones) to the LoKr launch
-    std::vector<LoraTargetDev> tg, ktg, dtg, dktg;   // d*: the targets with a DoRA term, by the kernel that forms their V
-    std::vector<DoraDev> ddv, dkdv;
-    int dtiles = 0, dktiles = 0, dmax_n = 0;
-    size_t dscratch_at = 0;
-    std::vector<LoraTermDev> tm;
-    std::vector<KronTermDev> ktm;
-    std::vector<KronFactorDev> jobs;
-    int tiles = 0, ktiles = 0, jtiles = 0, klds = 4;
-    size_t scratch_at = 0;
-    bool kv = false, o = false;
-    auto factor = [&](const void* a, const void* b, int rows, int cols, int rank) -> const void* {
-        KronFactorDev f{};
-        f.a = (const bf16_t*)a; f.b = (const bf16_t*)b; f.dst = h->lora.kscratch + scratch_at;
-        f.rows = rows; f.cols = cols; f.rank = rank;
-        f.tiles_n = (cols + 127) / 128; f.tile0 = jtiles;
-        jtiles += (rows + 63) / 64 * f.tiles_n;
-        scratch_at += ((size_t)rows * cols + 3) / 4 * 4;
-        jobs.push_back(f);
-        return f.dst;
-    };
-    for (size_t i = 0; i < order.size(); ++i) {
-        const PackDest& d = dests[i];
-        ACE_CHECK(d.cols % 8 == 0, "set_adapters: target columns must be a multiple of 8");
-        const bool to_kron = !kby[i].empty() || (by[i].empty() && any_kron);
-        LoraTargetDev x{};
-        x.dst = (bf16_t*)d.dst; x.src = pristine_of(d.dst); x.ld = d.dst_ld; x.row0 = d.dst_row0; x.mode = d.mode; x.p0 = d.p0;
-        x.rows = (int)d.rows; x.cols = (int)d.cols;
-        static_assert(LORA_TILE_ROWS == LOKR_TILE_ROWS && LORA_TILE_COLS == LOKR_TILE_COLS, "dora.h: one tile shape for both merge kernels");
-        const bool dk = dby[i] && to_kron;   // a DoRA target goes to launches of its own
-        if (dby[i]) {
-            const ace355_dora_term* t = dby[i];
-            DoraDev v{};
-            v.per_input = t->per_input; v.eps = t->eps; v.m = t->multiplier; v.g = t->g_dev;
-            v.n = t->per_input ? x.cols : x.rows;
-            v.ntiles = t->per_input ? (x.rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS : (x.cols + LORA_TILE_COLS - 1) / LORA_TILE_COLS;
-            v.part = (double*)((char*)h->lora.dscratch + dscratch_at);
-            dscratch_at += up16((size_t)v.n * v.ntiles * sizeof(double));
-            v.f = (float*)((char*)h->lora.dscratch + dscratch_at);
-            dscratch_at += up16((size_t)v.n * sizeof(float));
-            dmax_n = std::max(dmax_n, v.n);
-            (dk ? dkdv : ddv).push_back(v);
+    if (int rc = grow((void**)&h->lora.kscratch, &h->lora.kscratch_floats, plan.kscratch_floats, sizeof(float))) return rc;
+    if (int rc = grow(&h->lora.dscratch, &h->lora.dscratch_bytes, plan.dscratch_bytes, 1)) return rc;
+    if (int rc = grow(&h->lora.tab, &h->lora.tab_bytes, plan.table.size(), 1)) return rc;
+    adapter_table_patch(plan, where.data(), (uintptr_t)h->lora.kscratch, (uintptr_t)h->lora.dscratch);
+    ACE_HIP(hipMemcpyAsync(h->lora.tab, plan.table.data(), plan.table.size(), hipMemcpyHostToDevice, s));
+    int rc = 0;
+    for (const AdapterLaunch& l : plan.launches) {
+        auto sec = [&](int i) -> const void* { return l.sec[i] < 0 ? nullptr : (const char*)h->lora.tab + plan.at[l.sec[i]]; };
+        const LoraTargetDev* tg = (const LoraTargetDev*)sec(0);
+        const DoraDev* dv = (const DoraDev*)sec(2);
+        switch (l.kernel) {
+        case ADAPTER_KERNEL_LORA_MERGE: rc = launch_lora_merge(tg, l.n, l.grid_x, (const LoraTermDev*)sec(1), s, dv, l.pass); break;
+        case ADAPTER_KERNEL_KRON_FACTORS: rc = launch_lokr_factors((const KronFactorDev*)sec(0), l.n, l.grid_x, s); break;
+        case ADAPTER_KERNEL_KRON_MERGE:
+            rc = launch_lokr_merge(tg, l.n, l.grid_x, (const KronTermDev*)sec(1), l.lds_bytes / (int)sizeof(float), s, dv, l.pass);
+            break;
+        default: rc = launch_dora_factors((const DoraDev*)sec(0), l.n, l.grid_x, s); break;
         }
-        if (to_kron) {
-            int& at = dk ? dktiles : ktiles;
-            x.tiles_n = (x.cols + LOKR_TILE_COLS - 1) / LOKR_TILE_COLS;
-            x.tile0 = at;
-            at += (x.rows + LOKR_TILE_ROWS - 1) / LOKR_TILE_ROWS * x.tiles_n;
-            x.term0 = (int)ktm.size();
-            for (const ace355_kron_term* t : kby[i]) {
-                KronTermDev u{};
-                u.w1 = t->r1 ? factor(t->w1a_dev, t->w1b_dev, t->out_l, t->in_m, t->r1) : t->w1_dev; u.w1_f32 = t->r1 ? 1 : 0;
-                u.w2 = t->r2 ? factor(t->w2a_dev, t->w2b_dev, t->out_k, t->in_n, t->r2) : t->w2_dev; u.w2_f32 = t->r2 ? 1 : 0;
-                u.out_l = t->out_l; u.out_k = t->out_k; u.in_m = t->in_m; u.in_n = t->in_n; u.scale = t->scale;
-                u.wide = t->in_n % 8 == 0 && t->in_n <= LOKR_TILE_COLS && (u.w2_f32 || (uintptr_t)u.w2 % 16 == 0);
-                klds = std::max(klds, lokr_lds_floats(t->out_k, t->in_n));
-                ktm.push_back(u);
-            }
-            x.nterms = (int)ktm.size() - x.term0;
-            (dk ? dktg : ktg).push_back(x);
-        } else {
-            int& at = dby[i] ? dtiles : tiles;
-            x.tiles_n = (x.cols + LORA_TILE_COLS - 1) / LORA_TILE_COLS;
-            x.tile0 = at;
-            at += (x.rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS * x.tiles_n;
-            x.term0 = (int)tm.size();
-            for (const ace355_lora_term* t : by[i]) tm.push_back(LoraTermDev{(const bf16_t*)t->A_dev, (const bf16_t*)t->B_dev, t->rank, t->scale});
-            x.nterms = (int)tm.size() - x.term0;
-            (dby[i] ? dtg : tg).push_back(x);
-        }
-        const std::string& n = order[i];
-        kv = kv || n.find(".cross_attn.k_proj.") != std::string::npos || n.find(".cross_attn.v_proj.") != std::string::npos;
-        o = o || n.find(".cross_attn.o_proj.") != std::string::npos;
-    }
-    auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t tg_bytes = pad(tg.size() * sizeof(LoraTargetDev)), tm_bytes = std::max<size_t>(tm.size(), 1) * sizeof(LoraTermDev);
-    const size_t ktg_at = any_kron ? pad(tg_bytes + tm_bytes) : tg_bytes + tm_bytes, ktm_at = ktg_at + pad(ktg.size() * sizeof(LoraTargetDev));
-    const size_t job_at = ktm_at + pad(ktm.size() * sizeof(KronTermDev));
-    const size_t bytes0 = any_kron ? job_at + std::max<size_t>(jobs.size(), 1) * sizeof(KronFactorDev) : tg_bytes + tm_bytes;
-    // DoRA tables behind those of the plain merges: LoRA-formed targets and their DoraDev, Kronecker-formed targets and theirs
-    const size_t dtg_at = pad(bytes0), ddv_at = dtg_at + pad(dtg.size() * sizeof(LoraTargetDev));
-    const size_t dktg_at = ddv_at + pad(ddv.size() * sizeof(DoraDev)), dkdv_at = dktg_at + pad(dktg.size() * sizeof(LoraTargetDev));
-    const size_t bytes = any_dora ? dkdv_at + std::max<size_t>(dkdv.size(), 1) * sizeof(DoraDev) : bytes0;
-    if (bytes > h->lora.tab_bytes) {
-        if (h->lora.tab) hipFree(h->lora.tab);
-        h->lora.tab = nullptr; h->lora.tab_bytes = 0;
-        ACE_HIP(hipMalloc(&h->lora.tab, bytes));
-        h->lora.tab_bytes = bytes;
-    }
-    std::vector<char> host(bytes, 0);
-    if (!tg.empty()) memcpy(host.data(), tg.data(), tg.size() * sizeof(LoraTargetDev));
-    if (!tm.empty()) memcpy(host.data() + tg_bytes, tm.data(), tm.size() * sizeof(LoraTermDev));
-    if (!ktg.empty()) memcpy(host.data() + ktg_at, ktg.data(), ktg.size() * sizeof(LoraTargetDev));
-    if (!ktm.empty()) memcpy(host.data() + ktm_at, ktm.data(), ktm.size() * sizeof(KronTermDev));
-    if (!jobs.empty()) memcpy(host.data() + job_at, jobs.data(), jobs.size() * sizeof(KronFactorDev));
-    if (!dtg.empty()) memcpy(host.data() + dtg_at, dtg.data(), dtg.size() * sizeof(LoraTargetDev));
-    if (!ddv.empty()) memcpy(host.data() + ddv_at, ddv.data(), ddv.size() * sizeof(DoraDev));
-    if (!dktg.empty()) memcpy(host.data() + dktg_at, dktg.data(), dktg.size() * sizeof(LoraTargetDev));
-    if (!dkdv.empty()) memcpy(host.data() + dkdv_at, dkdv.data(), dkdv.size() * sizeof(DoraDev));
-    ACE_HIP(hipMemcpyAsync(h->lora.tab, host.data(), bytes, hipMemcpyHostToDevice, s));
-    char* tab = (char*)h->lora.tab;
-    int rc = launch_lora_merge((const LoraTargetDev*)tab, (int)tg.size(), tiles, (const LoraTermDev*)(tab + tg_bytes), s);
-    if (!rc && any_kron) {
-        rc = launch_lokr_factors((const KronFactorDev*)(tab + job_at), (int)jobs.size(), jtiles, s);
-        if (!rc) rc = launch_lokr_merge((const LoraTargetDev*)(tab + ktg_at), (int)ktg.size(), ktiles, (const KronTermDev*)(tab + ktm_at), klds, s);
-    }
-    if (!rc && any_dora) {   // pass 1 of both kernels, the factors, pass 2 of both: in order on the one stream
-        const LoraTargetDev *a = (const LoraTargetDev*)(tab + dtg_at), *b = (const LoraTargetDev*)(tab + dktg_at);
-        const DoraDev *av = (const DoraDev*)(tab + ddv_at), *bv = (const DoraDev*)(tab + dkdv_at);
-        const LoraTermDev* tmd = (const LoraTermDev*)(tab + tg_bytes);
-        const KronTermDev* ktmd = (const KronTermDev*)(tab + ktm_at);
-        rc = launch_lora_merge(a, (int)dtg.size(), dtiles, tmd, s, av, 1);
-        if (!rc) rc = launch_lokr_merge(b, (int)dktg.size(), dktiles, ktmd, klds, s, bv, 1);
-        if (!rc) rc = launch_dora_factors(av, (int)ddv.size(), dmax_n, s);
-        if (!rc) rc = launch_dora_factors(bv, (int)dkdv.size(), dmax_n, s);
-        if (!rc) rc = launch_lora_merge(a, (int)dtg.size(), dtiles, tmd, s, av, 2);
-        if (!rc) rc = launch_lokr_merge(b, (int)dktg.size(), dktiles, ktmd, klds, s, bv, 2);
+        if (rc) break;
     }
     ACE_HIP(hipStreamSynchronize(s));   // (pageable source of the table copy; a merge is rare next to the requests it serves)
     if (rc) return rc;
-    if (kv) h->lora.gen_kv++;   // condition slots built from the old cross k / v (or, broadcast, o) weights are stale now
-    if (o) h->lora.gen_o++;
-    h->lora.applied = std::set<std::string>(order.begin(), order.begin() + n_merge);
+    if (plan.stale_kv) h->lora.gen_kv++;   // condition slots built from the old cross k / v (or, broadcast, o) weights are stale now
+    if (plan.stale_o) h->lora.gen_o++;
+    h->lora.applied.clear();
+    for (int i = 0; i < plan.n_merged; ++i) h->lora.applied.insert(plan.targets[i].name);
     h->nf.key.clear();   // the folded-norm bias tables are products with the q / k / v and gate / up weights
     if (h->dual.ctx) h->dual.ctx->nf.key.clear();
     if (h->lora.applied.empty()) lora_free_pristine(h);   // the base is back everywhere (the stream was synchronised above)

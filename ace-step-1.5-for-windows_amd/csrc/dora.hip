@@ -24,9 +24,9 @@ __global__ __launch_bounds__(256) void dora_factor_kernel(const DoraDev* __restr
 
 }  // namespace
 
-int launch_dora_factors(const DoraDev* dora_dev, int n_targets, int max_n, hipStream_t s) {
-    if (n_targets <= 0 || max_n <= 0) return 0;
-    hipLaunchKernelGGL(dora_factor_kernel, dim3((max_n + 255) / 256, n_targets), dim3(256), 0, s, dora_dev);
+int launch_dora_factors(const DoraDev* dora_dev, int n_targets, int chunks, hipStream_t s) {
+    if (n_targets <= 0 || chunks <= 0) return 0;
+    hipLaunchKernelGGL(dora_factor_kernel, dim3(chunks, n_targets), dim3(256), 0, s, dora_dev);
     ACE_LAUNCH_CHECK();
     return 0;
 }

@@ -13,7 +13,7 @@ namespace {
 
 constexpr int TM = LOKR_TILE_ROWS;   // source rows of a tile
 constexpr int TN = LOKR_TILE_COLS;   // columns of a tile
-constexpr int FM = 64, FN = 128;     // factor pre-pass tile
+constexpr int FM = LOKR_FACTOR_ROWS, FN = LOKR_FACTOR_COLS;   // factor pre-pass tile
 constexpr int KC = 32;               // rank step = the K of one v_mfma_f32_16x16x32_bf16
 constexpr int KP = KC + 8;           // LDS row pitch of the staged operands (80 bytes: 16-byte fragment reads stay aligned)
 
@@ -203,12 +203,6 @@ __global__ __launch_bounds__(256) void lokr_merge_kernel(const LoraTargetDev* __
 }
 
 }  // namespace
-
-int lokr_lds_floats(int out_k, int in_n) {
-    const int a = out_k < TM ? out_k : TM, b = in_n < TN ? in_n : TN;
-    const int nl = TM % a == 0 && out_k <= TM ? TM / a : (TM - 1) / a + 2, nm = TN % b == 0 && in_n <= TN ? TN / b : (TN - 1) / b + 2;
-    return ((nl * nm + 3) & ~3) + a * lokr_w2_pitch(b);
-}
 
 int launch_lokr_factors(const KronFactorDev* jobs_dev, int n_jobs, int total_tiles, hipStream_t s) {
     if (n_jobs <= 0 || total_tiles <= 0) return 0;

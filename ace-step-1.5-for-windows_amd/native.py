@@ -129,6 +129,50 @@ class DoraTermC(C.Structure):
     _fields_ = [("name", C.c_char_p), ("g_dev", C.c_void_p), ("per_input", C.c_int32), ("eps", C.c_float), ("multiplier", C.c_float)]
 
 
+ADAPTER_CLASSES = ("lora", "kron", "dora_lora", "dora_kron")                    # ACE355_ADAPTER_CLASS_*
+ADAPTER_KERNELS = ("lora_merge", "kron_factors", "kron_merge", "dora_factors")  # ACE355_ADAPTER_KERNEL_*
+ADAPTER_SECTIONS = ("lora_targets", "lora_terms", "kron_targets", "kron_terms", "kron_factors", "dora_lora_targets", "dora_lora_rows",
+                    "dora_kron_targets", "dora_kron_rows")
+
+
+class AdapterTargetInfoC(C.Structure):
+    _fields_ = [("name", C.c_char_p)] + [(n, C.c_int32) for n in (
+        "cls", "row", "rows", "cols", "tile0", "tiles_n", "term0", "nterms", "restored")]
+
+
+class AdapterLaunchInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "pass", "entries", "grid_x", "grid_y", "lds_bytes")] + [("sections", C.c_int32 * 3)]
+
+
+class AdapterKronInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("out_l", "out_k", "in_m", "in_n", "wide", "w1_f32", "w2_f32")] + [
+        ("scale", C.c_float), ("w1_offset", C.c_int64), ("w2_offset", C.c_int64)]
+
+
+class AdapterFactorInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("rows", "cols", "rank", "tile0", "tiles_n", "reserved")] + [("offset", C.c_int64)]
+
+
+class AdapterDoraInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("cls", "per_input", "n", "ntiles")] + [
+        ("eps", C.c_float), ("multiplier", C.c_float), ("part_offset", C.c_int64), ("f_offset", C.c_int64)]
+
+
+class AdapterPlanRowsC(C.Structure):
+    _fields_ = [("targets", C.POINTER(AdapterTargetInfoC)), ("cap_targets", C.c_int32),
+                ("launches", C.POINTER(AdapterLaunchInfoC)), ("cap_launches", C.c_int32),
+                ("kron", C.POINTER(AdapterKronInfoC)), ("cap_kron", C.c_int32),
+                ("factors", C.POINTER(AdapterFactorInfoC)), ("cap_factors", C.c_int32),
+                ("dora", C.POINTER(AdapterDoraInfoC)), ("cap_dora", C.c_int32)]
+
+
+class AdapterPlanInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_targets", "n_merged", "n_launches", "n_lora_terms", "n_kron_terms", "n_factors", "n_dora",
+                                         "stale_kv", "stale_o", "reserved")] + [
+        ("table_bytes", C.c_int64), ("kscratch_floats", C.c_int64), ("dscratch_bytes", C.c_int64),
+        ("section_at", C.c_int64 * len(ADAPTER_SECTIONS)), ("section_bytes", C.c_int64 * len(ADAPTER_SECTIONS))]
+
+
 # name -> (restype, argtypes); every symbol include/ace355.h declares
 SIGNATURES = {
     "ace355_last_error": (C.c_char_p, []),
@@ -158,6 +202,9 @@ SIGNATURES = {
     "ace355_gemm_set_k_rotation": (C.c_int, [C.c_int]),
     "ace355_gemm_plan": (C.c_int, [C.POINTER(GemmRequestC), C.POINTER(GemmPlanInfoC)]),
     "ace355_attn_plan": (C.c_int, [C.POINTER(AttnRequestC), C.POINTER(AttnPlanInfoC)]),
+    "ace355_adapter_plan": (C.c_int, [C.POINTER(DitConfigC), C.POINTER(LoraTermC), C.c_int, C.POINTER(KronTermC), C.c_int,
+                                      C.POINTER(DoraTermC), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(AdapterPlanRowsC),
+                                      C.POINTER(AdapterPlanInfoC)]),
     "ace355_dit_set_dual": (C.c_int, [C.c_void_p, C.c_int]),
     "ace355_dit_dual_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ace355_dit_set_dedup": (C.c_int, [C.c_void_p, C.c_int]),
@@ -316,6 +363,46 @@ def attn_plan(N: int, Sq: int, Skv: int, Hq: int, Hkv: int, window: int = -1, **
     out = AttnPlanInfoC()
     check(lib().ace355_attn_plan(C.byref(rq), C.byref(out)), "attn_plan")
     return {**{n: int(getattr(out, n)) for n, _t in AttnPlanInfoC._fields_}, "kernel": ATTN_KERNELS[out.kernel]}
+
+
+def _rows(arr, n):
+    out = []
+    for i in range(n):
+        r = {}
+        for f, _t in arr[i]._fields_:
+            v = getattr(arr[i], f)
+            r[f] = v.decode() if isinstance(v, bytes) else list(v) if hasattr(v, "_length_") else v
+        r.pop("reserved", None)
+        out.append(r)
+    return out
+
+
+def adapter_plan(cfg: DitConfigC, lora=(), kron=(), dora=(), applied=()) -> dict:
+    """`ace355_adapter_plan` (include/ace355.h): what a set_adapters call with these terms comes to on a decoder of configuration ``cfg``
+    whose targets ``applied`` hold a merge now - targets, Kronecker term rows, factor jobs, DoRA rows, launches, table sections and
+    scratch sizes, as dicts with classes, kernels and sections by name.  ``lora`` / ``kron`` / ``dora`` are tuples of the fields of
+    LoraTermC / KronTermC / DoraTermC (names as bytes; device pointers are any numbers, only tested).  No GPU, no handle."""
+    la = (LoraTermC * max(len(lora), 1))(*[LoraTermC(*r) for r in lora])
+    ka = (KronTermC * max(len(kron), 1))(*[KronTermC(*r) for r in kron])
+    da = (DoraTermC * max(len(dora), 1))(*[DoraTermC(*r) for r in dora])
+    names = (C.c_char_p * max(len(applied), 1))(*[n.encode() if isinstance(n, str) else n for n in applied])
+    nt, nk = len(lora) + len(kron) + len(dora) + len(applied) + 1, len(kron) + 1
+    tg, ln, kr, fa, dr = (AdapterTargetInfoC * nt)(), (AdapterLaunchInfoC * 9)(), (AdapterKronInfoC * nk)(), (AdapterFactorInfoC * (2 * nk))(), \
+        (AdapterDoraInfoC * (len(dora) + 1))()
+    rows = AdapterPlanRowsC(tg, nt, ln, 9, kr, nk, fa, 2 * nk, dr, len(dora) + 1)
+    info = AdapterPlanInfoC()
+    check(lib().ace355_adapter_plan(C.byref(cfg), la, len(lora), ka, len(kron), da, len(dora), names, len(applied), C.byref(rows),
+                                    C.byref(info)), "adapter_plan")
+    assert info.n_targets <= nt and info.n_launches <= 9 and info.n_kron_terms <= nk and info.n_factors <= 2 * nk and info.n_dora <= len(dora) + 1
+    out = {n: int(getattr(info, n)) for n, _t in AdapterPlanInfoC._fields_[:13] if n != "reserved"}
+    out["sections"] = {s: (int(info.section_at[i]), int(info.section_bytes[i])) for i, s in enumerate(ADAPTER_SECTIONS)}
+    out["targets"] = [{**r, "cls": ADAPTER_CLASSES[r["cls"]]} for r in _rows(tg, info.n_targets)]
+    out["launches"] = [{**r, "kernel": ADAPTER_KERNELS[r["kernel"]], "sections": [ADAPTER_SECTIONS[s] if s >= 0 else None for s in r["sections"]]}
+                       for r in _rows(ln, info.n_launches)]
+    out["kron"] = _rows(kr, info.n_kron_terms)
+    out["factors"] = _rows(fa, info.n_factors)
+    out["dora"] = [{**r, "cls": ADAPTER_CLASSES[r["cls"]]} for r in _rows(dr, info.n_dora)]
+    return out
 
 
 def current_stream_ptr() -> int:

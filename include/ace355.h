@@ -294,7 +294,8 @@ typedef struct ace355_lora_term {
  * quantised models, H/lora/lifecycle.py:173-178): ERR_STATE otherwise.  An unknown name, rank < 1 or a null pointer: ERR_INVALID.
  * While adapters are applied, ace355_dit_set_precision to another precision and ace355_dit_load_tensor return ERR_STATE.  A call
  * that rewrites a cross-attention k / v (or o, for broadcast slots) projection makes the condition slots built before it stale:
- * a forward / sample reading one returns ERR_STATE until ace355_dit_set_condition rebuilds it. */
+ * a forward / sample reading one returns ERR_STATE until ace355_dit_set_condition rebuilds it.
+ * Which launches a call makes: ace355_adapter_plan. */
 int ace355_dit_set_adapters(ace355_dit* h, const ace355_lora_term* terms, int n_terms, void* stream);
 /* LoKr adapters (LyCORIS LokrModule semantics, restated from its published source: the weight delta of a module is
  * scale x multiplier x kron(W1, W2), each factor held in full or as a low-rank product w_a @ w_b).  The reference loads a LoKr
@@ -317,7 +318,8 @@ typedef struct ace355_kron_term {
  * sum over a target's terms (call order) are fp32, one rounding.  n_kron 0 IS ace355_dit_set_adapters (the same launches, the same
  * bits).  Several Kronecker terms may name one target; scale 0 drops a term.  ERR_INVALID: a target named by both a LoRA and a
  * Kronecker term (the reference never has both, lifecycle.py:244-246), out_l out_k != out or in_m in_n != in, a missing or doubled
- * factor pointer (a full factor has rank 0, a decomposed one rank >= 1), a rank below 0, a non-finite scale, an unknown name. */
+ * factor pointer (a full factor has rank 0, a decomposed one rank >= 1), a rank below 0, a non-finite scale, an unknown name.
+ * Which launches a call makes: ace355_adapter_plan. */
 int ace355_dit_set_adapters_mixed(ace355_dit* h, const ace355_lora_term* lora, int n_lora, const ace355_kron_term* kron, int n_kron,
                                   void* stream);
 /* DoRA (weight decomposition) on top of the additive terms of one target: LyCORIS LokrModule with `wd` (forward, not bypass:
@@ -349,9 +351,72 @@ typedef struct ace355_dora_term {
  * ace355_dit_set_adapters_mixed.  n_dora 0 IS ace355_dit_set_adapters_mixed (the same launches, the same bits).  g_dev may be released
  * when the call returns.  ERR_INVALID, nothing changed: two DoRA terms on one target, a DoRA term with multiplier != 0 on a target
  * that no LoRA / Kronecker term of the call names, a null g_dev, per_input outside {0, 1}, a non-finite or negative eps, a non-finite
- * multiplier, an unknown name, and everything ace355_dit_set_adapters_mixed refuses. */
+ * multiplier, an unknown name, and everything ace355_dit_set_adapters_mixed refuses.  Which launches a call makes: ace355_adapter_plan. */
 int ace355_dit_set_adapters_dora(ace355_dit* h, const ace355_lora_term* lora, int n_lora, const ace355_kron_term* kron, int n_kron,
                                  const ace355_dora_term* dora, int n_dora, void* stream);
+/* Which targets, tables, scratch regions and launches a set_adapters call comes to (no reference counterpart; a test and review aid, as
+ * ace355_gemm_plan): the three entry points above do exactly what one pure function of the call says (csrc/adapter_plan.h
+ * plan_adapters), and this evaluates it for a decoder of configuration `cfg` whose targets `applied` (n_applied names) hold a merge now.
+ * No GPU is touched and no handle is needed; the device pointers of the terms are only tested (null, and w2 for 16-byte alignment) and
+ * may be any numbers.  Refusals are those of the entry points, code and message; a name among `applied` that is no target is
+ * ERR_INVALID.  Every array of `rows` is caller-sized: up to its cap rows are written, `info` holds the full counts. */
+#define ACE355_ADAPTER_CLASS_LORA 0       /* plain, formed by the LoRA merge kernel (and, in a call without a live Kronecker term, restored) */
+#define ACE355_ADAPTER_CLASS_KRON 1       /* plain, formed by the Kronecker merge kernel (and, beside a live Kronecker term, restored) */
+#define ACE355_ADAPTER_CLASS_DORA_LORA 2  /* DoRA, V formed by the LoRA merge kernel */
+#define ACE355_ADAPTER_CLASS_DORA_KRON 3  /* DoRA, V formed by the Kronecker merge kernel */
+#define ACE355_ADAPTER_KERNEL_LORA_MERGE 0
+#define ACE355_ADAPTER_KERNEL_KRON_FACTORS 1
+#define ACE355_ADAPTER_KERNEL_KRON_MERGE 2
+#define ACE355_ADAPTER_KERNEL_DORA_FACTORS 3
+#define ACE355_ADAPTER_SECTIONS 9 /* of the device table: LoRA targets, LoRA terms, Kronecker targets, Kronecker terms, factor jobs, DoRA-LoRA
+                                   * targets, their DoRA rows, DoRA-Kronecker targets, their DoRA rows */
+typedef struct ace355_adapter_target_info {
+    const char* name;            /* the caller's string */
+    int32_t cls;                 /* ACE355_ADAPTER_CLASS_*: which launches it rides */
+    int32_t row;                 /* its row in its class's target section; in a DoRA class also its row among the class's DoRA rows */
+    int32_t rows, cols;
+    int32_t tile0, tiles_n;      /* first tile in its class's launches, column tiles per row tile */
+    int32_t term0, nterms;       /* its rows of the LoRA resp. Kronecker term section */
+    int32_t restored;            /* 1: no term now, its rows go back to the base */
+} ace355_adapter_target_info;
+typedef struct ace355_adapter_launch_info {
+    int32_t kernel, pass;        /* ACE355_ADAPTER_KERNEL_*; pass 0 plain, 1 / 2 the DoRA passes of a merge kernel */
+    int32_t entries;             /* rows of its first section */
+    int32_t grid_x, grid_y, lds_bytes;
+    int32_t sections[3];         /* table sections it reads, -1: none */
+} ace355_adapter_launch_info;
+typedef struct ace355_adapter_kron_info {   /* one row of the Kronecker term section */
+    int32_t out_l, out_k, in_m, in_n, wide, w1_f32, w2_f32;
+    float scale;
+    int64_t w1_offset, w2_offset; /* bytes into the factor scratch where the factor is a product (w*_f32), else -1 */
+} ace355_adapter_kron_info;
+typedef struct ace355_adapter_factor_info { /* one row of the factor job section */
+    int32_t rows, cols, rank, tile0, tiles_n, reserved;
+    int64_t offset;              /* bytes into the factor scratch */
+} ace355_adapter_factor_info;
+typedef struct ace355_adapter_dora_info {   /* one DoRA row; cls 2 rows first, then cls 3, each in target order */
+    int32_t cls, per_input, n, ntiles;
+    float eps, multiplier;
+    int64_t part_offset, f_offset; /* bytes into the DoRA scratch */
+} ace355_adapter_dora_info;
+typedef struct ace355_adapter_plan_rows {
+    ace355_adapter_target_info* targets;  int32_t cap_targets;
+    ace355_adapter_launch_info* launches; int32_t cap_launches;
+    ace355_adapter_kron_info* kron;       int32_t cap_kron;
+    ace355_adapter_factor_info* factors;  int32_t cap_factors;
+    ace355_adapter_dora_info* dora;       int32_t cap_dora;
+} ace355_adapter_plan_rows;
+typedef struct ace355_adapter_plan_info {
+    int32_t n_targets, n_merged;  /* merged targets first, in first-mention order, then the restored ones */
+    int32_t n_launches, n_lora_terms, n_kron_terms, n_factors, n_dora;
+    int32_t stale_kv, stale_o;    /* the call makes condition slots built from the cross-attention k / v resp. o weights stale */
+    int32_t reserved;
+    int64_t table_bytes, kscratch_floats, dscratch_bytes;
+    int64_t section_at[ACE355_ADAPTER_SECTIONS], section_bytes[ACE355_ADAPTER_SECTIONS];
+} ace355_adapter_plan_info;
+int ace355_adapter_plan(const ace355_dit_config* cfg, const ace355_lora_term* lora, int n_lora, const ace355_kron_term* kron, int n_kron,
+                        const ace355_dora_term* dora, int n_dora, const char* const* applied, int n_applied,
+                        const ace355_adapter_plan_rows* rows, ace355_adapter_plan_info* info);
 /* Copy the live (merged) weight of one of the ten target kinds above to dst_dev in the reference layout [out, in] (the inverse of the
  * packing's row map), as ACE355_DTYPE_F32 or ACE355_DTYPE_BF16; enqueued on `stream`.  Tests, and export of merged weights. */
 int ace355_dit_read_weight(ace355_dit* h, const char* name, void* dst_dev, int dtype, void* stream);
