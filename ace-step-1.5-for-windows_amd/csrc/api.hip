@@ -9,6 +9,7 @@
 #include "../../include/ace355.h"
 #include "adapter_plan.h"
 #include "attn_plan.h"
+#include "vae_plan.h"
 #include "gemm_plan.h"
 #include <dlfcn.h>
 #include <stdlib.h>
@@ -126,6 +127,49 @@ int ace355_attn_plan(const ace355_attn_request* r, ace355_attn_plan_info* out) {
     ACE_CHECK(r->N > 0 && r->Sq > 0 && r->Skv > 0 && r->Hq > 0 && r->Hkv > 0 && r->Hq % r->Hkv == 0 && r->part_floats >= 0, "attn_plan: empty problem or Hq % Hkv");
     const AttnPlan p = attn_plan_query(AttnRequest{r->N, r->Sq, r->Skv, r->Hq, r->Hkv, r->window, r->cu_slots, r->has_kv_len, r->mx_out, (long)r->part_floats});
     *out = ace355_attn_plan_info{p.kernel, p.nw, p.grid_x, p.grid_y, p.grid_z, p.threads, p.kv_split, p.merge_grid, p.mx_out_ok};
+    return ACE355_OK;
+}
+
+int ace355_conv_plan(const ace355_conv_request* r, ace355_conv_plan_info* out) {
+    ACE_CHECK(r && out, "conv_plan: null pointer");
+    ACE_CHECK(r->B > 0 && r->M > 0 && r->N > 0 && r->Cin > 0 && r->Cin % 64 == 0 && r->taps >= 1, "conv_plan: empty problem or Cin % 64");
+    ACE_CHECK(!r->fused || (r->Cin == 128 && r->N == 128 && r->taps == 7 && !r->x_view), "conv_plan: the fused k = 1 stage needs Cin = N = 128 and a plain k = 7 conv");
+    *out = plan_conv(*r, conv_knobs());
+    return ACE355_OK;
+}
+
+int ace355_vae_plan(const ace355_vae_config* cfg, int encoder, int B, int64_t T, int64_t budget_bytes, int overlap_frames,
+                    ace355_vae_step_info* steps_out, int capacity, int32_t* n_out, ace355_vae_plan_info* info_out) {
+    ACE_CHECK(cfg && n_out && info_out && capacity >= 0 && (steps_out || capacity == 0), "vae_plan: null pointer");
+    const char* bad = vae_config_error(*cfg);
+    ACE_CHECK(!bad, bad);
+    ACE_CHECK(B > 0 && T > 0 && T < (1L << 30) && budget_bytes >= 0 && overlap_frames >= 0, "vae_plan: sizes");
+    const VaeShape sh = vae_shape(*cfg);
+    const size_t budget = budget_bytes ? (size_t)budget_bytes : (size_t)96 << 30;
+    ace355_vae_plan_info info{};
+    VaePlan p;
+    if (encoder) {
+        ACE_CHECK(vae_latent_frames(sh, T) > 0, "vae_plan: audio shorter than one latent frame");
+        const long slot = plan_vae(sh, true, 1, T, VaeWindow{}, conv_knobs()).slot_elems;
+        info.items_per_window = vae_encode_group(B, T, slot, budget);
+        p = plan_vae(sh, true, info.items_per_window, T, VaeWindow{}, conv_knobs());
+        info.window_len = T;
+        info.activation_bytes = (int64_t)info.items_per_window * (slot * 2 * 3 + T * 64 * 2);
+    } else {
+        ACE_CHECK(T * sh.hop < (1L << 31), "vae_plan: sequence too long (2^31 samples per item)");
+        const VaeWindowPlan wp = plan_vae_windows(sh, B, (int)T, budget, overlap_frames);
+        ACE_CHECK(!wp.error, wp.error);
+        const VaeWindow w = vae_window_at(wp, (int)T, 0);
+        p = plan_vae(sh, false, wp.nb, T, w, conv_knobs());
+        info.items_per_window = wp.nb, info.core_frames = wp.tc, info.overlap_frames = wp.ov;
+        info.window_len = w.we - w.ws;
+        info.activation_bytes = (int64_t)vae_decode_bytes(sh, wp.nb, vae_window_frames(wp, (int)T));
+    }
+    info.n_steps = (int)p.steps.size(), info.n_stages = (int)p.stages.size();
+    info.out_len = p.out_len, info.slot_elems = p.slot_elems;
+    for (int i = 0; i < std::min(capacity, info.n_steps); ++i) steps_out[i] = p.steps[i];
+    *n_out = info.n_steps;
+    *info_out = info;
     return ACE355_OK;
 }
 

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "vae_plan.h"
 
 // (the round-3 chunk / tap loop, the register-staged fused k = 1 stage, s_setprio in the tap loops and the de-phasing of the two resident
 // workgroups were A/B arms of rounds 4-5: measured, not kept, removed in round 6 - git history up to dd0c588, numbers in DESIGN.md 13.7)
@@ -668,6 +669,21 @@ __global__ void ncl_to_nlc_kernel(const float* __restrict__ z, bf16_t* __restric
 
 }  // namespace
 
+const ConvKnobs& conv_knobs() {
+    static const ConvKnobs kn = [] {
+        auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+        const ConvKnobs d = CONV_KNOBS_DEFAULT;
+        return ConvKnobs{env("ACE355_CONV_RAS", d.ras), env("ACE355_CONV_CLK", d.clk), env("ACE355_CONV_TM", d.tm), env("ACE355_CONV_F8", d.f8),
+                         env("ACE355_CONV_FUSE_RU", d.fuse_ru), env("ACE355_VAE_EPISNAKE", d.episnake)};
+    }();
+    return kn;
+}
+
+// The four instantiations a plan can name (in the order the code object has always held them).
+using ConvKernel = void (*)(ConvArgs);
+static const struct { int bn, tm, ws; ConvKernel fn; } g_conv_kernels[] = {
+    {128, 256, 1, conv_kernel<128, 256, 1>}, {128, 256, 0, conv_kernel<128, 256>}, {128, 128, 0, conv_kernel<128, 128>}, {32, 128, 0, conv_kernel<32, 128>}};
+
 int launch_conv(const ConvArgs& a, hipStream_t s) {
     ACE_CHECK(a.Cin % 64 == 0, "conv: Cin must be a multiple of 64");
     ACE_CHECK(a.taps >= 1 && (a.taps - 1) * a.dil <= HALO_MAX && a.dil >= 1, "conv: window too large");
@@ -687,72 +703,14 @@ int launch_conv(const ConvArgs& a, hipStream_t s) {
                      (a.N % 8) == 0 && (a.y_shift % 8) == 0 &&
                      (a.y_batch_stride % 8) == 0 && (a.res_batch_stride % 8) == 0;
     }
-    static int tm_env = -1, clk_env = -1, ras_env = -1;
-    if (ras_env < 0) {
-        const char* e = getenv("ACE355_CONV_RAS");  // 0: the plain (m, n, b) grid (A/B runs); default 1: XCD-aware rasterisation
-        ras_env = e ? atoi(e) : 1;
-    }
-    if (clk_env < 0) {
-        const char* e = getenv("ACE355_CONV_CLK");
-        clk_env = e ? atoi(e) : 0;
-    }
-    aw.clk_probe = clk_env;
-    if (tm_env < 0) {
-        const char* e = getenv("ACE355_CONV_TM");  // 128 / 256 force a tile height (A/B runs); default: by problem size
-        tm_env = e ? atoi(e) : 0;
-    }
-    if (a.N >= 128 || a.N % 128 == 0) {
-        const long wgs128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) * a.B;
-        // 8-wave tiles pay off where the tap loop dominates (Cin >= 256: +2-5 %); at Cin = 128 and for k = 1 the exposed
-        // window load of the un-prefetched form costs more than the sharing saves (-5 % / -35 %)
-        // (the 2-tap transposed / strided convs are faster on the 4-wave tile at every stage: 1.31 / 1.34 / 1.46 ms against
-        //  1.44 / 1.50 / 1.83 ms)
-        // (the fused k = 1 stage of a residual unit is written for the 4-wave 128-row tile only: forcing the tall tile onto it with
-        //  ACE355_CONV_TM=256 gave a - 6 dB decode, caught by test_decode_at_the_metric_length_vs_oracle; it is refused here)
-        // Round 4, after the Snake move (the transposed convs stage plain rows now) and a per-launch sweep of the forced heights
-        // (profiles/r04/r04_conv_tile_height_sweep.txt, 8 x 30 s): the k = 7 convs at C = 1024 are 3776 four-wave tiles - below the old 4096
-        // threshold - and run 1076-1097 us on them against 875-897 us on 1888 tall ones: (threshold lowered, see below); the plain-row transposed convs with Cin >= 1024 gain too (782 -> 689 and 1096 -> 1008 us), the ones with
-        // Cin <= 512 lose (1128 -> 1174, 1349 -> 1510, 1660 -> 2112 us) and stay on the four-wave tile, like the k = 1 convs (+ 5-25 %).
-        // The same sweep at 4 / 2 / 1 songs (profiles/r04/r04_conv_tile_height_sweep_small_batches.txt) shows the size threshold itself was
-        // wrong for the k = 7 convs: the tall tile wins at every batch (one song: 205 -> 190, 259 -> 221, 240 -> 197 us at C = 1024 / 512 /
-        // 256; two songs: 328 -> 254, 450 -> 376 us), down to the 472 four-wave tiles of one 30 s song at C = 1024: threshold 448.  The
-        // plain-row transposed convs with Cin >= 1024 gain from ~ 900 four-wave tiles up (one song, 2048 -> 1024, 480 tiles: 149 -> 170 us).
-        // Round 5, after version 2 of the chunk / tap loop (the 8-wave form no longer spills, its window loads are no longer serialised
-        // by scratch reloads): re-swept at 1 / 2 / 4 / 8 songs (profiles/r05/r05_conv_tile_height_sweep.txt).  The 8-wave tile now wins on
-        // EVERY k >= 2 launch that fills the chip about one and a half times (512 tall workgroups are resident at once = 1024 four-wave
-        // tiles): the transposed convs at every Cin (8 songs: 1645 -> 1388, 1256 -> 1069, 1020 -> 845 us for Cin = 128 / 256 / 512), the k = 7
-        // convs from ~1400 four-wave tiles (one song: C = 256 204 -> 175 us, C = 512 224 -> 221, C = 1024 (472 tiles) 177 -> 197: stays 4-wave;
-        // two songs: all three win), the unfused k = 7 at C = 128 too (3.38 -> 2.98 ms).  Below that the tail of half-empty rounds costs more.
-        const bool tall_k = a.Cin >= 128 && a.taps >= 3 && wgs128 >= 1400;
-        const bool tall_t = a.taps == 2 && a.Cin >= 128 && !a.alpha && !a.x_valid && wgs128 >= 1500;
-        const bool tall = !a.w2 && !a.res && (tm_env ? tm_env == 256 : (tall_k || tall_t));
-        const int tm_rows = tall ? 256 : 128;
-        dim3 grid((a.M + tm_rows - 1) / tm_rows, (a.N + 127) / 128, a.B);
-        aw.ras_tm = aw.ras_tn = 0;
-        if (ras_env && grid.y > 1 && (long)grid.x * grid.y < (1L << 31)) {
-            aw.ras_tm = (int)grid.x, aw.ras_tn = (int)grid.y;
-            grid = dim3(grid.x * grid.y, 1, a.B);
-        }
-        // fused residual unit (C = 128): the 8-wave form with 32 x 128 wave tiles from the same size threshold as the other k = 7 convs
-        // (ACE355_CONV_F8=0 / 1: never / always, A/B runs); both forms give the same bits (frag_kperm)
-        static int f8_env = -2;
-        if (f8_env == -2) {
-            const char* e = getenv("ACE355_CONV_F8");
-            f8_env = e ? atoi(e) : -1;
-        }
-        const bool f8 = a.w2 && (f8_env >= 0 ? f8_env != 0 : wgs128 >= 1400);
-        if (f8) {
-            dim3 g8((a.M + 255) / 256, 1, a.B);
-            aw.ras_tm = aw.ras_tn = 0;
-            hipLaunchKernelGGL((conv_kernel<128, 256, 1>), g8, dim3(512), 0, s, aw);
-        } else
-        if (tall) hipLaunchKernelGGL((conv_kernel<128, 256>), grid, dim3(512), 0, s, aw);
-        else hipLaunchKernelGGL((conv_kernel<128, 128>), grid, dim3(256), 0, s, aw);
-    } else {
-        aw.ras_tm = aw.ras_tn = 0;
-        dim3 grid((a.M + 127) / 128, (a.N + 31) / 32, a.B);
-        hipLaunchKernelGGL((conv_kernel<32, 128>), grid, dim3(256), 0, s, aw);
-    }
+    const ConvKnobs& kn = conv_knobs();
+    const ConvPlan p = plan_conv(ConvRequest{a.B, a.M, a.N, a.Cin, a.taps, a.alpha != nullptr, a.x_valid != 0, a.res != nullptr, a.w2 != nullptr, 0}, kn);
+    aw.ras_tm = p.ras_tm, aw.ras_tn = p.ras_tn, aw.clk_probe = kn.clk;
+    ConvKernel fn = nullptr;
+    for (const auto& r : g_conv_kernels)
+        if (r.bn == p.bn && r.tm == p.tm && r.ws == p.ws) fn = r.fn;
+    ACE_CHECK(fn, "conv: the plan names no kernel instantiation");
+    hipLaunchKernelGGL(fn, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(p.threads), 0, s, aw);
     ACE_LAUNCH_CHECK();
     if (aw.clk_probe) {
         ACE_HIP(hipStreamSynchronize(s));

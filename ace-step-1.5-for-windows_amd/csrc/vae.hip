@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "encoder.h"   // dev_alloc
+#include "vae_plan.h"
 
 using namespace ace355;
 
@@ -27,19 +28,16 @@ struct SnakeP {
 struct ResUnitW {
     SnakeP s1, s2;
     ConvW c1, c2;
-    int dil = 1;
 };
 struct BlockW {
     SnakeP s1;
     ConvW ct;
-    int stride = 1, pad = 0, cin = 0, cout = 0;
     ResUnitW ru[3];
 };
 struct EncBlockW {
     ResUnitW ru[3];
     SnakeP s1;       // tiled `stride` times (virtual channel c' -> channel c' % cin)
     ConvW cd;        // strided conv as 2 taps over stride*cin virtual channels
-    int stride = 1, pad = 0, cin = 0, cout = 0;
 };
 struct RawT {
     float* p = nullptr;
@@ -165,6 +163,7 @@ __global__ void cvt_bf16_f32_kernel(const bf16_t* __restrict__ in, float* __rest
 
 struct ace355_vae {
     ace355_vae_config cfg;
+    VaeShape shape;   // widths, strides and pads of both halves (vae_plan.h): what finalize builds and what the plans walk
     int hop = 1;
     std::map<std::string, RawT> raw;
     std::vector<void*> allocs;
@@ -197,11 +196,8 @@ struct ace355_vae {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
     double flops = 0;
     long launches = 0;
-    // stage taps (ace355_vae_set_tap): [0] decoder, [1] encoder; stage -> (destination, capacity in bytes).  tap_stages is the stage
-    // list of the running call (empty when that half has no tap: nothing is looked up or copied), tap_next the next stage to come
+    // stage taps (ace355_vae_set_tap): [0] decoder, [1] encoder; stage -> (destination, capacity in bytes)
     std::map<int, std::pair<void*, size_t>> taps[2];
-    std::vector<ace355_vae_stage_info> tap_stages;
-    int tap_next = 0;
 };
 
 namespace {
@@ -354,9 +350,8 @@ int build_snake_tiled(ace355_vae* h, const std::string& base, int C, int reps, S
     return 0;
 }
 
-int build_res_unit(ace355_vae* h, const std::string& r, int C, int dil, ResUnitW* R) {
+int build_res_unit(ace355_vae* h, const std::string& r, int C, ResUnitW* R) {
     int rc;
-    R->dil = dil;
     if ((rc = build_snake(h, r + ".snake1", C, &R->s1))) return rc;
     if ((rc = build_conv(h, r + ".conv1", C, C, 7, true, &R->c1))) return rc;
     if ((rc = build_snake(h, r + ".snake2", C, &R->s2))) return rc;
@@ -386,16 +381,12 @@ extern "C" {
 
 int ace355_vae_create(const ace355_vae_config* cfg, ace355_vae** out) {
     ACE_CHECK(cfg && out, "vae_create: null argument");
-    ACE_CHECK(cfg->num_blocks > 0 && cfg->num_blocks <= ACE355_MAX_BLOCKS, "vae_create: num_blocks");
-    ACE_CHECK(cfg->decoder_input_channels % 64 == 0 && cfg->decoder_channels % 64 == 0, "vae_create: channels must be multiples of 64");
-    ACE_CHECK(cfg->audio_channels >= 1 && cfg->audio_channels <= 32, "vae_create: audio_channels");
+    const char* bad = vae_config_error(*cfg);
+    ACE_CHECK(!bad, bad);
     ace355_vae* h = new ace355_vae();
     h->cfg = *cfg;
-    h->hop = 1;
-    for (int i = 0; i < cfg->num_blocks; ++i) {
-        ACE_CHECK(cfg->upsampling_ratios[i] >= 1 && cfg->channel_multiples[i] >= 1, "vae_create: ratios/multiples");
-        h->hop *= cfg->upsampling_ratios[i];
-    }
+    h->shape = vae_shape(*cfg);
+    h->hop = h->shape.hop;
     if (const char* e = getenv("ACE355_VAE_BUDGET_MB")) { const long mb = atol(e); if (mb > 0) h->decode_budget = (size_t)mb << 20; }
     *out = h;
     return ACE355_OK;
@@ -443,62 +434,39 @@ int ace355_vae_load_tensor(ace355_vae* h, const char* name, const void* data, in
 
 int ace355_vae_finalize(ace355_vae* h) {
     ACE_CHECK(h, "vae_finalize: null handle");
-    const ace355_vae_config& c = h->cfg;
-    const int nb = c.num_blocks;
-    int cm[ACE355_MAX_BLOCKS + 1];
-    cm[0] = 1;
-    for (int i = 0; i < nb; ++i) cm[i + 1] = c.channel_multiples[i];
+    const VaeShape& sh = h->shape;
+    const int nb = sh.nb;
     int rc;
-    const int C0 = c.decoder_channels * cm[nb];
-    if ((rc = build_conv(h, "decoder.conv1", C0, c.decoder_input_channels, 7, true, &h->conv1))) return rc;
+    if ((rc = build_conv(h, "decoder.conv1", sh.dec_c0, sh.zc, 7, true, &h->conv1))) return rc;
     h->blocks.assign(nb, BlockW());
     for (int i = 0; i < nb; ++i) {
         BlockW& B = h->blocks[i];
-        B.cin = c.decoder_channels * cm[nb - i];
-        B.cout = c.decoder_channels * cm[nb - i - 1];
-        B.stride = c.upsampling_ratios[i];
-        B.pad = (B.stride + 1) / 2;
-        ACE_CHECK(B.cin % 64 == 0 && B.cout % 64 == 0, "vae_finalize: block channels must be multiples of 64");
+        const VaeBlockShape& S = sh.dec[i];
         const std::string p = "decoder.block." + std::to_string(i);
-        if ((rc = build_snake(h, p + ".snake1", B.cin, &B.s1))) return rc;
-        if ((rc = build_convt(h, p + ".conv_t1", B.cin, B.cout, B.stride, &B.ct))) return rc;
-        const int dils[3] = {1, 3, 9};
-        for (int j = 0; j < 3; ++j) {
-            ResUnitW& R = B.ru[j];
-            R.dil = dils[j];
-            const std::string r = p + ".res_unit" + std::to_string(j + 1);
-            if ((rc = build_snake(h, r + ".snake1", B.cout, &R.s1))) return rc;
-            if ((rc = build_conv(h, r + ".conv1", B.cout, B.cout, 7, true, &R.c1))) return rc;
-            if ((rc = build_snake(h, r + ".snake2", B.cout, &R.s2))) return rc;
-            if ((rc = build_conv(h, r + ".conv2", B.cout, B.cout, 1, true, &R.c2))) return rc;
-        }
+        if ((rc = build_snake(h, p + ".snake1", S.cin, &B.s1))) return rc;
+        if ((rc = build_convt(h, p + ".conv_t1", S.cin, S.cout, S.stride, &B.ct))) return rc;
+        for (int j = 0; j < 3; ++j)
+            if ((rc = build_res_unit(h, p + ".res_unit" + std::to_string(j + 1), S.cout, &B.ru[j]))) return rc;
     }
-    if ((rc = build_snake(h, "decoder.snake1", c.decoder_channels, &h->s_out))) return rc;
-    if ((rc = build_conv(h, "decoder.conv2", c.audio_channels, c.decoder_channels, 7, false, &h->conv2))) return rc;
+    if ((rc = build_snake(h, "decoder.snake1", sh.dec_cl, &h->s_out))) return rc;
+    if ((rc = build_conv(h, "decoder.conv2", sh.audio, sh.dec_cl, 7, false, &h->conv2))) return rc;
     // encoder half (optional): vae_model.py:148-187.  encoder_hidden_size = 2 * latent channels (mean | scale)
     h->has_encoder = false;
     for (auto& kv : h->raw) if (kv.first.rfind("encoder.", 0) == 0) { h->has_encoder = true; break; }
     if (h->has_encoder) {
-        const int EH = 2 * c.decoder_input_channels;
-        ACE_CHECK(EH % 64 == 0, "vae_finalize: encoder width must be a multiple of 64");
-        if ((rc = build_conv_im2col(h, "encoder.conv1", EH, c.audio_channels, 7, &h->e_conv1))) return rc;
+        if ((rc = build_conv_im2col(h, "encoder.conv1", sh.eh, sh.audio, 7, &h->e_conv1))) return rc;
         h->e_blocks.assign(nb, EncBlockW());
         for (int i = 0; i < nb; ++i) {
             EncBlockW& B = h->e_blocks[i];
-            B.cin = EH * cm[i];
-            B.cout = EH * cm[i + 1];
-            B.stride = c.upsampling_ratios[nb - 1 - i];  // downsampling_ratios = reversed upsampling_ratios
-            B.pad = (B.stride + 1) / 2;
-            ACE_CHECK(B.cin % 64 == 0 && B.cout % 64 == 0, "vae_finalize: encoder block channels must be multiples of 64");
+            const VaeBlockShape& S = sh.enc[i];
             const std::string p = "encoder.block." + std::to_string(i);
-            const int dils[3] = {1, 3, 9};
             for (int j = 0; j < 3; ++j)
-                if ((rc = build_res_unit(h, p + ".res_unit" + std::to_string(j + 1), B.cin, dils[j], &B.ru[j]))) return rc;
-            if ((rc = build_snake_tiled(h, p + ".snake1", B.cin, B.stride, &B.s1))) return rc;
-            if ((rc = build_conv_strided(h, p + ".conv1", B.cout, B.cin, B.stride, &B.cd))) return rc;
+                if ((rc = build_res_unit(h, p + ".res_unit" + std::to_string(j + 1), S.cin, &B.ru[j]))) return rc;
+            if ((rc = build_snake_tiled(h, p + ".snake1", S.cin, S.stride, &B.s1))) return rc;
+            if ((rc = build_conv_strided(h, p + ".conv1", S.cout, S.cin, S.stride, &B.cd))) return rc;
         }
-        if ((rc = build_snake(h, "encoder.snake1", EH * cm[nb], &h->e_s_out))) return rc;
-        if ((rc = build_conv(h, "encoder.conv2", EH, EH * cm[nb], 3, true, &h->e_conv2))) return rc;
+        if ((rc = build_snake(h, "encoder.snake1", sh.enc_cl, &h->e_s_out))) return rc;
+        if ((rc = build_conv(h, "encoder.conv2", sh.eh, sh.enc_cl, 3, true, &h->e_conv2))) return rc;
     }
     ACE_HIP(hipDeviceSynchronize());
     // raw weight_v / weight_g copies are no longer needed (biases are still referenced)
@@ -514,266 +482,71 @@ int ace355_vae_finalize(ace355_vae* h) {
 
 int ace355_vae_hop(const ace355_vae* h) { return h ? h->hop : 0; }
 
-// Residual unit in place on `state` (scratch `tmp`), shared by decode and encode: x + conv_k1(snake2(conv_k7_dil(snake1(x))))
-// ACE355_VAE_EPISNAKE (default 1): the Snake of an activation with ONE reader is applied by its producer's epilogue (ConvArgs::osnake_a):
-// snake2 of an unfused residual unit by the k = 7 conv (the k = 1 conv then stages plain rows: it evaluated the Snake once per 128-column
-// tile, 2 / 4 / 8 times per element at C = 256 / 512 / 1024), the next block's (or the output conv's) Snake by a decoder block's last unit
-// and by conv1 (the 2-tap transposed convs evaluated it s * Cout / 128 = 80 / 24 / 8 / 4 / 2 times per element).  0: every Snake in its
-// reader's window staging (A/B runs).  `out_snake`: the reader's Snake when the unit's output has that single reader, else null.
-static int episnake_on() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("ACE355_VAE_EPISNAKE");
-        on = e ? atoi(e) : 1;
-    }
-    return on;
-}
-static bool unit_fused(int C) {
-    static int fuse = -1;
-    if (fuse < 0) {
-        const char* e = getenv("ACE355_CONV_FUSE_RU");  // 0: two launches per unit everywhere (A/B runs)
-        fuse = e ? atoi(e) : 1;
-    }
-    return fuse && C == 128;
-}
-
-// The stored tensors of a decode of T latent frames / an encode of T samples, in launch order (ace355.h: ACE355_VAE_STAGE_*).  The
-// decode / encode below walk the same sequence and tap_stage checks every stage's kind against this list as it comes.
-static void stage_push(std::vector<ace355_vae_stage_info>& v, int kind, int block, int unit, int channels, int flags, int src, int res,
-                       int dil, long rows) {
-    ace355_vae_stage_info si;
-    si.kind = kind; si.block = block; si.unit = unit; si.channels = channels; si.flags = flags; si.src = src; si.res = res;
-    si.dilation = dil; si.rows = rows;
-    v.push_back(si);
-}
-static void stage_push_unit(std::vector<ace355_vae_stage_info>& v, int block, int unit, int C, int dil, long rows, bool epi, bool out_snake) {
-    const int in = (int)v.size() - 1;
-    const int osn = out_snake ? ACE355_VAE_FLAG_OUT_SNAKE : 0;
-    if (unit_fused(C)) {
-        stage_push(v, ACE355_VAE_STAGE_UNIT, block, unit, C, ACE355_VAE_FLAG_FUSED | ACE355_VAE_FLAG_IN_SNAKE | osn, in, in, dil, rows);
-        return;
-    }
-    stage_push(v, ACE355_VAE_STAGE_UNIT_K7, block, unit, C, ACE355_VAE_FLAG_IN_SNAKE | (epi ? ACE355_VAE_FLAG_OUT_SNAKE : 0), in, -1, dil, rows);
-    stage_push(v, ACE355_VAE_STAGE_UNIT_K1, block, unit, C, (epi ? 0 : ACE355_VAE_FLAG_IN_SNAKE) | osn, in + 1, in, 1, rows);
-}
-static int stage_list(const ace355_vae* h, int enc, long T, std::vector<ace355_vae_stage_info>& v) {
-    v.clear();
-    const ace355_vae_config& c = h->cfg;
-    if (!enc) {
-        const bool epi = episnake_on() != 0 && !h->blocks.empty();
-        stage_push(v, ACE355_VAE_STAGE_INPUT, -1, -1, c.decoder_input_channels, 0, -1, -1, 1, T);
-        stage_push(v, ACE355_VAE_STAGE_CONV_IN, -1, -1, h->conv1.N, epi ? ACE355_VAE_FLAG_OUT_SNAKE : 0, 0, -1, 1, T);
-        long L = T;
-        for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
-            const BlockW& Bk = h->blocks[bi];
-            L = (L - 1) * Bk.stride - 2 * Bk.pad + 2 * Bk.stride;
-            stage_push(v, ACE355_VAE_STAGE_CONVT, (int)bi, -1, Bk.cout, epi ? 0 : ACE355_VAE_FLAG_IN_SNAKE, (int)v.size() - 1, -1, 1, L);
-            for (int j = 0; j < 3; ++j) stage_push_unit(v, (int)bi, j, Bk.cout, Bk.ru[j].dil, L, epi, epi && j == 2);
-        }
-        return 0;
-    }
-    const bool epi = episnake_on() != 0;
-    const int EH = 2 * c.decoder_input_channels;
-    stage_push(v, ACE355_VAE_STAGE_INPUT, -1, -1, 64, 0, -1, -1, 1, T);
-    stage_push(v, ACE355_VAE_STAGE_CONV_IN, -1, -1, EH, 0, 0, -1, 1, T);
-    long L = T;
-    for (size_t bi = 0; bi < h->e_blocks.size(); ++bi) {
-        const EncBlockW& Bk = h->e_blocks[bi];
-        for (int j = 0; j < 3; ++j) stage_push_unit(v, (int)bi, j, Bk.cin, Bk.ru[j].dil, L, epi, epi && j == 2);
-        L = (L + 2 * Bk.pad - 2 * Bk.stride) / Bk.stride + 1;
-        ACE_CHECK(L > 0, "vae stages: audio shorter than one latent frame");
-        stage_push(v, ACE355_VAE_STAGE_DOWN, (int)bi, -1, Bk.cout,
-                   (epi ? 0 : ACE355_VAE_FLAG_IN_SNAKE) | (epi && bi + 1 == h->e_blocks.size() ? ACE355_VAE_FLAG_OUT_SNAKE : 0), (int)v.size() - 1,
-                   -1, 1, L);
-    }
-    stage_push(v, ACE355_VAE_STAGE_HEAD, -1, -1, EH,
-               ACE355_VAE_FLAG_F32_NCL | ((!epi || h->e_blocks.empty()) ? ACE355_VAE_FLAG_IN_SNAKE : 0), (int)v.size() - 1, -1, 1, L);
-    return 0;
-}
-// The stage that was just launched: copy it out when it is tapped.  Without a tap on this half tap_stages is empty and nothing happens.
-static int tap_stage(ace355_vae* h, int enc, int kind, const void* p, int B, hipStream_t s) {
-    if (h->tap_stages.empty()) return 0;
-    const int k = h->tap_next++;
-    ACE_CHECK(k < (int)h->tap_stages.size() && h->tap_stages[k].kind == kind, "vae tap: the stage list and the launch sequence disagree");
+// A stage that was just stored: copy it out when it is tapped.
+static int tap_copy(ace355_vae* h, int enc, const ace355_vae_stage_info& si, int k, const void* p, int B, hipStream_t s) {
     auto it = h->taps[enc].find(k);
     if (it == h->taps[enc].end()) return 0;
-    const ace355_vae_stage_info& si = h->tap_stages[k];
     const size_t bytes = (size_t)B * si.rows * si.channels * ((si.flags & ACE355_VAE_FLAG_F32_NCL) ? 4 : 2);
     ACE_CHECK(bytes <= it->second.second, "vae tap: the destination is smaller than the stage");
     ACE_HIP(hipMemcpyAsync(it->second.first, p, bytes, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 // Start of a decode / encode: with a tap on this half the call must be one whole-sequence window over the whole batch
-static int tap_begin(ace355_vae* h, int enc, long T, bool single_window) {
-    h->tap_stages.clear();
-    h->tap_next = 0;
-    if (h->taps[enc].empty()) return 0;
-    if (!single_window) {
-        set_error("vae tap: the call splits into several windows under the activation budget; a tap needs one whole-sequence window");
-        return ACE355_ERR_STATE;
-    }
-    int rc = stage_list(h, enc, T, h->tap_stages);
-    if (rc) { h->tap_stages.clear(); return rc; }
-    ACE_CHECK(h->taps[enc].rbegin()->first < (int)h->tap_stages.size(), "vae tap: no such stage");
-    return 0;
-}
-static int tap_end(ace355_vae* h) {
-    const bool ok = h->tap_stages.empty() || h->tap_next == (int)h->tap_stages.size();
-    h->tap_stages.clear();
-    ACE_CHECK(ok, "vae tap: the stage list and the launch sequence disagree");
-    return 0;
+static int tap_begin(ace355_vae* h, int enc, bool single_window) {
+    if (h->taps[enc].empty() || single_window) return 0;
+    set_error("vae tap: the call splits into several windows under the activation budget; a tap needs one whole-sequence window");
+    return ACE355_ERR_STATE;
 }
 
-static int run_res_unit(ace355_vae* h, const ResUnitW& R, bf16_t*& state, bf16_t*& tmp, int B, long L, int C, hipStream_t s,
-                        int enc, const SnakeP* out_snake = nullptr) {
-    if (unit_fused(C)) {
-        // C = 128: one workgroup tile spans all channels, so the k = 1 conv runs on the k = 7 result inside the same kernel
-        // (conv.hip, ConvArgs::w2).  The unit's output lands in `tmp` (neighbouring tiles still read `state`'s halo rows):
-        // the two buffers trade places.
-        ConvArgs f{};
-        f.x = state; f.x_batch_stride = L * C; f.L_in = (int)L; f.Cin = C;
-        f.w = R.c1.w; f.bias = R.c1.bias; f.alpha = R.s1.ea; f.beta = R.s1.ib;
-        f.w2 = R.c2.w; f.bias2 = R.c2.bias; f.alpha2 = R.s2.ea; f.beta2 = R.s2.ib;
-        f.res = state; f.res_batch_stride = L * C;
-        f.y = tmp; f.y_batch_stride = L * C;
-        f.B = B; f.M = (int)L; f.N = C; f.taps = 7; f.dil = R.dil; f.center = 3;
-        f.y_shift = 0; f.y_valid = L * C; f.out_mode = 0;
-        if (out_snake) f.osnake_a = out_snake->ea, f.osnake_b = out_snake->ib;
-        const int rcf = run_conv(h, f, s);
-        if (rcf) return rcf;
-        std::swap(state, tmp);
-        return tap_stage(h, enc, ACE355_VAE_STAGE_UNIT, state, B, s);
-    }
-    ConvArgs a{};
-    a.x = state; a.x_batch_stride = L * C; a.L_in = (int)L; a.Cin = C;
-    a.w = R.c1.w; a.bias = R.c1.bias; a.alpha = R.s1.ea; a.beta = R.s1.ib;
-    a.y = tmp; a.y_batch_stride = L * C;
-    a.B = B; a.M = (int)L; a.N = C; a.taps = 7; a.dil = R.dil; a.center = 3;
-    a.y_shift = 0; a.y_valid = L * C; a.out_mode = 0;
-    const bool epi = episnake_on() != 0;
-    if (epi) a.osnake_a = R.s2.ea, a.osnake_b = R.s2.ib;   // tmp = snake2(conv_k7(...)): its only reader is the k = 1 conv below
-    int rc = run_conv(h, a, s);
-    if (rc) return rc;
-    if ((rc = tap_stage(h, enc, ACE355_VAE_STAGE_UNIT_K7, tmp, B, s))) return rc;
-    a = ConvArgs{};
-    a.x = tmp; a.x_batch_stride = L * C; a.L_in = (int)L; a.Cin = C;
-    a.w = R.c2.w; a.bias = R.c2.bias;
-    if (!epi) a.alpha = R.s2.ea, a.beta = R.s2.ib;
-    if (out_snake) a.osnake_a = out_snake->ea, a.osnake_b = out_snake->ib;
-    a.res = state; a.res_batch_stride = L * C;
-    a.y = state; a.y_batch_stride = L * C;
-    a.B = B; a.M = (int)L; a.N = C; a.taps = 1; a.dil = 1; a.center = 0;
-    a.y_shift = 0; a.y_valid = L * C; a.out_mode = 0;
-    if ((rc = run_conv(h, a, s))) return rc;
-    return tap_stage(h, enc, ACE355_VAE_STAGE_UNIT_K1, state, B, s);
-}
-
-// Bytes of the three ping-pong activation buffers for a decode of `nb` items x `frames` latent frames (largest stage: L * C).
-static size_t decode_elems(const ace355_vae* h, long frames) {
-    size_t need = (size_t)frames * h->conv1.N;
-    long L = frames;
-    for (const BlockW& Bk : h->blocks) {
-        L = (L - 1) * Bk.stride - 2 * Bk.pad + 2 * Bk.stride;
-        need = std::max(need, (size_t)L * Bk.cout);
-    }
-    return need;
-}
-static size_t decode_bytes(const ace355_vae* h, int nb, long frames) { return 3 * (decode_elems(h, frames) * (size_t)nb * 2 + 256); }
-
-// Receptive half-width of one output sample in LATENT frames: conv1 (k7) + per block {2-tap polyphase transposed conv at the input
-// rate, three k7 residual units with dilations 1 / 3 / 9 at the output rate} + the k7 output conv.  Everything further away from a
-// window edge than this is bit-identical to the whole-sequence decode (same per-element MFMA accumulation order).
-static int decode_receptive_frames(const ace355_vae* h) {
-    double rf = 3.0, rate = 1.0;
-    for (const BlockW& Bk : h->blocks) {
-        rf += 1.0 / rate;
-        rate *= Bk.stride;
-        rf += 3.0 * (1 + 3 + 9) / rate;
-    }
-    rf += 3.0 / rate;
-    return (int)ceil(rf);
-}
-
-// One decode window: `nb` items, latent frames [ws, we) of every item (zin rows; rows outside the window are treated as zero,
-// which is the true padding at the sequence ends and discarded halo elsewhere); the samples of frames [cs, ce) are written to wav.
-static int decode_window(ace355_vae* h, int b0, int nb, int T, int ws, int we, int cs, int ce, float* wav_out_dev, hipStream_t s) {
-    const ace355_vae_config& c = h->cfg;
-    const int Tw = we - ws;
-    bf16_t *cur = h->buf[0], *nxt = h->buf[1], *tmp = h->buf[2];
-    long L = Tw;
+// The executor: one decode window / encode group, the steps of its plan in order (vae_plan.h).  `in` / `out`: the call's input image and
+// output at the window's first item.  Roles become pointers, a step becomes ConvArgs, a tapped stage is copied out behind its launch.
+static int run_plan(ace355_vae* h, int enc, const VaePlan& p, int B, const bf16_t* in, void* out, hipStream_t s) {
+    const bool tapped = !h->taps[enc].empty();
+    ACE_CHECK(!tapped || h->taps[enc].rbegin()->first < (int)p.stages.size(), "vae tap: no such stage");
     int rc;
-    ConvArgs a{};
-    // conv1: k7, no snake (vae_model.py:224)
-    a.x = h->zin + ((size_t)b0 * T + ws) * c.decoder_input_channels; a.x_batch_stride = (long)T * c.decoder_input_channels; a.L_in = Tw;
-    a.Cin = c.decoder_input_channels;
-    a.w = h->conv1.w; a.bias = h->conv1.bias;
-    a.y = cur; a.y_batch_stride = (long)Tw * h->conv1.N;
-    a.B = nb; a.M = Tw; a.N = h->conv1.N; a.taps = 7; a.dil = 1; a.center = 3;
-    a.y_shift = 0; a.y_valid = (long)Tw * h->conv1.N; a.out_mode = 0;
-    const bool epi = episnake_on() != 0 && !h->blocks.empty();
-    if (epi) a.osnake_a = h->blocks[0].s1.ea, a.osnake_b = h->blocks[0].s1.ib;   // conv1's only reader: block 0's Snake -> transposed conv
-    if ((rc = run_conv(h, a, s))) return rc;
-    if ((rc = tap_stage(h, 0, ACE355_VAE_STAGE_CONV_IN, cur, nb, s))) return rc;
-
-    for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
-        const BlockW& Bk = h->blocks[bi];
-        // the Snake of whoever reads this block's output (the next block's transposed conv, or the output conv): applied by the last unit
-        const SnakeP* next_snake = !epi ? nullptr : (bi + 1 < h->blocks.size() ? &h->blocks[bi + 1].s1 : &h->s_out);
-        const long Lout = (L - 1) * Bk.stride - 2 * Bk.pad + 2 * Bk.stride;
-        // snake -> ConvTranspose1d as the 2-tap polyphase GEMM (vae_model.py:136-137)
-        a = ConvArgs{};
-        a.x = cur; a.x_batch_stride = L * Bk.cin; a.L_in = (int)L; a.Cin = Bk.cin;
-        a.w = Bk.ct.w; a.bias = Bk.ct.bias;
-        if (!epi) a.alpha = Bk.s1.ea, a.beta = Bk.s1.ib;   // (epi: `cur` already holds snake(x), written by its producer)
-        a.y = nxt; a.y_batch_stride = Lout * Bk.cout;
-        a.B = nb; a.M = (int)L + 1; a.N = Bk.ct.N; a.taps = 2; a.dil = 1; a.center = 1;
-        a.y_shift = -(long)Bk.pad * Bk.cout; a.y_valid = Lout * Bk.cout; a.out_mode = 0;
-        if ((rc = run_conv(h, a, s))) return rc;
-        if ((rc = tap_stage(h, 0, ACE355_VAE_STAGE_CONVT, nxt, nb, s))) return rc;
-        for (int j = 0; j < 3; ++j)  // x + conv_k1(snake2(conv_k7_dil(snake1(x)))), in place on the block state (vae_model.py:79-87)
-            if ((rc = run_res_unit(h, Bk.ru[j], nxt, tmp, nb, Lout, Bk.cout, s, 0, j == 2 ? next_snake : nullptr))) return rc;
-        std::swap(cur, nxt);
-        L = Lout;
-    }
-    // snake -> conv k7 -> [B, audio, hop * T] fp32 (vae_model.py:228-229): the window's core samples go straight to their place
-    const long hop = h->hop, Lall = hop * T;
-    a = ConvArgs{};
-    a.x = cur; a.x_batch_stride = L * c.decoder_channels; a.L_in = (int)L; a.Cin = c.decoder_channels;
-    a.w = h->conv2.w; a.bias = nullptr;
-    if (!epi) a.alpha = h->s_out.ea, a.beta = h->s_out.ib;
-    a.y = wav_out_dev + (size_t)b0 * c.audio_channels * Lall; a.y_batch_stride = Lall * c.audio_channels;
-    a.B = nb; a.M = (int)L; a.N = c.audio_channels; a.taps = 7; a.dil = 1; a.center = 3;
-    a.out_mode = 1; a.n_real = c.audio_channels;
-    a.ncl_ld = Lall; a.ncl_off = (long)cs * hop; a.ncl_m_lo = (int)((cs - ws) * hop); a.ncl_m_hi = (int)((ce - ws) * hop);
-    return run_conv(h, a, s);
-}
-
-// Window plan of a decode under the activation budget (the reference bounds decode memory by policy: chunk sizes by free VRAM,
-// H/memory_utils.py:48-83, overlap-discard windows, H/vae_decode_chunks.py:51-112): whole batch and whole sequence when the three
-// ping-pong buffers fit; else fewer items per window (exact: items are independent); else windows of `tc` core frames with `ov`
-// halo frames on either side, the halo decoded and discarded.
-static int decode_plan(const ace355_vae* h, int B, int T, size_t budget, int* nb_out, int* tc_out, int* ov_out) {
-    const int rf = decode_receptive_frames(h);
-    int ov = h->decode_overlap > 0 ? h->decode_overlap : std::max(16, ((rf + 2 + 7) / 8) * 8);
-    ACE_CHECK(ov >= rf, "vae_decode: the window overlap must cover the decoder's receptive field");
-    int nb = B, tc = T;
-    if (decode_bytes(h, B, T) > budget) {
-        const size_t per_item = decode_bytes(h, 1, T);
-        if (per_item <= budget) nb = (int)std::max<size_t>(1, std::min<size_t>(B, budget / per_item));
-        else {
-            nb = 1;
-            // bytes grow linearly in the window length: largest window that fits, minus the two halos
-            const size_t per_frame = decode_bytes(h, 1, 1024) / 1024 + 1;
-            const long win = (long)(budget / per_frame);
-            tc = (int)std::min<long>(T, win - 2L * ov);
-            ACE_CHECK(tc >= ov, "vae_decode: the activation budget is smaller than one decode window (raise ACE355_VAE_BUDGET_MB)");
-            tc = (tc / 8) * 8;  // (whole 8-frame groups: window starts stay 16-byte aligned in the latent rows)
-            // several items per window when they fit
-            const size_t per_win = decode_bytes(h, 1, std::min<long>(T, tc + 2L * ov));
-            nb = (int)std::max<size_t>(1, std::min<size_t>(B, budget / per_win));
+    if (tapped && (rc = tap_copy(h, enc, p.stages[0], 0, in, B, s))) return rc;
+    auto unit = [&](int block, int j) -> const ResUnitW& { return enc ? h->e_blocks[block].ru[j] : h->blocks[block].ru[j]; };
+    auto buf = [&](int role) -> bf16_t* {
+        return role == ACE355_VAE_BUF_NONE ? nullptr : role == ACE355_VAE_BUF_IN ? const_cast<bf16_t*>(in) : role == ACE355_VAE_BUF_OUT ? (bf16_t*)out : h->buf[role];
+    };
+    for (const VaeStep& st : p.steps) {
+        auto snake = [&](int which, int block) -> const SnakeP* {
+            switch (which) {
+                case ACE355_VAE_SNAKE_UNIT_S1: return &unit(block, st.unit).s1;
+                case ACE355_VAE_SNAKE_UNIT_S2: return &unit(block, st.unit).s2;
+                case ACE355_VAE_SNAKE_BLOCK: return enc ? &h->e_blocks[block].s1 : &h->blocks[block].s1;   // (encoder: tiled `stride` times)
+                case ACE355_VAE_SNAKE_FINAL: return enc ? &h->e_s_out : &h->s_out;
+                default: return nullptr;
+            }
+        };
+        const ConvW* W = nullptr;
+        switch (st.weight) {
+            case ACE355_VAE_W_CONV_IN: W = enc ? &h->e_conv1 : &h->conv1; break;
+            case ACE355_VAE_W_CONVT: W = &h->blocks[st.block].ct; break;
+            case ACE355_VAE_W_UNIT_C1: W = &unit(st.block, st.unit).c1; break;
+            case ACE355_VAE_W_UNIT_C2: W = &unit(st.block, st.unit).c2; break;
+            case ACE355_VAE_W_DOWN: W = &h->e_blocks[st.block].cd; break;
+            case ACE355_VAE_W_OUT: W = &h->conv2; break;
+            default: W = &h->e_conv2; break;
         }
+        ConvArgs a{};
+        a.x = buf(st.src) + st.src_off; a.x_batch_stride = st.x_batch_stride; a.L_in = st.L_in; a.Cin = st.Cin;
+        a.x_shift = st.x_shift; a.x_valid = st.x_valid;
+        a.w = W->w; a.bias = W->bias;
+        if (const SnakeP* sp = snake(st.in_snake, st.in_snake_block)) a.alpha = sp->ea, a.beta = sp->ib;
+        if (const SnakeP* sp = snake(st.out_snake, st.out_snake_block)) a.osnake_a = sp->ea, a.osnake_b = sp->ib;
+        if (st.fused) {
+            const ResUnitW& R = unit(st.block, st.unit);
+            a.w2 = R.c2.w; a.bias2 = R.c2.bias; a.alpha2 = R.s2.ea; a.beta2 = R.s2.ib;
+        }
+        a.res = buf(st.res); a.res_batch_stride = st.res_batch_stride;
+        a.y = buf(st.dst); a.y_batch_stride = st.y_batch_stride;
+        a.B = B; a.M = st.M; a.N = st.N; a.taps = st.taps; a.dil = st.dil; a.center = st.center;
+        a.y_shift = st.y_shift; a.y_valid = st.y_valid; a.out_mode = st.out_mode; a.n_real = st.n_real;
+        a.ncl_ld = st.ncl_ld; a.ncl_off = st.ncl_off; a.ncl_m_lo = st.ncl_m_lo; a.ncl_m_hi = st.ncl_m_hi;
+        if ((rc = run_conv(h, a, s))) return rc;
+        if (tapped && st.stage >= 0 && (rc = tap_copy(h, enc, st.stage_info, st.stage, a.y, B, s))) return rc;
     }
-    *nb_out = nb; *tc_out = tc; *ov_out = ov;
     return 0;
 }
 
@@ -784,16 +557,16 @@ int ace355_vae_decode(ace355_vae* h, const float* z_dev, int B, int T, float* wa
     ACE_CHECK(B > 0 && T > 0, "vae_decode: empty problem");
     ACE_CHECK((long)T * h->hop < (1L << 31), "vae_decode: sequence too long (2^31 samples per item)");
     hipStream_t s = (hipStream_t)stream;
-    const ace355_vae_config& c = h->cfg;
+    const VaeShape& sh = h->shape;
     size_t budget = h->decode_budget;
-    int nb = B, tc = T, ov = 0;
+    VaeWindowPlan wp;
     // allocation with the reference's out-of-memory policy (H/vae_decode_chunks.py:40-81 retries smaller instead of failing):
     // a refused hipMalloc halves the budget and re-plans, down to one minimal window
     for (int attempt = 0;; ++attempt) {
-        int rc = decode_plan(h, B, T, budget, &nb, &tc, &ov);
-        if (rc) return rc;
-        const long win = std::min<long>(T, tc == T ? T : tc + 2L * ov);
-        const size_t need_elems = decode_elems(h, win) * (size_t)nb;
+        wp = plan_vae_windows(sh, B, T, budget, h->decode_overlap);
+        ACE_CHECK(!wp.error, wp.error);
+        const long win = vae_window_frames(wp, T);
+        const size_t need_elems = vae_decode_elems(sh, win) * (size_t)wp.nb;
         if (need_elems <= h->buf_elems) break;
         ACE_HIP(hipStreamSynchronize(s));
         bool ok = true;
@@ -806,13 +579,13 @@ int ace355_vae_decode(ace355_vae* h, const float* z_dev, int B, int T, float* wa
         if (ok) { h->buf_elems = need_elems; break; }
         (void)hipGetLastError();
         for (int i = 0; i < 3; ++i) { if (h->buf[i]) hipFree(h->buf[i]); h->buf[i] = nullptr; }
-        budget = std::min(budget, decode_bytes(h, nb, win)) / 2;
-        if (attempt >= 12 || budget < decode_bytes(h, 1, 3L * ov + 8)) {
+        budget = std::min(budget, vae_decode_bytes(sh, wp.nb, win)) / 2;
+        if (attempt >= 12 || budget < vae_decode_bytes(sh, 1, 3L * wp.ov + 8)) {
             set_error("vae_decode: out of device memory even for one minimal decode window");
             return ACE355_ERR_HIP;
         }
     }
-    const size_t zel = (size_t)B * T * c.decoder_input_channels;
+    const size_t zel = (size_t)B * T * sh.zc;
     if (zel > h->zin_elems) {
         ACE_HIP(hipStreamSynchronize(s));
         if (h->zin) hipFree(h->zin);
@@ -820,20 +593,18 @@ int ace355_vae_decode(ace355_vae* h, const float* z_dev, int B, int T, float* wa
         ACE_HIP(hipMalloc((void**)&h->zin, zel * 2 + 256));
         h->zin_elems = zel;
     }
-    int rc = tap_begin(h, 0, T, nb == B && tc == T);
+    int rc = tap_begin(h, 0, wp.nb == B && wp.tc == T);
     if (rc) return rc;
-    if ((rc = launch_ncl_to_nlc(z_dev, h->zin, B, c.decoder_input_channels, T, s))) return rc;
-    if ((rc = tap_stage(h, 0, ACE355_VAE_STAGE_INPUT, h->zin, B, s))) return rc;
-    h->last_plan[0] = nb; h->last_plan[1] = tc; h->last_plan[2] = ov;
-    for (int b0 = 0; b0 < B; b0 += nb) {
-        const int nbw = std::min(nb, B - b0);
-        for (int cs = 0; cs < T; cs += tc) {
-            const int ce = std::min(T, cs + tc);
-            const int ws = tc == T ? 0 : std::max(0, cs - ov), we = tc == T ? T : std::min(T, ce + ov);
-            if ((rc = decode_window(h, b0, nbw, T, ws, we, cs, ce, wav_out_dev, s))) return rc;
+    if ((rc = launch_ncl_to_nlc(z_dev, h->zin, B, sh.zc, T, s))) return rc;
+    h->last_plan[0] = wp.nb; h->last_plan[1] = wp.tc; h->last_plan[2] = wp.ov;
+    for (int b0 = 0; b0 < B; b0 += wp.nb) {
+        const int nbw = std::min(wp.nb, B - b0);
+        for (int cs = 0; cs < T; cs += wp.tc) {
+            const VaePlan p = plan_vae(sh, false, nbw, T, vae_window_at(wp, T, cs), conv_knobs());
+            if ((rc = run_plan(h, 0, p, nbw, h->zin + (size_t)b0 * T * sh.zc, wav_out_dev + (size_t)b0 * sh.audio * sh.hop * T, s))) return rc;
         }
     }
-    return tap_end(h);
+    return ACE355_OK;
 }
 
 int ace355_vae_set_decode_budget(ace355_vae* h, int64_t bytes, int overlap_frames) {
@@ -841,7 +612,7 @@ int ace355_vae_set_decode_budget(ace355_vae* h, int64_t bytes, int overlap_frame
     ACE_CHECK(bytes >= 0 && overlap_frames >= 0, "vae_set_decode_budget: negative argument");
     if (bytes > 0) h->decode_budget = (size_t)bytes;
     if (overlap_frames > 0) {
-        ACE_CHECK(overlap_frames >= decode_receptive_frames(h) && overlap_frames % 8 == 0,
+        ACE_CHECK(overlap_frames >= vae_receptive_frames(h->shape) && overlap_frames % 8 == 0,
                   "vae_set_decode_budget: the overlap must cover the receptive field and be a multiple of 8 frames");
         h->decode_overlap = overlap_frames;
     }
@@ -852,54 +623,21 @@ int ace355_vae_decode_plan(ace355_vae* h, int B, int T, int32_t* items_per_windo
                            int64_t* activation_bytes) {
     ACE_CHECK(h && B > 0 && T > 0, "vae_decode_plan: bad argument");
     if (!h->finalized) { set_error("vae_decode_plan: call ace355_vae_finalize first"); return ACE355_ERR_STATE; }
-    int nb, tc, ov;
-    int rc = decode_plan(h, B, T, h->decode_budget, &nb, &tc, &ov);
-    if (rc) return rc;
-    if (items_per_window) *items_per_window = nb;
-    if (core_frames) *core_frames = tc;
-    if (overlap_frames) *overlap_frames = ov;
-    if (activation_bytes) *activation_bytes = (int64_t)decode_bytes(h, nb, std::min<long>(T, tc == T ? T : tc + 2L * ov));
+    const VaeWindowPlan wp = plan_vae_windows(h->shape, B, T, h->decode_budget, h->decode_overlap);
+    ACE_CHECK(!wp.error, wp.error);
+    if (items_per_window) *items_per_window = wp.nb;
+    if (core_frames) *core_frames = wp.tc;
+    if (overlap_frames) *overlap_frames = wp.ov;
+    if (activation_bytes) *activation_bytes = (int64_t)vae_decode_bytes(h->shape, wp.nb, vae_window_frames(wp, T));
     return ACE355_OK;
 }
 
-static int encode_group(ace355_vae* h, const float* audio_dev, const float* noise_dev, int B, int64_t L, float* latents_out_dev, hipStream_t s);
-
-int ace355_vae_encode(ace355_vae* h, const float* audio_dev, const float* noise_dev, int B, int64_t L, float* latents_out_dev,
-                      void* stream) {
-    ACE_CHECK(h && audio_dev && latents_out_dev, "vae_encode: null argument");
-    if (!h->finalized) { set_error("vae_encode: call ace355_vae_finalize first"); return ACE355_ERR_STATE; }
-    if (!h->has_encoder) { set_error("vae_encode: no encoder.* tensors were loaded"); return ACE355_ERR_STATE; }
-    ACE_CHECK(B > 0 && L > 0 && L < (1L << 30), "vae_encode: sizes");
-    // same activation budget as the decode (ace355_vae_set_decode_budget): above it the batch is encoded in groups of items (exact:
-    // items are independent; the reference's 30 s / 2 s-overlap encode tiling, H/vae_encode.py:47-86, is the same kind of memory bound)
-    const ace355_vae_config& c = h->cfg;
-    const int EH = 2 * c.decoder_input_channels, Z = c.decoder_input_channels;
-    const size_t per_item = (size_t)L * EH * 2 * 3 + (size_t)L * 64 * 2;
-    int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, h->decode_budget / std::max<size_t>(per_item, 1)));
-    long T = L;
-    for (const EncBlockW& Bk : h->e_blocks) T = (T + 2 * Bk.pad - 2 * Bk.stride) / Bk.stride + 1;
-    ACE_CHECK(T > 0, "vae_encode: audio shorter than one latent frame");
-    int rct = tap_begin(h, 1, L, nb == B);
-    if (rct) return rct;
-    for (int b0 = 0; b0 < B; b0 += nb) {
-        const int n = std::min(nb, B - b0);
-        int rc = encode_group(h, audio_dev + (size_t)b0 * c.audio_channels * L, noise_dev ? noise_dev + (size_t)b0 * Z * T : nullptr, n, L,
-                              latents_out_dev + (size_t)b0 * Z * T, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return tap_end(h);
-}
-
-static int encode_group(ace355_vae* h, const float* audio_dev, const float* noise_dev, int B, int64_t L, float* latents_out_dev, hipStream_t s) {
-    const ace355_vae_config& c = h->cfg;
-    const int EH = 2 * c.decoder_input_channels, Z = c.decoder_input_channels;
-    // stage lengths: Conv1d(k = 2s, stride s, pad ceil(s/2)): L_out = floor((L + 2 pad - 2 s) / s) + 1
-    long T = L;
-    for (const EncBlockW& Bk : h->e_blocks) {
-        T = (T + 2 * Bk.pad - 2 * Bk.stride) / Bk.stride + 1;
-        ACE_CHECK(T > 0, "vae_encode: audio shorter than one latent frame");
-    }
-    const size_t need_elems = (size_t)B * L * EH;
+// One group of items of an encode: im2col, the plan's steps, the Gaussian head
+static int encode_group(ace355_vae* h, const float* audio_dev, const float* noise_dev, int B, int64_t L, const VaePlan& p, float* latents_out_dev,
+                        hipStream_t s) {
+    const VaeShape& sh = h->shape;
+    const long T = p.out_len;
+    const size_t need_elems = (size_t)B * p.slot_elems;
     if (need_elems > h->buf_elems) {
         ACE_HIP(hipStreamSynchronize(s));
         for (int i = 0; i < 3; ++i) {
@@ -916,93 +654,70 @@ static int encode_group(ace355_vae* h, const float* audio_dev, const float* nois
         ACE_HIP(hipMalloc((void**)&h->ain, ael * 2 + 256));
         h->ain_elems = ael;
     }
-    const size_t hel = (size_t)B * EH * T;
+    const size_t hel = (size_t)B * sh.eh * T;
     if (hel > h->e_head_elems) {
         ACE_HIP(hipStreamSynchronize(s));
         if (h->e_head) hipFree(h->e_head);
         ACE_HIP(hipMalloc((void**)&h->e_head, hel * 4 + 256));
         h->e_head_elems = hel;
     }
-    hipLaunchKernelGGL(audio_im2col_kernel, dim3((unsigned)((ael + 255) / 256)), dim3(256), 0, s, audio_dev, h->ain, c.audio_channels, (long)L, 7,
-                       (long)ael);
+    hipLaunchKernelGGL(audio_im2col_kernel, dim3((unsigned)((ael + 255) / 256)), dim3(256), 0, s, audio_dev, h->ain, sh.audio, (long)L, 7, (long)ael);
     ACE_LAUNCH_CHECK();
+    int rc = run_plan(h, 1, p, B, h->ain, h->e_head, s);
+    if (rc) return rc;
+    const long total = (long)B * sh.zc * T;
+    hipLaunchKernelGGL(gaussian_head_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->e_head, noise_dev, latents_out_dev, sh.zc, T, total);
+    ACE_LAUNCH_CHECK();
+    return ACE355_OK;
+}
 
-    bf16_t *cur = h->buf[0], *nxt = h->buf[1], *tmp = h->buf[2];
-    int rc;
-    if ((rc = tap_stage(h, 1, ACE355_VAE_STAGE_INPUT, h->ain, B, s))) return rc;
-    ConvArgs a{};
-    // conv1 (k7 over the audio channels, vae_model.py:166) as one tap over the im2col'ed rows
-    a.x = h->ain; a.x_batch_stride = L * 64; a.L_in = (int)L; a.Cin = 64;
-    a.w = h->e_conv1.w; a.bias = h->e_conv1.bias;
-    a.y = cur; a.y_batch_stride = L * EH;
-    a.B = B; a.M = (int)L; a.N = EH; a.taps = 1; a.dil = 1; a.center = 0;
-    a.y_shift = 0; a.y_valid = L * EH; a.out_mode = 0;
-    if ((rc = run_conv(h, a, s))) return rc;
-    if ((rc = tap_stage(h, 1, ACE355_VAE_STAGE_CONV_IN, cur, B, s))) return rc;
-    long Lc = L;
-    const bool epi = episnake_on() != 0;   // (run_res_unit: the Snakes with one reader move to their producers, as in the decoder)
-    for (size_t bi = 0; bi < h->e_blocks.size(); ++bi) {
-        const EncBlockW& Bk = h->e_blocks[bi];
-        for (int j = 0; j < 3; ++j)   // (s1 is tiled `stride` times: its first cin entries are the per-channel parameters)
-            if ((rc = run_res_unit(h, Bk.ru[j], cur, tmp, B, Lc, Bk.cin, s, 1, (epi && j == 2) ? &Bk.s1 : nullptr))) return rc;
-        // snake -> Conv1d(k = 2s, stride s) as 2 taps over the shifted view x'[r][c'] = x_flat[(r*s - pad)*cin + c'] (vae_model.py:113-115)
-        const long Lo = (Lc + 2 * Bk.pad - 2 * Bk.stride) / Bk.stride + 1;
-        a = ConvArgs{};
-        a.x = cur; a.x_batch_stride = Lc * Bk.cin; a.L_in = (int)Lo + 1; a.Cin = Bk.stride * Bk.cin;
-        a.x_shift = -(long)Bk.pad * Bk.cin; a.x_valid = Lc * Bk.cin;
-        a.w = Bk.cd.w; a.bias = Bk.cd.bias;
-        if (!epi) a.alpha = Bk.s1.ea, a.beta = Bk.s1.ib;
-        if (epi && bi + 1 == h->e_blocks.size()) a.osnake_a = h->e_s_out.ea, a.osnake_b = h->e_s_out.ib;   // read by conv2 only
-        a.y = nxt; a.y_batch_stride = Lo * Bk.cout;
-        a.B = B; a.M = (int)Lo; a.N = Bk.cout; a.taps = 2; a.dil = 1; a.center = 0;
-        a.y_shift = 0; a.y_valid = Lo * Bk.cout; a.out_mode = 0;
-        if ((rc = run_conv(h, a, s))) return rc;
-        if ((rc = tap_stage(h, 1, ACE355_VAE_STAGE_DOWN, nxt, B, s))) return rc;
-        std::swap(cur, nxt);
-        Lc = Lo;
+int ace355_vae_encode(ace355_vae* h, const float* audio_dev, const float* noise_dev, int B, int64_t L, float* latents_out_dev,
+                      void* stream) {
+    ACE_CHECK(h && audio_dev && latents_out_dev, "vae_encode: null argument");
+    if (!h->finalized) { set_error("vae_encode: call ace355_vae_finalize first"); return ACE355_ERR_STATE; }
+    if (!h->has_encoder) { set_error("vae_encode: no encoder.* tensors were loaded"); return ACE355_ERR_STATE; }
+    ACE_CHECK(B > 0 && L > 0 && L < (1L << 30), "vae_encode: sizes");
+    // same activation budget as the decode (ace355_vae_set_decode_budget): above it the batch is encoded in groups of items (exact:
+    // items are independent; the reference's 30 s / 2 s-overlap encode tiling, H/vae_encode.py:47-86, is the same kind of memory bound)
+    const VaeShape& sh = h->shape;
+    const long T = vae_latent_frames(sh, L);
+    ACE_CHECK(T > 0, "vae_encode: audio shorter than one latent frame");
+    const long slot_elems = plan_vae(sh, true, 1, L, VaeWindow{}, conv_knobs()).slot_elems;
+    const int nb = vae_encode_group(B, L, slot_elems, h->decode_budget);
+    int rc = tap_begin(h, 1, nb == B);
+    if (rc) return rc;
+    for (int b0 = 0; b0 < B; b0 += nb) {
+        const int n = std::min(nb, B - b0);
+        rc = encode_group(h, audio_dev + (size_t)b0 * sh.audio * L, noise_dev ? noise_dev + (size_t)b0 * sh.zc * T : nullptr, n, L,
+                          plan_vae(sh, true, n, L, VaeWindow{}, conv_knobs()), latents_out_dev + (size_t)b0 * sh.zc * T, (hipStream_t)stream);
+        if (rc) return rc;
     }
-    // snake -> conv k3 -> f32 [B][2Z][T] (vae_model.py:185-186), then the diagonal Gaussian head (:296-302)
-    const int Cl = h->e_conv2.Cin;
-    a = ConvArgs{};
-    a.x = cur; a.x_batch_stride = Lc * Cl; a.L_in = (int)Lc; a.Cin = Cl;
-    a.w = h->e_conv2.w; a.bias = h->e_conv2.bias;
-    if (!epi || h->e_blocks.empty()) a.alpha = h->e_s_out.ea, a.beta = h->e_s_out.ib;
-    a.y = h->e_head; a.y_batch_stride = (long)EH * Lc;
-    a.B = B; a.M = (int)Lc; a.N = EH; a.taps = 3; a.dil = 1; a.center = 1;
-    a.out_mode = 1; a.n_real = EH;
-    if ((rc = run_conv(h, a, s))) return rc;
-    if ((rc = tap_stage(h, 1, ACE355_VAE_STAGE_HEAD, h->e_head, B, s))) return rc;
-    const long total = (long)B * Z * Lc;
-    hipLaunchKernelGGL(gaussian_head_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->e_head, noise_dev, latents_out_dev, Z, Lc, total);
-    ACE_LAUNCH_CHECK();
     return ACE355_OK;
 }
 
 int ace355_vae_latent_frames(const ace355_vae* h, int64_t L) {
     if (!h || !h->finalized || !h->has_encoder || L <= 0) return -1;
-    long T = L;
-    for (const EncBlockW& Bk : h->e_blocks) {
-        T = (T + 2 * Bk.pad - 2 * Bk.stride) / Bk.stride + 1;
-        if (T <= 0) return -1;
-    }
-    return (int)T;
+    return (int)vae_latent_frames(h->shape, L);
+}
+
+// The public stages are the plan's: of one whole-sequence window
+static VaePlan stage_plan(const ace355_vae* h, int enc, long T) {
+    return plan_vae(h->shape, enc != 0, 1, T, VaeWindow{0, (int)T, 0, (int)T}, conv_knobs());
 }
 
 int ace355_vae_num_stages(const ace355_vae* h, int encoder) {
     if (!h || !h->finalized || (encoder && !h->has_encoder)) return -1;
-    std::vector<ace355_vae_stage_info> v;
-    if (stage_list(h, encoder != 0, encoder ? (long)h->hop * 4 : 4, v)) return -1;   // (the count does not depend on the length)
-    return (int)v.size();
+    const VaePlan p = stage_plan(h, encoder, encoder ? (long)h->hop * 4 : 4);   // (the count does not depend on the length)
+    return p.error ? -1 : (int)p.stages.size();
 }
 
 int ace355_vae_get_stage(const ace355_vae* h, int encoder, int stage, int64_t T, ace355_vae_stage_info* out) {
     ACE_CHECK(h && out && T > 0, "vae_get_stage: bad argument");
     if (!h->finalized || (encoder && !h->has_encoder)) { set_error("vae_get_stage: not finalized, or no encoder.* tensors were loaded"); return ACE355_ERR_STATE; }
-    std::vector<ace355_vae_stage_info> v;
-    int rc = stage_list(h, encoder != 0, (long)T, v);
-    if (rc) return rc;
-    ACE_CHECK(stage >= 0 && stage < (int)v.size(), "vae_get_stage: no such stage");
-    *out = v[stage];
+    const VaePlan p = stage_plan(h, encoder, (long)T);
+    ACE_CHECK(!p.error, "vae stages: audio shorter than one latent frame");
+    ACE_CHECK(stage >= 0 && stage < (int)p.stages.size(), "vae_get_stage: no such stage");
+    *out = p.stages[stage];
     return ACE355_OK;
 }
 

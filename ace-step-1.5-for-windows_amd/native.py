@@ -109,6 +109,32 @@ ATTN_KERNELS = ("attn3", "gqa", "rot")   # ACE355_ATTN_KERNEL_*
 ATTN_HOOK_PART_FLOATS = 16 << 20         # the split-KV scratch ace355_attention / ace355_attention_masked lend (csrc/api.hip)
 
 
+class ConvRequestC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "M", "N", "Cin", "taps", "in_snake", "x_view", "res", "fused", "reserved")]
+
+
+class ConvPlanInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("bn", "tm", "ws", "grid_x", "grid_y", "grid_z", "threads", "ras_tm", "ras_tn", "reserved")]
+
+
+class VaeStepInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "weight", "block", "unit", "fused", "in_snake", "in_snake_block", "out_snake", "out_snake_block", "src", "dst", "res", "Cin", "N", "taps",
+        "dil", "center", "L_in", "M", "out_mode", "n_real", "ncl_m_lo", "ncl_m_hi", "stage", "reserved")] + [(n, C.c_int64) for n in (
+        "src_off", "x_batch_stride", "x_shift", "x_valid", "res_batch_stride", "y_batch_stride", "y_shift", "y_valid", "ncl_ld", "ncl_off")] + [
+        ("stage_info", VaeStageInfoC), ("plan", ConvPlanInfoC)]
+
+
+class VaePlanInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("items_per_window", "core_frames", "overlap_frames", "n_steps", "n_stages", "reserved")] + [
+        (n, C.c_int64) for n in ("window_len", "out_len", "slot_elems", "activation_bytes")]
+
+
+# ACE355_VAE_W_* / ACE355_VAE_SNAKE_* / ACE355_VAE_BUF_* of include/ace355.h, by name
+VAE_WEIGHTS = ("conv_in", "convt", "unit_c1", "unit_c2", "down", "out", "head")
+VAE_SNAKES = (None, "unit_s1", "unit_s2", "block", "final")
+VAE_BUFS = {-1: None, 0: "slot0", 1: "slot1", 2: "slot2", 3: "in", 4: "out"}
+
 # ACE355_VAE_STAGE_* / ACE355_VAE_FLAG_* of include/ace355.h
 VAE_STAGE_INPUT, VAE_STAGE_CONV_IN, VAE_STAGE_CONVT, VAE_STAGE_UNIT, VAE_STAGE_UNIT_K7, VAE_STAGE_UNIT_K1, VAE_STAGE_DOWN, VAE_STAGE_HEAD = range(8)
 VAE_FLAG_IN_SNAKE, VAE_FLAG_OUT_SNAKE, VAE_FLAG_FUSED, VAE_FLAG_F32_NCL = 1, 2, 4, 8
@@ -202,6 +228,9 @@ SIGNATURES = {
     "ace355_gemm_set_k_rotation": (C.c_int, [C.c_int]),
     "ace355_gemm_plan": (C.c_int, [C.POINTER(GemmRequestC), C.POINTER(GemmPlanInfoC)]),
     "ace355_attn_plan": (C.c_int, [C.POINTER(AttnRequestC), C.POINTER(AttnPlanInfoC)]),
+    "ace355_conv_plan": (C.c_int, [C.POINTER(ConvRequestC), C.POINTER(ConvPlanInfoC)]),
+    "ace355_vae_plan": (C.c_int, [C.POINTER(VaeConfigC), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.POINTER(VaeStepInfoC), C.c_int,
+                                  C.POINTER(C.c_int32), C.POINTER(VaePlanInfoC)]),
     "ace355_adapter_plan": (C.c_int, [C.POINTER(DitConfigC), C.POINTER(LoraTermC), C.c_int, C.POINTER(KronTermC), C.c_int,
                                       C.POINTER(DoraTermC), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(AdapterPlanRowsC),
                                       C.POINTER(AdapterPlanInfoC)]),
@@ -363,6 +392,41 @@ def attn_plan(N: int, Sq: int, Skv: int, Hq: int, Hkv: int, window: int = -1, **
     out = AttnPlanInfoC()
     check(lib().ace355_attn_plan(C.byref(rq), C.byref(out)), "attn_plan")
     return {**{n: int(getattr(out, n)) for n, _t in AttnPlanInfoC._fields_}, "kernel": ATTN_KERNELS[out.kernel]}
+
+
+def conv_plan(B: int, M: int, N: int, Cin: int, taps: int, **bits) -> dict:
+    """`ace355_conv_plan` (include/ace355.h): the conv_kernel instantiation and grid a conv launch would get, as a dict of the plan's
+    fields.  ``bits``: in_snake, x_view, res, fused (0 when left out)."""
+    rq = ConvRequestC(B=B, M=M, N=N, Cin=Cin, taps=taps)
+    for k, v in bits.items():
+        assert hasattr(rq, k), k
+        setattr(rq, k, int(v))
+    out = ConvPlanInfoC()
+    check(lib().ace355_conv_plan(C.byref(rq), C.byref(out)), "conv_plan")
+    return {n: int(getattr(out, n)) for n, _t in ConvPlanInfoC._fields_ if n != "reserved"}
+
+
+def vae_plan(cfg, encoder: bool, B: int, T: int, budget_bytes: int = 0, overlap_frames: int = 0) -> dict:
+    """`ace355_vae_plan` (include/ace355.h): the conv launches of the first window of a decode of (B, T latent frames) / the first group
+    of an encode of (B, T samples) on configuration ``cfg`` (a config.VaeConfig), in launch order, with weights, Snakes and buffers by
+    name, each step's public stage (or None) and its conv plan; plus the window plan and the buffer size.  No GPU, no handle."""
+    ups, cm = list(cfg.upsampling_ratios), list(cfg.channel_multiples)
+    c = VaeConfigC(cfg.decoder_channels, cfg.decoder_input_channels, cfg.audio_channels, len(ups), (C.c_int32 * MAX_BLOCKS)(*cm),
+                   (C.c_int32 * MAX_BLOCKS)(*ups))
+    cap = 2 + 7 * MAX_BLOCKS
+    steps, n, info = (VaeStepInfoC * cap)(), C.c_int32(), VaePlanInfoC()
+    check(lib().ace355_vae_plan(C.byref(c), 1 if encoder else 0, B, T, budget_bytes, overlap_frames, steps, cap, C.byref(n), C.byref(info)), "vae_plan")
+    assert n.value <= cap
+    out = {k: int(getattr(info, k)) for k, _t in VaePlanInfoC._fields_ if k != "reserved"}
+    out["steps"] = []
+    for st in steps[:n.value]:
+        r = {k: int(getattr(st, k)) for k, t in VaeStepInfoC._fields_ if t in (C.c_int32, C.c_int64) and k != "reserved"}
+        r.update(weight=VAE_WEIGHTS[st.weight], in_snake=VAE_SNAKES[st.in_snake], out_snake=VAE_SNAKES[st.out_snake],
+                 src=VAE_BUFS[st.src], dst=VAE_BUFS[st.dst], res=VAE_BUFS[st.res],
+                 stage_info={k: int(getattr(st.stage_info, k)) for k, _t in VaeStageInfoC._fields_} if st.stage >= 0 else None,
+                 plan={k: int(getattr(st.plan, k)) for k, _t in ConvPlanInfoC._fields_ if k != "reserved"})
+        out["steps"].append(r)
+    return out
 
 
 def _rows(arr, n):

@@ -111,6 +111,23 @@ typedef struct ace355_attn_plan_info {
     int32_t mx_out_ok;                           /* the kernel of this request can write MXFP8 */
 } ace355_attn_plan_info;
 int ace355_attn_plan(const ace355_attn_request* request, ace355_attn_plan_info* plan_out);
+/* The same for the conv launches of the VAE (and ace355_conv1d_nlc): which instantiation of conv_kernel and which grid a request gets
+ * under the process's ACE355_CONV_* switches.  The structs are the library's ConvRequest / ConvPlan (csrc/vae_plan.h), described there. */
+typedef struct ace355_conv_request {
+    int32_t B, M, N, Cin, taps;
+    int32_t in_snake;       /* the launch applies a Snake while staging its input */
+    int32_t x_view;         /* the input is the shifted flat view of a strided conv */
+    int32_t res;            /* a residual is added */
+    int32_t fused;          /* one-launch residual unit (the k = 1 conv inside the launch) */
+    int32_t reserved;
+} ace355_conv_request;
+typedef struct ace355_conv_plan_info {
+    int32_t bn, tm, ws;                          /* conv_kernel<bn = 32 | 128, tm = 128 | 256, ws = 0 | 1> */
+    int32_t grid_x, grid_y, grid_z, threads;
+    int32_t ras_tm, ras_tn;                      /* XCD-aware rasterisation of a (ras_tm x ras_tn) tile grid, 0: the plain grid */
+    int32_t reserved;
+} ace355_conv_plan_info;
+int ace355_conv_plan(const ace355_conv_request* request, ace355_conv_plan_info* plan_out);
 
 /* ------------------------------------------------------------------------------------------
  * DiT decoder (AceStepDiTModel, base.py:1240-1507) + sampler (generate_audio, base.py:1783-1989)
@@ -497,7 +514,9 @@ int ace355_vae_get_profile(ace355_vae* h, double* conv_ms, double* conv_flops, i
  * before the Gaussian arithmetic).  A residual unit that runs as ONE launch is one stage (UNIT); one that runs as two launches is two
  * (UNIT_K7: the k = 7 result as stored for the k = 1 conv, UNIT_K1: the unit's output), so every stage but INPUT is the output of exactly
  * one conv launch.  Which form a unit takes, and where the Snakes are applied, depends on the width and on the A/B switches of the process
- * (ACE355_CONV_FUSE_RU, ACE355_VAE_EPISNAKE): the flags below say it, so a test never hard-codes the rounding points. */
+ * (ACE355_CONV_FUSE_RU, ACE355_VAE_EPISNAKE): the flags below say it, so a test never hard-codes the rounding points.
+ * The list is not written down anywhere: it is read off the steps of plan_vae (csrc/vae_plan.h; ace355_vae_plan below), the same steps
+ * the decode and the encode execute, so a stage and its launch cannot disagree. */
 #define ACE355_VAE_STAGE_INPUT 0   /* decoder: bf16(z) as [T][64]; encoder: bf16 im2col rows [L][64], column k * audio_channels + c = audio[c][l + k - 3] */
 #define ACE355_VAE_STAGE_CONV_IN 1 /* decoder.conv1 / encoder.conv1 */
 #define ACE355_VAE_STAGE_CONVT 2   /* decoder.block.{block}.conv_t1 */
@@ -531,6 +550,54 @@ int ace355_vae_get_stage(const ace355_vae* h, int encoder, int stage, int64_t T,
  * window over the whole batch: if the budget splits it, it returns ACE355_ERR_STATE and launches nothing.  Taps only observe: the conv
  * launches and their arguments are those of an untapped call. */
 int ace355_vae_set_tap(ace355_vae* h, int encoder, int stage, void* dst_dev, int64_t capacity_bytes);
+
+/* The conv launches of one decode window or one encode group as data, in launch order: plan_vae of csrc/vae_plan.h, which
+ * ace355_vae_decode / _encode execute step by step.  A step names everything its launch takes except pointers.  No GPU, no handle. */
+#define ACE355_VAE_W_CONV_IN 0  /* decoder.conv1 / encoder.conv1 */
+#define ACE355_VAE_W_CONVT 1    /* decoder.block.{block}.conv_t1 */
+#define ACE355_VAE_W_UNIT_C1 2  /* ...block.{block}.res_unit{unit + 1}.conv1 (fused: + conv2 and snake2 inside the launch) */
+#define ACE355_VAE_W_UNIT_C2 3  /* ...res_unit{unit + 1}.conv2 */
+#define ACE355_VAE_W_DOWN 4     /* encoder.block.{block}.conv1 */
+#define ACE355_VAE_W_OUT 5      /* decoder.conv2 */
+#define ACE355_VAE_W_HEAD 6     /* encoder.conv2 */
+#define ACE355_VAE_SNAKE_NONE 0
+#define ACE355_VAE_SNAKE_UNIT_S1 1 /* block.{snake_block}.res_unit{unit + 1}.snake1 */
+#define ACE355_VAE_SNAKE_UNIT_S2 2 /* ...snake2 */
+#define ACE355_VAE_SNAKE_BLOCK 3   /* block.{snake_block}.snake1 */
+#define ACE355_VAE_SNAKE_FINAL 4   /* decoder.snake1 / encoder.snake1 */
+#define ACE355_VAE_BUF_NONE (-1)
+#define ACE355_VAE_BUF_SLOT0 0     /* 0 .. 2: the three ping-pong activation buffers */
+#define ACE355_VAE_BUF_IN 3        /* the call's input image (bf16 latent rows / im2col'ed audio rows) */
+#define ACE355_VAE_BUF_OUT 4       /* the call's output (the waveform / the encoder head's f32 image) */
+typedef struct ace355_vae_step_info {
+    int32_t weight, block, unit;                   /* ACE355_VAE_W_* and where; -1 outside the blocks / units */
+    int32_t fused;
+    int32_t in_snake, in_snake_block;              /* ACE355_VAE_SNAKE_*: applied while staging the input */
+    int32_t out_snake, out_snake_block;            /* the single reader's Snake, applied by this launch's epilogue */
+    int32_t src, dst, res;                         /* ACE355_VAE_BUF_* */
+    int32_t Cin, N, taps, dil, center, L_in, M;    /* as ConvArgs (csrc/common.h) */
+    int32_t out_mode, n_real, ncl_m_lo, ncl_m_hi;
+    int32_t stage;                                 /* index of the public stage this launch stores, -1: none (the decoder's output conv) */
+    int32_t reserved;
+    int64_t src_off;                               /* elements from the start of the source buffer's first item (a decode window's first row) */
+    int64_t x_batch_stride, x_shift, x_valid, res_batch_stride, y_batch_stride, y_shift, y_valid, ncl_ld, ncl_off;
+    ace355_vae_stage_info stage_info;              /* valid when stage >= 0 */
+    ace355_conv_plan_info plan;
+} ace355_vae_step_info;
+typedef struct ace355_vae_plan_info {
+    int32_t items_per_window, core_frames, overlap_frames;   /* decoder: the window plan; encoder: items per group, 0, 0 */
+    int32_t n_steps, n_stages;
+    int32_t reserved;
+    int64_t window_len;        /* latent frames (decoder) / samples (encoder) per item the steps cover */
+    int64_t out_len;           /* per item: samples the window decodes / latent frames */
+    int64_t slot_elems;        /* bf16 elements per item of each ping-pong buffer: the largest extent a step writes */
+    int64_t activation_bytes;  /* of the buffers the budget counts, for items_per_window items */
+} ace355_vae_plan_info;
+/* The steps of the FIRST window of a decode of (B, T latent frames) or the first group of an encode of (B, T samples) under a budget in
+ * bytes (0: the default of a new handle) and, for the decoder, a window overlap in frames (0: the default).  steps_out may be NULL or
+ * shorter than the plan (capacity): n_out is the plan's step count either way. */
+int ace355_vae_plan(const ace355_vae_config* cfg, int encoder, int B, int64_t T, int64_t budget_bytes, int overlap_frames,
+                    ace355_vae_step_info* steps_out, int capacity, int32_t* n_out, ace355_vae_plan_info* info_out);
 
 /* ------------------------------------------------------------------------------------------
  * Condition encoder: AceStepConditionEncoder.forward, base.py:1509-1554

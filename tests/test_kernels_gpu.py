@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 import _attn_plan_cases as _attn_cases
 import _gemm_plan_cases as _plan_cases
+import _vae_plan_cases as _vae_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -328,18 +329,13 @@ def test_apg_euler(lib, gpu_device, B, T):
     assert torch.equal(avg, avg_before)
 
 
-@pytest.mark.parametrize("B,L,Cin,Cout,taps,dil,snake,res", [
-    (2, 300, 128, 128, 7, 1, True, False), (1, 517, 128, 128, 7, 9, True, False), (2, 200, 256, 256, 7, 3, True, False),
-    (2, 300, 128, 128, 1, 1, True, True), (1, 40, 64, 2048, 7, 1, False, False), (1, 1000, 128, 2, 7, 1, True, False),
-    # wgs128 = 516 * 2 * 4 = 4128, but a residual keeps a launch off the 8-wave form (launch_conv: tall = !w2 && !res && ...): the 4-wave
-    # 128-row tile with a residual, ragged last tile (66000 % 128 = 80)
-    (4, 66000, 256, 256, 7, 3, True, True),
-    # its residual-free twin: wgs128 = 4128 >= 1400 -> the 8-wave conv_kernel<128, 256>, ragged last tile (66000 % 256 = 208)
-    (4, 66000, 256, 256, 7, 3, True, False),
-    # wgs128 = 235 * 4 * 8 = 7520 >= 1400 -> 8-wave, dilation 9 (54 halo rows), 30000 % 256 = 48; and without the Snake (plain staging)
-    (8, 30000, 512, 512, 7, 9, True, False), (8, 30000, 512, 512, 7, 9, False, False)])
+# the rows, each with the launch form it was chosen for: tests/_vae_plan_cases.py CONV1D_ROWS (tests/test_vae_plan_cpu.py pins them on any machine)
+@pytest.mark.parametrize("B,L,Cin,Cout,taps,dil,snake,res", [row for row, _form in _vae_cases.CONV1D_ROWS])
 def test_conv1d_nlc(lib, gpu_device, B, L, Cin, Cout, taps, dil, snake, res):
     from oracle import oobleck as o_vae
+    from ace355 import native
+    row = (B, L, Cin, Cout, taps, dil, snake, res)
+    assert _vae_cases.form(native.conv_plan(**_vae_cases.conv1d_request(row))) == dict(_vae_cases.CONV1D_ROWS)[row], "the row is not on the form it was chosen for"
     g = torch.Generator().manual_seed(L + Cin + taps + dil)
     x = _bf(torch.randn(B, L, Cin, generator=g))
     w = _bf(torch.randn(Cout, Cin, taps, generator=g) / (Cin * taps) ** 0.5)

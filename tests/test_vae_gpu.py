@@ -265,11 +265,21 @@ def test_fused_unit_forms_agree_bit_for_bit(gpu_device):
     present the same K-slot order to the matrix unit (frag_kperm) and must give the SAME BITS.  ACE355_CONV_F8 = 0 / 1 forces one form at
     every size (read once per process: child processes); the full-width config so that the C = 128 units exist."""
     import subprocess, sys, os, tempfile
+    import _vae_plan_cases as plan_cases
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # the shapes below run the one-launch units on the 4-wave form by default: ACE355_CONV_F8=1 is what reaches the other one (each child
+    # asserts the form of ITS process against the step lists it is about to execute)
+    assert plan_cases.FUSED_FORM_CALLS == [(plan_cases.FULL, False, 2, 41), (plan_cases.FULL, True, 1, 12)]
+    for kw, enc, B, fr in plan_cases.FUSED_FORM_CALLS:
+        assert {plan_cases.form(st["plan"]) for st in plan_cases.vae_call(kw, enc, B, fr)["steps"] if st["fused"]} == {"w4"}
     code = (
-        "import sys, torch; sys.path.insert(0, %r)\n"
-        "import ace355\nfrom ace355 import weightgen\nfrom ace355.vae import NativeVae\n"
+        "import os, sys, torch; sys.path.insert(0, %r)\n"
+        "import ace355\nfrom ace355 import native, weightgen\nfrom ace355.vae import NativeVae\n"
         "cfg = ace355.VaeConfig()\n"
+        "want = {'bn': 128, 'tm': 256, 'ws': 1} if os.environ['ACE355_CONV_F8'] == '1' else {'bn': 128, 'tm': 128, 'ws': 0}\n"
+        "for enc, B, T in ((False, 2, 41), (True, 1, cfg.hop * 12)):\n"
+        "    fused = [st['plan'] for st in native.vae_plan(cfg, enc, B, T)['steps'] if st['fused']]\n"
+        "    assert fused and all({k: p[k] for k in want} == want for p in fused), fused\n"
         "w = weightgen.make_vae_weights({**cfg.weight_shapes(), **cfg.encoder_weight_shapes()}, seed=2, mode='test')\n"
         "vae = NativeVae(cfg, 'cuda:0'); vae.load_state_dict(w)\n"
         "z = torch.randn(2, 64, 41, generator=torch.Generator().manual_seed(5))\n"

@@ -5,31 +5,20 @@ product really uses, so the launch forms of ``launch_conv`` that whole decodes o
 
     |got - ref| <= u |ref| + tau absref        (u = 2^-8 bf16 / 2^-23 fp32; tau: _vae_layers.tau_for)
 
-Launch forms per case, re-derived from launch_conv (wgs128 = ceil(M / 128) * ceil(N / 128) * B; 8-wave 256-row tile: k >= 3 convs with
-Cin >= 128 and no residual from wgs128 >= 1400, the one-launch unit from 1400, plain-row transposed convs from 1500; N < 128: the
-32-column tile; rasterisation when there is more than one column tile):
+Which launch form every layer of a case takes is not derived here: tests/_vae_plan_cases.py LAYER_CASES states it per case (with the
+tile counts that put it there), tests/test_vae_plan_cpu.py holds the statement to the library's plan_conv on any machine, and each test
+below asserts it against ``native.vae_plan`` - the step list the decode / encode is about to execute - before it launches.  In short:
 
-  small  B=2 T=37   widths 256 / 128 / 64, ratios 6 / 4 / 2, odd lengths (37, 222, 888, 1776): ragged last tiles everywhere; C = 64 units
-                    and the output conv (N = 2) on the 32-column tile; C = 128 units as one launch on the 4-wave tile; transposed convs
-                    cropped by y_shift / y_valid with M = L + 1; everything else 4-wave (largest wgs128 = 14 * 1 * 2).  Re-run in child
-                    processes with ACE355_VAE_EPISNAKE=0 (every Snake in its reader's staging, an extra rounding of the k = 7 result)
-                    and ACE355_CONV_FUSE_RU=0 (C = 128 units as two launches), so those launches get the same treatment.
-  full   B=1 T=24   widths 2048 ... 128: every 4-wave form (largest wgs128: block 0's transposed conv, 1 * 80 * 1 = 80; k = 7 at C = 1024:
-                    2 * 8 = 16; one-launch units at C = 128: 180 and 360 < 1400 -> 4-wave, snake2 through the LDS image).  Rasterisation
-                    with tiles_m < 8 - the tail-only path - at block 0 (tiles_m = 1 x 80 column tiles, units 2 x 8) and block 1's
-                    transposed conv (2 x 24); full groups of 8 row blocks plus a tail at block 1's units (12 x 4), block 2 (12 x 8,
-                    units 45 x 2) and block 3's transposed conv (46 x 4).
-  full   B=8 T=280  every decoder launch on the form of the 8 x 30 s metric run.  Block 0: transposed conv M = 281 -> 3 * 80 * 8 = 1920
-                    >= 1500: tall; k = 7 at C = 1024, M = 2800 -> 22 * 8 * 8 = 1408 >= 1400: tall (the threshold is T >= 269: 21 row
-                    tiles give 1344).  Block 1: 22 * 24 * 8 = 4224 and 132 * 4 * 8 = 4224; block 2: 132 * 8 * 8 and 525 * 2 * 8; block 3:
-                    526 * 4 * 8, units 2100 * 8 = 16800 >= 1400: the 8-wave one-launch unit (snake2 from the accumulators); block 4:
-                    2101 * 2 * 8, units 4200 * 8.  conv1 (Cin = 64) and the k = 1 convs (residual) stay 4-wave by design; the output conv
-                    is the 32-column tile.  Reference on items 0 and 7 (items are independent: bit-tested in tests/test_vae_gpu.py).
-  enc    B=2 12 frames   L = 23040: im2col'ed first conv, one-launch units at C = 128 (4-wave: 180 * 2 = 360), k = 7 / k = 1 pairs at
-                    C = 256 / 512 / 1024, the strided convs over the shifted flat view (x_shift, x_valid; never tall), the fp32 head.
-  enc    B=4 188 frames  L = 360960: k = 7 at C = 256 (M = 45120 -> 353 * 2 * 4 = 2824) and C = 512 (M = 11280 -> 89 * 4 * 4 = 1424) on
-                    the 8-wave tile, the one-launch units at C = 128 on the 8-wave form (2820 * 4, 1410 * 4); C = 1024 (M = 1880 ->
-                    15 * 8 * 4 = 480) stays 4-wave.  Reference on item 3.
+  small  B=2 T=37   odd lengths (37, 222, 888, 1776): ragged last tiles everywhere; C = 64 units and the output conv (N = 2) on the
+                    32-column tile; C = 128 units as one launch on the 4-wave tile; transposed convs cropped by y_shift / y_valid with
+                    M = L + 1.  Re-run in child processes with ACE355_VAE_EPISNAKE=0 and ACE355_CONV_FUSE_RU=0.
+  full   B=1 T=24   every 4-wave form of the full widths; rasterisation with fewer than 8 row blocks (the tail-only path) and with full
+                    groups of 8 plus a tail.
+  full   B=8 T=280  every decoder launch on the form of the 8 x 30 s metric run (8-wave tiles, the 8-wave one-launch unit).  Reference on
+                    items 0 and 7 (items are independent: bit-tested in tests/test_vae_gpu.py).
+  enc    B=2 12 frames   im2col'ed first conv, one-launch units, k = 7 / k = 1 pairs, the strided convs over the shifted flat view
+                    (x_shift, x_valid; never tall), the fp32 head: all 4-wave.
+  enc    B=4 188 frames  k = 7 at C = 256 / 512 and the one-launch units on the 8-wave forms; C = 1024 stays 4-wave.  Reference on item 3.
 """
 import json
 import os
@@ -40,10 +29,19 @@ import tempfile
 import pytest
 
 import _vae_layers as vl
+import _vae_plan_cases as plan_cases
 
 pytestmark = pytest.mark.gpu
 
-SMALL = dict(decoder_channels=64, channel_multiples=(1, 2, 4), downsampling_ratios=(2, 4, 6))
+SMALL = plan_cases.SMALL
+CLAIMS = {cid: (kw, enc, B, fr, default, special) for cid, kw, enc, B, fr, default, special in plan_cases.LAYER_CASES}
+
+
+def _assert_claimed_forms(cid, cfg_kw, enc, B, frames):
+    """The launches this case is about to make are on the forms tests/_vae_plan_cases.py claims for it."""
+    kw, c_enc, c_B, c_fr, default, special = CLAIMS[cid]
+    assert (kw, c_enc, c_B, c_fr) == (cfg_kw, enc, B, frames), "the case table and this test's parameters differ"
+    plan_cases.assert_forms(plan_cases.vae_call(cfg_kw, enc, B, frames), default, special, cid)
 
 
 def _judge(tag, out, expect_kinds=None):
@@ -67,7 +65,8 @@ def _judge(tag, out, expect_kinds=None):
     (dict(), 1, 24, [0]),
     (dict(), 8, 280, [0, 7]),
 ], ids=["small-B2-T37", "full-B1-T24", "full-B8-T280"])
-def test_decoder_layers(gpu_device, cfg_kw, B, T, items):
+def test_decoder_layers(gpu_device, request, cfg_kw, B, T, items):
+    _assert_claimed_forms(request.node.callspec.id, cfg_kw, False, B, T)
     out = vl.run_case(cfg_kw, False, B, T, items, device=str(gpu_device))
     _judge(f"dec {cfg_kw and 'small' or 'full'} B={B} T={T}", out, [vl.CONV_IN, vl.CONVT, vl.UNIT, vl.UNIT_K7, vl.UNIT_K1])
 
@@ -77,7 +76,8 @@ def test_decoder_layers(gpu_device, cfg_kw, B, T, items):
     (dict(), 2, 12, [0, 1]),
     (dict(), 4, 188, [3]),
 ], ids=["small-B2-23", "full-B2-12", "full-B4-188"])
-def test_encoder_layers(gpu_device, cfg_kw, B, frames, items):
+def test_encoder_layers(gpu_device, request, cfg_kw, B, frames, items):
+    _assert_claimed_forms(request.node.callspec.id, cfg_kw, True, B, frames)
     out = vl.run_case(cfg_kw, True, B, frames, items, device=str(gpu_device))
     _judge(f"enc {cfg_kw and 'small' or 'full'} B={B} frames={frames}", out, [vl.CONV_IN, vl.UNIT, vl.UNIT_K7, vl.UNIT_K1, vl.DOWN, vl.HEAD])
 
