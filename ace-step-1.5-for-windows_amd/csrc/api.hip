@@ -9,6 +9,7 @@
 #include "../../include/ace355.h"
 #include "adapter_plan.h"
 #include "attn_plan.h"
+#include "dit_plan.h"
 #include "vae_plan.h"
 #include "gemm_plan.h"
 #include <dlfcn.h>
@@ -170,6 +171,28 @@ int ace355_vae_plan(const ace355_vae_config* cfg, int encoder, int B, int64_t T,
     for (int i = 0; i < std::min(capacity, info.n_steps); ++i) steps_out[i] = p.steps[i];
     *n_out = info.n_steps;
     *info_out = info;
+    return ACE355_OK;
+}
+
+int ace355_dit_pass_plan(const ace355_dit_config* cfg, const ace355_dit_pass_request* r, ace355_dit_step_info* steps_out, int capacity,
+                         int32_t* n_out, ace355_dit_pass_info* info_out) {
+    ACE_CHECK(cfg && r && n_out && info_out && capacity >= 0 && (steps_out || capacity == 0), "dit_pass_plan: null pointer");
+    ACE_CHECK(cfg->head_dim == 128 && cfg->patch_size == 2 && cfg->hidden_size > 0 && cfg->hidden_size % 64 == 0 && cfg->intermediate_size > 0 &&
+              cfg->intermediate_size % 64 == 0 && cfg->in_channels > 0 && (2 * cfg->in_channels) % 64 == 0 && cfg->num_kv_heads > 0 &&
+              cfg->num_heads > 0 && cfg->num_heads % cfg->num_kv_heads == 0 && cfg->num_layers > 0 && cfg->num_layers <= 64 && cfg->out_channels == 64,
+              "dit_pass_plan: configuration (ace355_dit_create's checks)");
+    ACE_CHECK(r->N > 0 && r->N <= ACE355_MAX_SEQS && r->T > 0 && (r->temb_rows == 1 || r->temb_rows == r->N), "dit_pass_plan: N in [1,64], T > 0, temb_rows 1 or N");
+    ACE_CHECK((long)r->N * ((r->T + 1) / 2) < (1L << 24), "dit_pass_plan: too many token rows");
+    ACE_CHECK(r->map_last < cfg->num_layers && (r->map_last < 0 || r->map_heads[r->map_last] > 0), "dit_pass_plan: map_last names a layer with requested heads");
+    DitPassRequest rq{};
+    static_cast<ace355_dit_pass_request&>(rq) = *r;
+    rq.cfg = *cfg;
+    if (rq.mx_copies < 0) rq.mx_copies = dit_mx_copies(*cfg);
+    const DitPassPlan p = dit_pass_plan_query(rq);
+    ACE_CHECK(!p.error, p.error);
+    for (int i = 0; i < std::min(capacity, p.info.n_steps); ++i) steps_out[i] = p.steps[i];
+    *n_out = p.info.n_steps;
+    *info_out = p.info;
     return ACE355_OK;
 }
 

@@ -56,10 +56,7 @@ class NativeDit(native.Owner):
         self.cfg = cfg
         self.device = torch.device(device)
         self._lib = native.lib()
-        mask = native.sliding_mask(cfg.layer_types, len(cfg.layer_types))
-        c = native.DitConfigC(cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers, cfg.num_attention_heads,
-                              cfg.num_key_value_heads, cfg.head_dim, int(cfg.sliding_window or 0), cfg.patch_size,
-                              cfg.in_channels, cfg.audio_acoustic_hidden_dim, cfg.rms_norm_eps, cfg.rope_theta, mask)
+        c = native.dit_config_c(cfg)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             native.check(self._lib.ace355_dit_create(C.byref(c), C.byref(h)), "dit_create")

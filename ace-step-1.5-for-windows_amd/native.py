@@ -17,6 +17,7 @@ OK = 0
 DTYPE_F32, DTYPE_BF16 = 0, 1
 MAX_BLOCKS = 8
 MAX_SLOTS = 32
+MAX_SEQS = 64
 
 
 class DitConfigC(C.Structure):
@@ -140,6 +141,35 @@ VAE_STAGE_INPUT, VAE_STAGE_CONV_IN, VAE_STAGE_CONVT, VAE_STAGE_UNIT, VAE_STAGE_U
 VAE_FLAG_IN_SNAKE, VAE_FLAG_OUT_SNAKE, VAE_FLAG_FUSED, VAE_FLAG_F32_NCL = 1, 2, 4, 8
 
 
+class DitPassRequestC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("N", "T", "temb_rows")] + [(n, C.c_int32 * MAX_SEQS) for n in ("seq_slot", "seq_L", "seq_broadcast")] + [
+        (n, C.c_int32) for n in ("precision", "mx_min_rows", "mx_copies", "nf_on", "nf_emb_on", "nf_rows", "dup_half", "dedup_on", "prefetch",
+                                 "cu_slots", "graph_mode", "zr_M", "map_last")] + [("map_heads", C.c_int32 * 64)] + [
+        (n, C.c_int32) for n in ("qkv_vt_epilogue", "qkv_vt_epilogue_half", "self_mx_out_ok", "cross_mx_out_ok")] + [
+        ("nf_cap_M", C.c_int64), ("tap_mask", C.c_uint64)]
+
+
+class DitStepInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "kind", "layer", "src", "dst", "M", "seqs", "proj", "path", "N", "K", "lda", "ldw", "ldc", "mode", "rows_per_seq", "bias", "gate", "cvec",
+        "cvec_row0", "hn", "hn_q_cols", "hn_qk_cols", "vt_offered", "nf_split", "nf_gA", "nf_gB", "nf_sqA", "nf_sqB", "nc_rowsq", "nc_bias", "a_wrap",
+        "a_zero_idx", "mxo", "next_proj", "next_layer", "next_M", "next_N", "next_K", "next_mode", "gs", "Sq", "Skv", "window", "mx_out", "Lpad",
+        "n_heads", "pair0", "reserved")] + [("count", C.c_int64), ("flops", C.c_double)]
+
+
+class DitPassInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("S", "M", "Sp", "Nc", "Mc", "n_sc", "L", "Lpad", "fold", "emb", "dedup0", "zero_rows", "n_steps",
+                                         "gemm_launches")] + [("vt_elems", C.c_int64), ("gemm_flops", C.c_double), ("attn_flops", C.c_double)]
+
+
+# ACE355_DIT_STEP_* / _PROJ_* / _PATH_* / _BUF_* of include/ace355.h, by name
+DIT_STEPS = ("mod_gs", "zero_rowsq", "norm_gs", "norm_gs_mx", "norm_w", "norm_w_mx", "gemm", "transpose_v", "attn_self", "attn_cross", "xattn_probs",
+             "tap", "norm_out")
+DIT_PROJS = ("patchify", "qkv", "o", "cross_q", "cross_o", "gate_up", "down", "out")
+DIT_PATHS = ("bf16", "mx_quant", "mx")
+DIT_BUFS = {-1: None, 0: "xin", 1: "h", 2: "xn", 3: "qkv", 4: "ao", 5: "act", 6: "aq", 7: "xq", 8: "vt", 9: "vpad", 10: "slot_kv", 11: "tap", 12: "maps"}
+
+
 class LoraTermC(C.Structure):
     _fields_ = [("name", C.c_char_p), ("A_dev", C.c_void_p), ("B_dev", C.c_void_p), ("rank", C.c_int32), ("scale", C.c_float)]
 
@@ -231,6 +261,8 @@ SIGNATURES = {
     "ace355_conv_plan": (C.c_int, [C.POINTER(ConvRequestC), C.POINTER(ConvPlanInfoC)]),
     "ace355_vae_plan": (C.c_int, [C.POINTER(VaeConfigC), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.POINTER(VaeStepInfoC), C.c_int,
                                   C.POINTER(C.c_int32), C.POINTER(VaePlanInfoC)]),
+    "ace355_dit_pass_plan": (C.c_int, [C.POINTER(DitConfigC), C.POINTER(DitPassRequestC), C.POINTER(DitStepInfoC), C.c_int, C.POINTER(C.c_int32),
+                                       C.POINTER(DitPassInfoC)]),
     "ace355_adapter_plan": (C.c_int, [C.POINTER(DitConfigC), C.POINTER(LoraTermC), C.c_int, C.POINTER(KronTermC), C.c_int,
                                       C.POINTER(DoraTermC), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(AdapterPlanRowsC),
                                       C.POINTER(AdapterPlanInfoC)]),
@@ -425,6 +457,53 @@ def vae_plan(cfg, encoder: bool, B: int, T: int, budget_bytes: int = 0, overlap_
                  src=VAE_BUFS[st.src], dst=VAE_BUFS[st.dst], res=VAE_BUFS[st.res],
                  stage_info={k: int(getattr(st.stage_info, k)) for k, _t in VaeStageInfoC._fields_} if st.stage >= 0 else None,
                  plan={k: int(getattr(st.plan, k)) for k, _t in ConvPlanInfoC._fields_ if k != "reserved"})
+        out["steps"].append(r)
+    return out
+
+
+def dit_config_c(cfg) -> DitConfigC:
+    """A config.DitConfig as the C struct."""
+    return DitConfigC(cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.num_key_value_heads,
+                      cfg.head_dim, int(cfg.sliding_window or 0), cfg.patch_size, cfg.in_channels, cfg.audio_acoustic_hidden_dim,
+                      cfg.rms_norm_eps, cfg.rope_theta, sliding_mask(cfg.layer_types, len(cfg.layer_types)))
+
+
+def dit_pass_plan(cfg, T: int, seqs, **fields) -> dict:
+    """`ace355_dit_pass_plan` (include/ace355.h): the launches of one decoder pass on configuration ``cfg`` (a config.DitConfig) in launch
+    order, as the handle would make them.  ``seqs``: per sequence (condition slot, that slot's key count L, set from one row?).  ``fields``:
+    further ace355_dit_pass_request fields; left out, they are a fresh bf16 handle's plain forward (temb_rows = N, MXFP8 copies as
+    set_precision would make them, dedup and prefetch allowed, no fold, no taps, no maps).  ``map_heads`` is a list per layer.  A refusal
+    raises with forward's text.  Steps: kinds, projections, paths and buffers by name; fields a step kind does not use are dropped."""
+    seqs = list(seqs)
+    rq = DitPassRequestC(N=len(seqs), T=T, temb_rows=len(seqs), mx_min_rows=1536, mx_copies=-1, dedup_on=1, prefetch=1, zr_M=-1, map_last=-1)
+    for i, (slot, L, bc) in enumerate(seqs):
+        rq.seq_slot[i], rq.seq_L[i], rq.seq_broadcast[i] = int(slot), int(L), int(bc)
+    for k, v in fields.items():
+        assert hasattr(rq, k), k
+        if k == "map_heads":
+            for l, n in enumerate(v):
+                rq.map_heads[l] = int(n)
+        else:
+            setattr(rq, k, int(v))
+    c = cfg if isinstance(cfg, DitConfigC) else dit_config_c(cfg)
+    n, info = C.c_int32(), DitPassInfoC()
+    check(lib().ace355_dit_pass_plan(C.byref(c), C.byref(rq), None, 0, C.byref(n), C.byref(info)), "dit_pass_plan")
+    steps = (DitStepInfoC * n.value)()
+    check(lib().ace355_dit_pass_plan(C.byref(c), C.byref(rq), steps, n.value, C.byref(n), C.byref(info)), "dit_pass_plan")
+    out = {k: getattr(info, k) for k, _t in DitPassInfoC._fields_}
+    gemm_only = ("proj", "path", "N", "K", "lda", "ldw", "ldc", "mode", "rows_per_seq", "bias", "gate", "cvec", "cvec_row0", "hn", "hn_q_cols",
+                 "hn_qk_cols", "vt_offered", "nf_split", "nf_gA", "nf_gB", "nf_sqA", "nf_sqB", "nc_rowsq", "nc_bias", "a_wrap", "a_zero_idx", "mxo",
+                 "next_proj", "next_layer", "next_M", "next_N", "next_K", "next_mode")
+    attn_only = ("Sq", "Skv", "window", "mx_out", "Lpad", "n_heads", "pair0")
+    out["steps"] = []
+    for st in steps:
+        kind = DIT_STEPS[st.kind]
+        r = {k: getattr(st, k) for k, _t in DitStepInfoC._fields_ if k != "reserved"}
+        r.update(kind=kind, src=DIT_BUFS[st.src], dst=DIT_BUFS[st.dst])
+        if kind == "gemm":
+            r.update(proj=DIT_PROJS[st.proj], path=DIT_PATHS[st.path], next_proj=DIT_PROJS[st.next_proj] if st.next_proj >= 0 else None)
+        for k in (() if kind == "gemm" else gemm_only) + (() if kind in ("attn_self", "attn_cross", "xattn_probs") else attn_only):
+            del r[k]
         out["steps"].append(r)
     return out
 

@@ -456,6 +456,117 @@ int ace355_dit_set_profile(ace355_dit* h, int enable);
 int ace355_dit_get_profile(ace355_dit* h, double* gemm_ms, double* gemm_flops, double* attn_ms, double* attn_flops,
                            int64_t* gemm_launches);
 
+/* One decoder pass (ace355_dit_forward, a step of ace355_dit_sample, ace355_dit_cross_attention_maps) as data, in launch order:
+ * plan_dit_pass of csrc/dit_plan.h, which the handle executes step by step.  A step names everything its launch takes except pointers
+ * and the sampler's step index; buffers appear as roles.  No GPU, no handle. */
+#define ACE355_DIT_STEP_MOD_GS 0        /* the (g, shift) vectors of the 2 NL modulated norms for this call's timestep rows */
+#define ACE355_DIT_STEP_ZERO_ROWSQ 1    /* zero fill of the folded norms' row sums (count elements) */
+#define ACE355_DIT_STEP_NORM_GS 2       /* rmsnorm(h) g + shift of table entry gs -> bf16 rows (dst) */
+#define ACE355_DIT_STEP_NORM_GS_MX 3    /* ... -> MXFP8 rows */
+#define ACE355_DIT_STEP_NORM_W 4        /* the cross-attention norm (plain weight) -> bf16 rows */
+#define ACE355_DIT_STEP_NORM_W_MX 5     /* ... -> MXFP8 rows */
+#define ACE355_DIT_STEP_GEMM 6
+#define ACE355_DIT_STEP_TRANSPOSE_V 7
+#define ACE355_DIT_STEP_ATTN_SELF 8
+#define ACE355_DIT_STEP_ATTN_CROSS 9
+#define ACE355_DIT_STEP_XATTN_PROBS 10
+#define ACE355_DIT_STEP_TAP 11          /* ace355_dit_set_tap's copy of the residual stream (count elements) */
+#define ACE355_DIT_STEP_NORM_OUT 12     /* norm_out with the timestep embedding's shift / scale */
+#define ACE355_DIT_PROJ_PATCHIFY 0
+#define ACE355_DIT_PROJ_QKV 1
+#define ACE355_DIT_PROJ_O 2
+#define ACE355_DIT_PROJ_CROSS_Q 3
+#define ACE355_DIT_PROJ_CROSS_O 4
+#define ACE355_DIT_PROJ_GATE_UP 5
+#define ACE355_DIT_PROJ_DOWN 6
+#define ACE355_DIT_PROJ_OUT 7
+#define ACE355_DIT_PATH_BF16 0
+#define ACE355_DIT_PATH_MX_QUANT 1      /* the bf16 operand is block-quantised first, then the MXFP8 GEMM */
+#define ACE355_DIT_PATH_MX 2            /* the MXFP8 GEMM on an operand its producer left as MXFP8 (src xq or aq) */
+#define ACE355_DIT_BUF_NONE (-1)
+#define ACE355_DIT_BUF_XIN 0            /* packed patch input bf16 [N][2S][in_channels] */
+#define ACE355_DIT_BUF_H 1              /* residual stream f32 [M][D] */
+#define ACE355_DIT_BUF_XN 2             /* normed rows bf16 [M + 1][D] */
+#define ACE355_DIT_BUF_QKV 3            /* q | k | v rows (self), q rows (cross) */
+#define ACE355_DIT_BUF_AO 4             /* attention output bf16 [M + 1][QD] */
+#define ACE355_DIT_BUF_ACT 5            /* SwiGLU output bf16 [M + 1][F] */
+#define ACE355_DIT_BUF_AQ 6             /* SwiGLU output as MXFP8 */
+#define ACE355_DIT_BUF_XQ 7             /* the MXFP8 operand scratch */
+#define ACE355_DIT_BUF_VT 8             /* V^T [N][KVH][128][Sp] */
+#define ACE355_DIT_BUF_VPAD 9           /* velocity rows f32 [M][2 out_channels] */
+#define ACE355_DIT_BUF_SLOT_KV 10       /* the condition slots' K rows / V^T tables, per sequence */
+#define ACE355_DIT_BUF_TAP 11
+#define ACE355_DIT_BUF_MAPS 12
+#define ACE355_DIT_G_NORM_CA (-2)       /* nf_gA: the layer's cross_attn_norm weight instead of a (g, shift) table entry */
+typedef struct ace355_dit_pass_request {
+    int32_t N, T;
+    int32_t temb_rows;                       /* 1: every sequence shares one timestep (the sampler); else N */
+    int32_t seq_slot[ACE355_MAX_SEQS];       /* per sequence: its condition slot ... */
+    int32_t seq_L[ACE355_MAX_SEQS];          /* ... that slot's key count (0: the slot is not set) ... */
+    int32_t seq_broadcast[ACE355_MAX_SEQS];  /* ... and whether it was set from one row (rows == 1) */
+    int32_t precision;                       /* ACE355_PRECISION_BF16 / _MXFP8 (the compute path) */
+    int32_t mx_min_rows;                     /* token rows below which MXFP8 launches stay bf16 (1536) */
+    int32_t mx_copies;                       /* MXFP8 weight copies that exist: 1 qkv, 2 o, 4 gate|up, 8 down, 16 cross q, 32 cross o; -1: those
+                                                ace355_dit_set_precision makes for the configuration */
+    int32_t nf_on, nf_emb_on, nf_rows;       /* the sampler call runs folded / reads its embeddings from the schedule tables / their steps */
+    int32_t dup_half;                        /* sequences [N/2, N) enter with the inputs of [0, N/2) (a CFG sampler step) */
+    int32_t dedup_on;                        /* ace355_dit_set_dedup */
+    int32_t prefetch;                        /* weight prefetch allowed (one chain) */
+    int32_t cu_slots;                        /* 0: the whole chip; 128: a chain planned for half of it */
+    int32_t graph_mode;                      /* ace355_dit_set_graph */
+    int32_t zr_M;                            /* the row of xn / ao / act the handle last zeroed, -1: none */
+    int32_t map_last;                        /* cross-attention maps: the last layer with a request (the pass stops there), -1: no maps */
+    int32_t map_heads[64];                   /* ... and the number of requested heads per layer */
+    int32_t qkv_vt_epilogue;                 /* GemmPlan::vt_epilogue of the QKV launch at M rows ... */
+    int32_t qkv_vt_epilogue_half;            /* ... and at the conditional half's rows (layer 0 of a deduplicated CFG step) */
+    int32_t self_mx_out_ok, cross_mx_out_ok; /* AttnPlan::mx_out_ok of the self- / cross-attention request */
+    int64_t nf_cap_M;                        /* rows the row-sum table holds */
+    uint64_t tap_mask;                       /* bit l: layer l is tapped (ace355_dit_set_tap) */
+} ace355_dit_pass_request;
+typedef struct ace355_dit_step_info {
+    int32_t kind, layer;                     /* ACE355_DIT_STEP_*; -1 outside the layers */
+    int32_t src, dst;                        /* ACE355_DIT_BUF_*: the row operand read, the buffer written */
+    int32_t M;                               /* rows: GEMM M, rows a norm writes, mod_gs timestep rows */
+    int32_t seqs;                            /* sequences of a transpose_v, attention or xattn_probs launch */
+    /* GEMM: GemmEpilogue (csrc/common.h) without pointers */
+    int32_t proj, path;                      /* ACE355_DIT_PROJ_*, ACE355_DIT_PATH_* */
+    int32_t N, K, lda, ldw, ldc, mode;
+    int32_t rows_per_seq;
+    int32_t bias;                            /* the projection has a bias vector (patchify, proj_out) */
+    int32_t gate;                            /* mode 2: row of the layer's scale_shift_table / of the timestep projection; -1: gate 1 */
+    int32_t cvec, cvec_row0;                 /* rows >= cvec_row0 add the broadcast slot's constant (cvec 1) */
+    int32_t hn;                              /* head-norm epilogue: 0 none, 1 self (q, k, RoPE), 2 cross (q only, no RoPE) */
+    int32_t hn_q_cols, hn_qk_cols;
+    int32_t vt_offered;                      /* V^T is offered to the epilogue */
+    int32_t nf_split, nf_gA, nf_gB;          /* fold producer (nf_split >= 0): (g, shift) table entries or ACE355_DIT_G_NORM_CA ... */
+    int32_t nf_sqA, nf_sqB;                  /* ... and row-sum table indices (3 layer + which) */
+    int32_t nc_rowsq, nc_bias;               /* fold consumer (nc_rowsq >= 0): row-sum index; bias table 0 none, 1 qkv, 2 gate|up */
+    int32_t a_wrap, a_zero_idx;
+    int32_t mxo;                             /* the SwiGLU epilogue writes MXFP8 */
+    int32_t next_proj, next_layer, next_M, next_N, next_K, next_mode;   /* prefetch target, next_proj -1: none */
+    /* norms */
+    int32_t gs;                              /* (g, shift) table entry: 2 layer + {0 self-attention, 1 MLP} */
+    /* attention, xattn_probs */
+    int32_t Sq, Skv, window, mx_out, Lpad;
+    int32_t n_heads, pair0;                  /* xattn_probs: requested heads of the layer, index of its first pair in the output */
+    int32_t reserved;
+    int64_t count;
+    double flops;
+} ace355_dit_step_info;
+typedef struct ace355_dit_pass_info {
+    int32_t S, M, Sp, Nc, Mc, n_sc, L, Lpad;
+    int32_t fold, emb, dedup0;
+    int32_t zero_rows;                       /* the call zeroes row M of xn / ao / act first */
+    int32_t n_steps, gemm_launches;
+    int64_t vt_elems;                        /* bf16 elements of V^T the call zeroes when (N, S) changed */
+    double gemm_flops, attn_flops;           /* sums over the steps */
+} ace355_dit_pass_info;
+/* cfg as ace355_dit_create checks it.  The four answers of other plans (qkv_vt_epilogue .. cross_mx_out_ok) are resolved here through
+ * ace355_gemm_plan's and ace355_attn_plan's queries, so the steps are what a handle in that state would launch; those four fields of
+ * `request` are ignored.  A refusal is ACE355_ERR_INVALID with forward's text.  steps_out may be NULL or shorter than the plan. */
+int ace355_dit_pass_plan(const ace355_dit_config* cfg, const ace355_dit_pass_request* request, ace355_dit_step_info* steps_out,
+                         int capacity, int32_t* n_out, ace355_dit_pass_info* info_out);
+
 /* ------------------------------------------------------------------------------------------
  * Oobleck VAE decoder (diffusers AutoencoderOobleck.decode; restated in models/mlx/vae_model.py:190-230)
  * ---------------------------------------------------------------------------------------- */
@@ -794,7 +905,7 @@ int ace355_gemm_bf16_fused(const void* A_dev, const void* W_dev, void* out_dev, 
                            const float* g1_dev, const float* g2_dev, int g2_stride, int rows_per_seq, void* stream);
 /* Residual GEMM with the whole epilogue of the DiT's o_proj / down_proj launches (gemm.hip mode 2): H[M,N] (f32) += gate * (A W^T),
  * gate as in ace355_gemm_bf16_fused mode 0, plus cvec[n] on rows m >= cvec_row0 (the constant cross-attention term of the CFG
- * null branch, dit.hip forward_core).  cvec NULL: none. */
+ * null branch: the o_proj step of csrc/dit_plan.h's pass plan).  cvec NULL: none. */
 int ace355_gemm_bf16_residual(const void* A_dev, const void* W_dev, float* H_dev, int M, int N, int K, const float* g1_dev,
                               const float* g2_dev, int g2_stride, int rows_per_seq, const float* cvec_dev, int cvec_row0,
                               void* stream);

@@ -60,12 +60,22 @@ def request(shape, **fields):
 
 
 def dit_launches(songs, T, cu_slots=0):
-    """The attention launches of dit.hip forward_core for `songs` songs with CFG at T latent frames: self-attention over both halves (layer 0
-    projects the conditional half only), full and banded, and cross-attention over the conditional half."""
-    S, c = (T + 1) // 2, dict(part_floats=PART, cu_slots=cu_slots)
-    return [("self, full", request((2 * songs, S, S, HQ, HKV, -1), **c)), ("self, sliding", request((2 * songs, S, S, HQ, HKV, WINDOW), **c)),
-            ("self, layer 0 (sliding), conditional half", request((songs, S, S, HQ, HKV, WINDOW), **c)),
-            ("cross", request((songs, S, L_COND, HQ, HKV, -1), **c))]
+    """The attention launches of a sampler step of the full-size DiT for `songs` songs with CFG at T latent frames, read from the library's
+    pass plan (native.dit_pass_plan): self-attention over both halves (layer 0 projects the conditional half only), full and banded, and
+    cross-attention over the conditional half."""
+    import ace355
+    from ace355 import native
+    cfg = ace355.DitConfig()
+    plan = native.dit_pass_plan(cfg, T, [(0, L_COND, 0)] * songs + [(1, L_COND, 1)] * songs, temb_rows=1, dup_half=1, cu_slots=cu_slots,
+                                prefetch=int(not cu_slots))
+    attn = [st for st in plan["steps"] if st["kind"] in ("attn_self", "attn_cross")]
+    first = lambda cond: next(st for st in attn if cond(st))
+    rq = lambda st: request((st["seqs"], st["Sq"], st["Skv"], cfg.num_attention_heads, cfg.num_key_value_heads, st["window"]), part_floats=PART, cu_slots=cu_slots)
+    layer0 = first(lambda st: st["kind"] == "attn_self" and st["layer"] == 0)
+    assert layer0["window"] == WINDOW and all(st["mx_out"] == 0 for st in attn)
+    return [("self, full", rq(first(lambda st: st["kind"] == "attn_self" and st["layer"] > 0 and st["window"] < 0))),
+            ("self, sliding", rq(first(lambda st: st["kind"] == "attn_self" and st["layer"] > 0 and st["window"] >= 0))),
+            ("self, layer 0 (sliding), conditional half", rq(layer0)), ("cross", rq(first(lambda st: st["kind"] == "attn_cross")))]
 
 
 def table_requests():

@@ -14,11 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = os.path.join(ROOT, "tests", "gemm_plan_table.json")
 VERIFIED, REFUSED = 1, 0
 
-# The DiT at full size (config.DitConfig defaults) and the prefetch rule of dit.hip / gemm_prefetch_plan: a launch carries prefetch
-# workgroups for the NEXT projection when that one has at most 800 rows and a residual or head epilogue.
-D, QD, KVD, F, IN2, OUT2 = 2048, 2048, 1024, 6144, 384, 128
-QKV = QD + 2 * KVD
-PF_X, PF_MAX_ROWS = 24, 800
+# The DiT pass rows are read from the library's pass plan (native.dit_pass_plan) at full size, T = 750, 769 condition tokens
+S_FULL, L_COND = 375, 769
 
 # test_gemm_launches_are_bit_reproducible's rows with the regime each was written for: (MT, WNW, NTW, PERS, NS, split-K).  The GPU test
 # imports this list, so the shapes exist once.
@@ -51,27 +48,49 @@ def entry_request(kind, M, N, K):
     return rq
 
 
-def _pf(next_rows, next_mode):
-    return PF_X if 0 < next_rows <= PF_MAX_ROWS and next_mode in (2, 4) else 0
+# The GEMMs of a pass the table names, as (projection, layer; -1: the last layer), and the request fields it records for each besides M, N, K,
+# mode, counters and cu_slots.  A field it does not record is 0 in that launch's request (asserted).
+PASS_ROWS = [("patchify", ("patchify", None), ()),
+             ("qkv layer 0", ("qkv", 0), ("fp8", "hn_q_cols", "hn_qk_cols", "vt_offered", "vt_heads", "fold_consumer", "pf_x")),
+             ("qkv", ("qkv", 1), ("fp8", "hn_q_cols", "hn_qk_cols", "vt_offered", "vt_heads", "fold_consumer", "pf_x")),
+             ("o_proj", ("o", 1), ("fp8", "fold_producer", "pf_x")),
+             ("cross q", ("cross_q", 1), ("hn_q_cols", "hn_qk_cols", "fold_consumer", "pf_x")),
+             ("cross o_proj", ("cross_o", 1), ("fold_producer", "pf_x")),
+             ("gate|up", ("gate_up", 1), ("fp8", "fold_consumer", "pf_x")),
+             ("down", ("down", 1), ("fp8", "fold_producer", "pf_x")),
+             ("down last layer", ("down", -1), ("fp8", "pf_x")),
+             ("proj_out", ("out", None), ())]
 
 
-def forward_core(M, Mc, fold, fp8=False, cu_slots=0, prefetch=True):
-    """Every GEMM of dit.hip forward_core for M rows of which Mc are conditional (cross-attention) rows: (name, request)."""
-    c = dict(counters=1, cu_slots=cu_slots)
-    pf = (lambda rows, mode: _pf(rows, mode)) if prefetch and not fp8 else (lambda rows, mode: 0)
-    out = [("patchify", dict(M=M, N=D, K=IN2, mode=1, **c))]
-    for layer0 in (True, False):
-        # layer 0 of a CFG forward projects q / k / v for the conditional half only (dedup0), and its input norm is never folded
-        Mq = Mc if layer0 and not fp8 and M == 2 * Mc else M
-        out.append((f"qkv{' layer 0' if layer0 else ''}", dict(M=Mq, N=QKV, K=D, mode=4, fp8=int(fp8), hn_q_cols=QD, hn_qk_cols=QD + KVD, vt_offered=1,
-                                                                vt_heads=KVD // 128, fold_consumer=int(fold and not layer0), pf_x=pf(M, 2), **c)))
-    out.append(("o_proj", dict(M=M, N=D, K=QD, mode=2, fp8=int(fp8), fold_producer=int(fold), pf_x=pf(Mc, 4), **c)))
-    out.append(("cross q", dict(M=Mc, N=QD, K=D, mode=4, hn_q_cols=QD, hn_qk_cols=QD, fold_consumer=int(fold), pf_x=pf(Mc, 2), **c)))
-    out.append(("cross o_proj", dict(M=Mc, N=D, K=QD, mode=2, fold_producer=int(fold), pf_x=pf(M, 3), **c)))
-    out.append(("gate|up", dict(M=M, N=2 * F, K=D, mode=3, fp8=int(fp8), fold_consumer=int(fold), pf_x=pf(M, 2), **c)))
-    out.append(("down", dict(M=M, N=D, K=F, mode=2, fp8=int(fp8), fold_producer=int(fold), pf_x=pf(M, 4), **c)))
-    out.append(("down last layer", dict(M=M, N=D, K=F, mode=2, fp8=int(fp8), pf_x=pf(M, 4), **c)))
-    out.append(("proj_out", dict(M=M, N=OUT2, K=D, mode=1, **c)))
+def step_request(st, kv_heads, cu_slots):
+    """The ace355_gemm_request of a pass plan's GEMM step.  pf_x: the prefetch workgroups gemm_prefetch_plan attaches for the step's target,
+    which ace355_gemm_plan reports for that target's own request.  counters: the handle lends its turn counters to every launch of the pass
+    (the MXFP8 launcher takes none; plan_gemm does not read the field for fp8)."""
+    from ace355 import native
+    pf_x = 0
+    if st["next_proj"] is not None:
+        pf_x = native.gemm_plan(st["next_M"], st["next_N"], st["next_K"], st["next_mode"], cu_slots=cu_slots)["next_pf_x"]
+    return dict(M=st["M"], N=st["N"], K=st["K"], mode=st["mode"], fp8=int(st["path"] != "bf16"), hn_q_cols=st["hn_q_cols"], hn_qk_cols=st["hn_qk_cols"],
+                vt_offered=st["vt_offered"], vt_heads=kv_heads if st["vt_offered"] else 0, fold_producer=int(st["nf_split"] >= 0),
+                fold_consumer=int(st["nc_rowsq"] >= 0), pf_x=pf_x, counters=1, cu_slots=cu_slots)
+
+
+def forward_core(M, Mc, fold, fp8=False, cu_slots=0):
+    """The GEMMs of a sampler step of the full-size DiT for M rows of which Mc are conditional (cross-attention) rows, the others the CFG
+    null branch, read from the library's pass plan: (name, request).  fold False: the same step with ACE355_NORM_FOLD=0."""
+    import ace355
+    from ace355 import native
+    cfg = ace355.DitConfig()
+    N, Nc = M // S_FULL, Mc // S_FULL
+    plan = native.dit_pass_plan(cfg, 2 * S_FULL, [(0, L_COND, 0)] * Nc + [(1, L_COND, 1)] * (N - Nc), temb_rows=1, dup_half=int(N > Nc),
+                                nf_on=int(fold), nf_emb_on=1, nf_rows=27, nf_cap_M=M, precision=int(fp8), cu_slots=cu_slots, prefetch=int(not cu_slots))
+    gemms = {(st["proj"], st["layer"] if st["layer"] >= 0 else None): st for st in plan["steps"] if st["kind"] == "gemm"}
+    out = []
+    for name, (proj, layer), recorded in PASS_ROWS:
+        rq = step_request(gemms[(proj, cfg.num_hidden_layers - 1 if layer == -1 else layer)], cfg.num_key_value_heads, cu_slots)
+        keep = ("M", "N", "K", "mode") + recorded + ("counters", "cu_slots")
+        assert all(v == 0 for k, v in rq.items() if k not in keep), (name, rq)
+        out.append((name, {k: v for k, v in rq.items() if k in keep}))
     return out
 
 
@@ -85,7 +104,7 @@ def table_requests():
     rows = []
     add = lambda group, items: rows.extend((f"{group}: {n}", r) for n, r in items)
     add("one song, CFG, sampler (folded norms)", forward_core(750, 375, True))
-    add("one song, CFG, plain forward", forward_core(750, 375, False))
+    add("one song, CFG, plain forward", forward_core(750, 375, False))   # (group names as recorded; see forward_core for fold False)
     add("one song, no CFG", forward_core(375, 375, False))
     add("metric batch, sampler", forward_core(6000, 3000, True))
     add("metric batch, plain forward", forward_core(6000, 3000, False))

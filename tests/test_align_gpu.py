@@ -137,9 +137,14 @@ def test_early_exit(full_dit_seed4):
     a = dit.cross_attention_maps(x, ctx2, t.tolist(), t.tolist(), [0, 0], prs)
     b = dit.cross_attention_maps(x, ctx2, t.tolist(), t.tolist(), [0, 0], prs + [(23, 15)])
     assert torch.equal(_bits(a), _bits(b[:len(prs)]))
-    # GEMM launches (dit.hip forward_core): patchify + 6 per layer (qkv, o, cross q, cross o, gate|up, down) + proj_out for the full
-    # forward; the maps call stops after the cross q of the last requested layer
+    # GEMM launches, read from the pass plan (native.dit_pass_plan): patchify + 6 per layer (qkv, o, cross q, cross o, gate|up, down) +
+    # proj_out for the full forward; the maps call stops after the cross q of the last requested layer
+    from ace355 import native
     max_layer = max(l for l, _ in prs)
+    L_enc = enc.shape[1]
+    heads = [sum(1 for l, _ in prs if l == li) for li in range(cfg.num_hidden_layers)]
+    plan_maps = native.dit_pass_plan(cfg, 121, [(0, L_enc, 0)] * 2, map_last=max_layer, map_heads=heads)["gemm_launches"]
+    plan_full = native.dit_pass_plan(cfg, 121, [(0, L_enc, 0)] * 2)["gemm_launches"]
     dit.set_profile(True)
     try:
         dit.cross_attention_maps(x, ctx2, t.tolist(), t.tolist(), [0, 0], prs)
@@ -149,8 +154,8 @@ def test_early_exit(full_dit_seed4):
         n_full = dit.get_profile()["gemm_launches"]
     finally:
         dit.set_profile(False)
-    assert n_maps == 1 + 6 * max_layer + 3 == 40
-    assert n_full == 1 + 6 * cfg.num_hidden_layers + 1
+    assert n_maps == plan_maps == 1 + 6 * max_layer + 3 == 40
+    assert n_full == plan_full == 1 + 6 * cfg.num_hidden_layers + 1
 
 
 # ------------------------------------------------------------------------------------------------ 5. no state leaks into later calls
