@@ -64,13 +64,6 @@ struct DevTmp {
     }
 };
 
-__global__ void snake_prep_kernel(const float* __restrict__ alpha, const float* __restrict__ beta, float* __restrict__ ea,
-                                  float* __restrict__ ib, int C) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= C) return;
-    ea[i] = expf(alpha[i]);
-    ib[i] = 1.0f / (expf(beta[i]) + 1e-9f);
-}
 // Box probe: every wave issues `iters` x 4 independent v_mfma_f32_32x32x16_bf16 on random bf16 operands, no memory traffic - the
 // matrix-pipe ceiling of THIS board under its power cap (tools/probe/mfma_clock_probe.hip is the stand-alone form).
 __global__ __launch_bounds__(512) void mfma_probe_kernel(float* sink, int iters) {
@@ -587,7 +580,8 @@ int ace355_conv1d_nlc(const void* x, const void* w, const float* bias, const flo
         ACE_HIP(hipMalloc(&t.p[0], (size_t)Cin * 4));
         ACE_HIP(hipMalloc(&t.p[1], (size_t)Cin * 4));
         ea = (float*)t.p[0], ib = (float*)t.p[1];
-        hipLaunchKernelGGL(snake_prep_kernel, dim3((Cin + 255) / 256), dim3(256), 0, s, alpha, beta, ea, ib, Cin);
+        const int rc = launch_snake_prep(alpha, beta, ea, ib, Cin, 1, s);
+        if (rc) return rc;
     }
     ConvArgs a{};
     a.x = (const bf16_t*)x; a.x_batch_stride = (long)L * Cin; a.L_in = L; a.Cin = Cin;

@@ -358,6 +358,8 @@ struct ConvArgs {
     int ras_tm; int ras_tn;
 };
 int launch_conv(const ConvArgs& a, hipStream_t s);
+// Snake parameters as ConvArgs takes them (vae.hip): ea[i] = exp(alpha[i % C]), ib[i] = 1 / (exp(beta[i % C]) + 1e-9) for i < C * reps
+int launch_snake_prep(const float* alpha, const float* beta, float* ea, float* ib, int C, int reps, hipStream_t s);
 int launch_ncl_to_nlc(const float* z, bf16_t* out, int B, int C, int T, hipStream_t s);
 
 // Adapter merges (lora.hip, lokr.hip, dora.hip; ace355_dit_set_adapters / _mixed / _dora).  The tables they read and the plan that fills

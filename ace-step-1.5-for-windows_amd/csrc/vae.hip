@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "encoder.h"   // dev_alloc
+#include "encoder.h"   // LoadBase, dev_alloc
 #include "vae_plan.h"
 
 using namespace ace355;
@@ -19,29 +19,19 @@ namespace {
 struct ConvW {
     bf16_t* w = nullptr;   // [N][taps][Cin]
     float* bias = nullptr; // [N] or null
-    int N = 0, taps = 0, Cin = 0;
 };
 struct SnakeP {
     float* ea = nullptr;  // exp(alpha)
     float* ib = nullptr;  // 1 / (exp(beta) + 1e-9)
 };
-struct ResUnitW {
-    SnakeP s1, s2;
-    ConvW c1, c2;
-};
-struct BlockW {
-    SnakeP s1;
-    ConvW ct;
-    ResUnitW ru[3];
-};
-struct EncBlockW {
-    ResUnitW ru[3];
-    SnakeP s1;       // tiled `stride` times (virtual channel c' -> channel c' % cin)
-    ConvW cd;        // strided conv as 2 taps over stride*cin virtual channels
-};
 struct RawT {
     float* p = nullptr;
     long n = 0;
+};
+// device temporaries of a load or a finalize: freed on every exit path
+struct DevTmp {
+    std::vector<void*> bag;
+    ~DevTmp() { for (void* q : bag) (void)hipFree(q); }
 };
 
 // ||v_row||_2 per row (one wave per row)
@@ -56,59 +46,25 @@ __global__ void rownorm_kernel(const float* __restrict__ v, long cols, float* __
     s = wave_sum_d(s);
     if (lane == 0) out[row] = (float)sqrt(s);
 }
-// Conv1d weight_v [Cout][Cin][K] (+g, norm) -> w[co][k][ci] bf16
-__global__ void pack_conv_kernel(const float* __restrict__ v, const float* __restrict__ g, const float* __restrict__ nrm,
-                                 bf16_t* __restrict__ w, int Cout, int Cin, int K) {
+// weight(_v) [d0][d1][K] (+ g and the norm over dimension 0) -> bf16 at vae_pack_index (vae_plan.h)
+__global__ void pack_weight_kernel(const float* __restrict__ v, const float* __restrict__ g, const float* __restrict__ nrm,
+                                   bf16_t* __restrict__ w, int kind, VaePackDims d, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)Cout * Cin * K) return;
-    const int k = (int)(i % K);
-    const long t = i / K;
-    const int ci = (int)(t % Cin), co = (int)(t / Cin);
+    if (i >= n) return;
     float x = v[i];
-    if (g) x = g[co] * x / (nrm[co] + 1e-9f);
-    w[((long)co * K + k) * Cin + ci] = f2bf(x);
-}
-// ConvTranspose1d weight_v [Cin][Cout][2s] (+g over dim 0) -> w[r*Cout + co][tap][ci]; tap0 <-> k = r + s (x[i0-1]), tap1 <-> k = r (x[i0])
-__global__ void pack_convt_kernel(const float* __restrict__ v, const float* __restrict__ g, const float* __restrict__ nrm,
-                                  bf16_t* __restrict__ w, int Cin, int Cout, int s) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int K = 2 * s;
-    if (i >= (long)Cin * Cout * K) return;
-    const int k = (int)(i % K);
-    const long t = i / K;
-    const int co = (int)(t % Cout), ci = (int)(t / Cout);
-    float x = v[i];
-    if (g) x = g[ci] * x / (nrm[ci] + 1e-9f);
-    const int r = k % s, tap = k >= s ? 0 : 1;
-    w[(((long)r * Cout + co) * 2 + tap) * Cin + ci] = f2bf(x);
-}
-// strided Conv1d weight_v [Cout][C][2s] (+g, norm) -> w[co][g][s' * C + ci] with k = g*s + s'  (2 taps over s*C virtual channels)
-__global__ void pack_conv_strided_kernel(const float* __restrict__ v, const float* __restrict__ g, const float* __restrict__ nrm,
-                                         bf16_t* __restrict__ w, int Cout, int C, int s) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int K = 2 * s;
-    if (i >= (long)Cout * C * K) return;
-    const int k = (int)(i % K);
-    const long t = i / K;
-    const int ci = (int)(t % C), co = (int)(t / C);
-    float x = v[i];
-    if (g) x = g[co] * x / (nrm[co] + 1e-9f);
-    const int gg = k / s, sp = k % s;
-    w[((long)co * 2 + gg) * ((long)s * C) + (long)sp * C + ci] = f2bf(x);
-}
-// first encoder conv (Cin = audio channels, k = 7) as a 1-tap conv over 64 virtual channels: w'[co][k*A + c] = w[co][c][k]
-__global__ void pack_conv_im2col_kernel(const float* __restrict__ v, const float* __restrict__ g, const float* __restrict__ nrm,
-                                        bf16_t* __restrict__ w, int Cout, int A, int K) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)Cout * 64) return;
-    const int cc = (int)(i % 64), co = (int)(i / 64);
-    float x = 0.f;
-    if (cc < K * A) {
-        const int k = cc / A, c = cc % A;
-        x = v[((long)co * A + c) * K + k];
-        if (g) x = g[co] * x / (nrm[co] + 1e-9f);
+    if (g) {
+        const long r = i / ((long)d.d1 * d.K);
+        x = g[r] * x / (nrm[r] + 1e-9f);
     }
-    w[i] = f2bf(x);
+    w[vae_pack_index(kind, d, i)] = f2bf(x);
+}
+// Snake parameters as conv_kernel takes them, the pair of C repeated `reps` times
+__global__ void snake_prep_kernel(const float* __restrict__ alpha, const float* __restrict__ beta, float* __restrict__ ea,
+                                  float* __restrict__ ib, int C, int reps) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= C * reps) return;
+    ea[i] = expf(alpha[i % C]);
+    ib[i] = 1.0f / (expf(beta[i % C]) + 1e-9f);
 }
 // audio f32 [B][A][L] -> x'[b][l][k*A + c] = audio[b][c][l + k - K/2] (zero outside), 64 bf16 per row
 __global__ void audio_im2col_kernel(const float* __restrict__ audio, bf16_t* __restrict__ out, int A, long L, int K, long total) {
@@ -142,13 +98,6 @@ __global__ void gaussian_head_kernel(const float* __restrict__ h, const float* _
     }
     z[i] = out;
 }
-__global__ void snake_prep_kernel(const float* __restrict__ alpha, const float* __restrict__ beta, float* __restrict__ ea,
-                                  float* __restrict__ ib, int C) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= C) return;
-    ea[i] = expf(alpha[i]);
-    ib[i] = 1.0f / (expf(beta[i]) + 1e-9f);
-}
 __global__ void tile_bias_kernel(const float* __restrict__ b, float* __restrict__ out, int C, int reps) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= C * reps) return;
@@ -161,21 +110,21 @@ __global__ void cvt_bf16_f32_kernel(const bf16_t* __restrict__ in, float* __rest
 
 }  // namespace
 
-struct ace355_vae {
+int ace355::launch_snake_prep(const float* alpha, const float* beta, float* ea, float* ib, int C, int reps, hipStream_t s) {
+    hipLaunchKernelGGL(snake_prep_kernel, dim3((C * reps + 255) / 256), dim3(256), 0, s, alpha, beta, ea, ib, C, reps);
+    ACE_LAUNCH_CHECK();
+    return 0;
+}
+
+struct ace355_vae : LoadBase {   // (allocs: what the last finalize built)
     ace355_vae_config cfg;
     VaeShape shape;   // widths, strides and pads of both halves (vae_plan.h): what finalize builds and what the plans walk
     int hop = 1;
-    std::map<std::string, RawT> raw;
-    std::vector<void*> allocs;
-    ConvW conv1, conv2;
-    SnakeP s_out;
-    std::vector<BlockW> blocks;
-    bool finalized = false;
-    // encoder (optional: present when encoder.* tensors were loaded)
+    std::map<std::string, RawT> raw;   // loaded and not yet consumed by a finalize
+    // [0] decoder, [1] encoder (optional: present when encoder.* tensors were loaded); both indexed by vae_weight_slot
+    std::vector<ConvW> conv[2];
+    std::vector<SnakeP> snake[2];
     bool has_encoder = false;
-    ConvW e_conv1, e_conv2;
-    SnakeP e_s_out;
-    std::vector<EncBlockW> e_blocks;
     bf16_t* ain = nullptr;      // im2col'ed audio [B][L][64]
     size_t ain_elems = 0;
     float* e_head = nullptr;    // conv2 output f32 [B][2Z][T]
@@ -190,7 +139,6 @@ struct ace355_vae {
     int last_plan[3] = {0, 0, 0};    // (items per window, core frames, overlap) of the last decode
     bf16_t* zin = nullptr;
     size_t zin_elems = 0;
-    float* scratch = nullptr;
     // profile
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -202,160 +150,31 @@ struct ace355_vae {
 
 namespace {
 
-template <typename T>
-int valloc(ace355_vae* h, T** p, size_t n) {
-    return dev_alloc(h->allocs, p, n);
-}
-
-const RawT* find(ace355_vae* h, const std::string& k) {
-    auto it = h->raw.find(k);
-    return it == h->raw.end() ? nullptr : &it->second;
-}
-
-int need(ace355_vae* h, const std::string& k, long n, const RawT** out) {
-    const RawT* r = find(h, k);
-    if (!r) { set_error("vae_finalize: missing tensor '" + k + "'"); return ACE355_ERR_STATE; }
-    if (r->n != n) { set_error("vae_finalize: wrong size for '" + k + "': got " + std::to_string(r->n) + ", expected " + std::to_string(n)); return ACE355_ERR_INVALID; }
-    *out = r;
-    return 0;
-}
-
-// Conv1d: base.weight_g [Cout,1,1], base.weight_v [Cout,Cin,K] (or fused base.weight), base.bias [Cout]
-int build_conv(ace355_vae* h, const std::string& base, int Cout, int Cin, int K, bool has_bias, ConvW* c) {
-    const RawT *v = nullptr, *g = nullptr, *b = nullptr;
-    int rc;
-    const bool fused = find(h, base + ".weight") != nullptr;
-    if (fused) {
-        if ((rc = need(h, base + ".weight", (long)Cout * Cin * K, &v))) return rc;
-    } else {
-        if ((rc = need(h, base + ".weight_v", (long)Cout * Cin * K, &v))) return rc;
-        if ((rc = need(h, base + ".weight_g", Cout, &g))) return rc;
+// One row of the weight table (vae_plan.h) from its raw tensors `t` (vae_row_tensors order) into slot `slot` of its half; `nrm`: scratch
+// for the row norms, shared by the rows (one stream)
+int build_row(ace355_vae* h, int half, int slot, const VaeWeightRow& r, float* const* t, bool fused, float* nrm) {
+    const VaePackDims& d = r.d;
+    if (r.kind == VAE_ROW_SNAKE) {
+        SnakeP& sp = h->snake[half][slot];
+        ALLOC(h->allocs, sp.ea, (size_t)d.d0 * d.s);
+        ALLOC(h->allocs, sp.ib, (size_t)d.d0 * d.s);
+        return launch_snake_prep(t[0], t[1], sp.ea, sp.ib, d.d0, d.s, 0);
     }
-    if (has_bias && (rc = need(h, base + ".bias", Cout, &b))) return rc;
-    c->N = Cout; c->taps = K; c->Cin = Cin;
-    if ((rc = valloc(h, &c->w, (size_t)Cout * Cin * K))) return rc;
-    float* nrm = nullptr;
-    if (g) {
-        if ((rc = valloc(h, &nrm, (size_t)Cout))) return rc;
-        hipLaunchKernelGGL(rownorm_kernel, dim3((Cout + 3) / 4), dim3(256), 0, 0, v->p, (long)Cin * K, nrm, Cout);
+    ConvW& c = h->conv[half][slot];
+    const VaePacked pk = vae_packed(r);
+    const float* g = fused ? nullptr : t[1];
+    const long n = vae_norm_rows(r) * vae_norm_cols(r);
+    ALLOC(h->allocs, c.w, (size_t)pk.elems);
+    if (pk.elems != n) ACE_HIP(hipMemsetAsync(c.w, 0, (size_t)pk.elems * 2, 0));   // (IM2COL's pad columns)
+    if (g) hipLaunchKernelGGL(rownorm_kernel, dim3((vae_norm_rows(r) + 3) / 4), dim3(256), 0, 0, t[0], vae_norm_cols(r), nrm, vae_norm_rows(r));
+    hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, t[0], g, nrm, c.w, r.kind, d, n);
+    if (r.bias_reps) {
+        const int C = pk.N / r.bias_reps;
+        ALLOC(h->allocs, c.bias, (size_t)pk.N);
+        hipLaunchKernelGGL(tile_bias_kernel, dim3((pk.N + 255) / 256), dim3(256), 0, 0, t[fused ? 1 : 2], c.bias, C, r.bias_reps);
     }
-    const long n = (long)Cout * Cin * K;
-    hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v->p, g ? g->p : nullptr, nrm, c->w, Cout, Cin, K);
-    c->bias = has_bias ? b->p : nullptr;
     ACE_LAUNCH_CHECK();
     return 0;
-}
-
-int build_convt(ace355_vae* h, const std::string& base, int Cin, int Cout, int s, ConvW* c) {
-    const RawT *v = nullptr, *g = nullptr, *b = nullptr;
-    int rc;
-    const int K = 2 * s;
-    const bool fused = find(h, base + ".weight") != nullptr;
-    if (fused) {
-        if ((rc = need(h, base + ".weight", (long)Cin * Cout * K, &v))) return rc;
-    } else {
-        if ((rc = need(h, base + ".weight_v", (long)Cin * Cout * K, &v))) return rc;
-        if ((rc = need(h, base + ".weight_g", Cin, &g))) return rc;
-    }
-    if ((rc = need(h, base + ".bias", Cout, &b))) return rc;
-    c->N = s * Cout; c->taps = 2; c->Cin = Cin;
-    if ((rc = valloc(h, &c->w, (size_t)Cin * Cout * K))) return rc;
-    float* nrm = nullptr;
-    if (g) {
-        if ((rc = valloc(h, &nrm, (size_t)Cin))) return rc;
-        hipLaunchKernelGGL(rownorm_kernel, dim3((Cin + 3) / 4), dim3(256), 0, 0, v->p, (long)Cout * K, nrm, Cin);
-    }
-    const long n = (long)Cin * Cout * K;
-    hipLaunchKernelGGL(pack_convt_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v->p, g ? g->p : nullptr, nrm, c->w, Cin, Cout, s);
-    if ((rc = valloc(h, &c->bias, (size_t)s * Cout))) return rc;
-    hipLaunchKernelGGL(tile_bias_kernel, dim3((s * Cout + 255) / 256), dim3(256), 0, 0, b->p, c->bias, Cout, s);
-    ACE_LAUNCH_CHECK();
-    return 0;
-}
-
-int build_snake(ace355_vae* h, const std::string& base, int C, SnakeP* sp) {
-    const RawT *a = nullptr, *b = nullptr;
-    int rc;
-    if ((rc = need(h, base + ".alpha", C, &a))) return rc;
-    if ((rc = need(h, base + ".beta", C, &b))) return rc;
-    if ((rc = valloc(h, &sp->ea, (size_t)C))) return rc;
-    if ((rc = valloc(h, &sp->ib, (size_t)C))) return rc;
-    hipLaunchKernelGGL(snake_prep_kernel, dim3((C + 255) / 256), dim3(256), 0, 0, a->p, b->p, sp->ea, sp->ib, C);
-    ACE_LAUNCH_CHECK();
-    return 0;
-}
-
-int build_conv_strided(ace355_vae* h, const std::string& base, int Cout, int C, int s, ConvW* c) {
-    const RawT *v = nullptr, *g = nullptr, *b = nullptr;
-    int rc;
-    const int K = 2 * s;
-    const bool fused = find(h, base + ".weight") != nullptr;
-    if (fused) {
-        if ((rc = need(h, base + ".weight", (long)Cout * C * K, &v))) return rc;
-    } else {
-        if ((rc = need(h, base + ".weight_v", (long)Cout * C * K, &v))) return rc;
-        if ((rc = need(h, base + ".weight_g", Cout, &g))) return rc;
-    }
-    if ((rc = need(h, base + ".bias", Cout, &b))) return rc;
-    c->N = Cout; c->taps = 2; c->Cin = s * C;
-    if ((rc = valloc(h, &c->w, (size_t)Cout * C * K))) return rc;
-    float* nrm = nullptr;
-    if (g) {
-        if ((rc = valloc(h, &nrm, (size_t)Cout))) return rc;
-        hipLaunchKernelGGL(rownorm_kernel, dim3((Cout + 3) / 4), dim3(256), 0, 0, v->p, (long)C * K, nrm, Cout);
-    }
-    const long n = (long)Cout * C * K;
-    hipLaunchKernelGGL(pack_conv_strided_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v->p, g ? g->p : nullptr, nrm, c->w, Cout, C, s);
-    c->bias = b->p;
-    ACE_LAUNCH_CHECK();
-    return 0;
-}
-
-int build_conv_im2col(ace355_vae* h, const std::string& base, int Cout, int A, int K, ConvW* c) {
-    const RawT *v = nullptr, *g = nullptr, *b = nullptr;
-    int rc;
-    ACE_CHECK(A * K <= 64, "vae_finalize: audio_channels * 7 must fit 64 virtual channels");
-    const bool fused = find(h, base + ".weight") != nullptr;
-    if (fused) {
-        if ((rc = need(h, base + ".weight", (long)Cout * A * K, &v))) return rc;
-    } else {
-        if ((rc = need(h, base + ".weight_v", (long)Cout * A * K, &v))) return rc;
-        if ((rc = need(h, base + ".weight_g", Cout, &g))) return rc;
-    }
-    if ((rc = need(h, base + ".bias", Cout, &b))) return rc;
-    c->N = Cout; c->taps = 1; c->Cin = 64;
-    if ((rc = valloc(h, &c->w, (size_t)Cout * 64))) return rc;
-    float* nrm = nullptr;
-    if (g) {
-        if ((rc = valloc(h, &nrm, (size_t)Cout))) return rc;
-        hipLaunchKernelGGL(rownorm_kernel, dim3((Cout + 3) / 4), dim3(256), 0, 0, v->p, (long)A * K, nrm, Cout);
-    }
-    const long n = (long)Cout * 64;
-    hipLaunchKernelGGL(pack_conv_im2col_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v->p, g ? g->p : nullptr, nrm, c->w, Cout, A, K);
-    c->bias = b->p;
-    ACE_LAUNCH_CHECK();
-    return 0;
-}
-
-// Snake parameters repeated `reps` times (the strided conv's virtual channels)
-int build_snake_tiled(ace355_vae* h, const std::string& base, int C, int reps, SnakeP* sp) {
-    SnakeP one;
-    int rc = build_snake(h, base, C, &one);
-    if (rc) return rc;
-    if ((rc = valloc(h, &sp->ea, (size_t)C * reps))) return rc;
-    if ((rc = valloc(h, &sp->ib, (size_t)C * reps))) return rc;
-    hipLaunchKernelGGL(tile_bias_kernel, dim3((C * reps + 255) / 256), dim3(256), 0, 0, one.ea, sp->ea, C, reps);
-    hipLaunchKernelGGL(tile_bias_kernel, dim3((C * reps + 255) / 256), dim3(256), 0, 0, one.ib, sp->ib, C, reps);
-    ACE_LAUNCH_CHECK();
-    return 0;
-}
-
-int build_res_unit(ace355_vae* h, const std::string& r, int C, ResUnitW* R) {
-    int rc;
-    if ((rc = build_snake(h, r + ".snake1", C, &R->s1))) return rc;
-    if ((rc = build_conv(h, r + ".conv1", C, C, 7, true, &R->c1))) return rc;
-    if ((rc = build_snake(h, r + ".snake2", C, &R->s2))) return rc;
-    return build_conv(h, r + ".conv2", C, C, 1, true, &R->c2);
 }
 
 int run_conv(ace355_vae* h, const ConvArgs& a, hipStream_t s) {
@@ -395,13 +214,12 @@ int ace355_vae_create(const ace355_vae_config* cfg, ace355_vae** out) {
 void ace355_vae_destroy(ace355_vae* h) {
     if (!h) return;
     hipDeviceSynchronize();
-    for (auto& kv : h->raw) if (kv.second.p) hipFree(kv.second.p);
-    for (void* p : h->allocs) hipFree(p);
+    for (auto& kv : h->raw) hipFree(kv.second.p);
+    free_base(h);
     for (int i = 0; i < 3; ++i) if (h->buf[i]) hipFree(h->buf[i]);
     if (h->zin) hipFree(h->zin);
     if (h->ain) hipFree(h->ain);
     if (h->e_head) hipFree(h->e_head);
-    if (h->scratch) hipFree(h->scratch);
     for (auto& e : h->ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     delete h;
 }
@@ -414,68 +232,76 @@ int ace355_vae_load_tensor(ace355_vae* h, const char* name, const void* data, in
         set_error("vae_load_tensor: unknown tensor name '" + key + "' (decoder.* / encoder.* expected)");
         return ACE355_ERR_INVALID;
     }
-    RawT& r = h->raw[key];
-    if (r.p) { hipFree(r.p); r.p = nullptr; }
-    ACE_HIP(hipMalloc((void**)&r.p, (size_t)numel * 4 + 256));
-    r.n = numel;
+    DevTmp tmp;   // [0]: the fp32 copy until the map owns it, [1]: bf16 staging
+    float* p = nullptr;
+    ALLOC(tmp.bag, p, (size_t)numel);
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (dtype == ACE355_DTYPE_F32) {
-        ACE_HIP(hipMemcpy(r.p, data, (size_t)numel * 4, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        ACE_HIP(hipMemcpy(p, data, (size_t)numel * 4, kind));
     } else {
-        bf16_t* tmp = nullptr;
-        ACE_HIP(hipMalloc((void**)&tmp, (size_t)numel * 2 + 256));
-        ACE_HIP(hipMemcpy(tmp, data, (size_t)numel * 2, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(cvt_bf16_f32_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, tmp, r.p, (long)numel);
+        bf16_t* st = nullptr;
+        ALLOC(tmp.bag, st, (size_t)numel);
+        ACE_HIP(hipMemcpy(st, data, (size_t)numel * 2, kind));
+        hipLaunchKernelGGL(cvt_bf16_f32_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, st, p, (long)numel);
         ACE_HIP(hipDeviceSynchronize());
-        hipFree(tmp);
     }
+    RawT& r = h->raw[key];
+    tmp.bag[0] = r.p;   // (a tensor loaded twice: the earlier copy goes)
+    r.p = p;
+    r.n = numel;
     h->finalized = false;
     return ACE355_OK;
 }
 
+// Host bookkeeping first: every tensor the weight table (vae_plan.h) names is there with its size, or nothing is touched.  Then what an
+// earlier finalize built goes, the rows are built, and the raw tensors - consumed or unused - leave the map: a later finalize needs a
+// full reload.
 int ace355_vae_finalize(ace355_vae* h) {
     ACE_CHECK(h, "vae_finalize: null handle");
-    const VaeShape& sh = h->shape;
-    const int nb = sh.nb;
-    int rc;
-    if ((rc = build_conv(h, "decoder.conv1", sh.dec_c0, sh.zc, 7, true, &h->conv1))) return rc;
-    h->blocks.assign(nb, BlockW());
-    for (int i = 0; i < nb; ++i) {
-        BlockW& B = h->blocks[i];
-        const VaeBlockShape& S = sh.dec[i];
-        const std::string p = "decoder.block." + std::to_string(i);
-        if ((rc = build_snake(h, p + ".snake1", S.cin, &B.s1))) return rc;
-        if ((rc = build_convt(h, p + ".conv_t1", S.cin, S.cout, S.stride, &B.ct))) return rc;
-        for (int j = 0; j < 3; ++j)
-            if ((rc = build_res_unit(h, p + ".res_unit" + std::to_string(j + 1), S.cout, &B.ru[j]))) return rc;
-    }
-    if ((rc = build_snake(h, "decoder.snake1", sh.dec_cl, &h->s_out))) return rc;
-    if ((rc = build_conv(h, "decoder.conv2", sh.audio, sh.dec_cl, 7, false, &h->conv2))) return rc;
-    // encoder half (optional): vae_model.py:148-187.  encoder_hidden_size = 2 * latent channels (mean | scale)
-    h->has_encoder = false;
-    for (auto& kv : h->raw) if (kv.first.rfind("encoder.", 0) == 0) { h->has_encoder = true; break; }
-    if (h->has_encoder) {
-        if ((rc = build_conv_im2col(h, "encoder.conv1", sh.eh, sh.audio, 7, &h->e_conv1))) return rc;
-        h->e_blocks.assign(nb, EncBlockW());
-        for (int i = 0; i < nb; ++i) {
-            EncBlockW& B = h->e_blocks[i];
-            const VaeBlockShape& S = sh.enc[i];
-            const std::string p = "encoder.block." + std::to_string(i);
-            for (int j = 0; j < 3; ++j)
-                if ((rc = build_res_unit(h, p + ".res_unit" + std::to_string(j + 1), S.cin, &B.ru[j]))) return rc;
-            if ((rc = build_snake_tiled(h, p + ".snake1", S.cin, S.stride, &B.s1))) return rc;
-            if ((rc = build_conv_strided(h, p + ".conv1", S.cout, S.cin, S.stride, &B.cd))) return rc;
+    const auto enc_key = h->raw.lower_bound("encoder.");
+    const bool has_encoder = enc_key != h->raw.end() && enc_key->first.rfind("encoder.", 0) == 0;
+    struct Src { float* t[3]; bool fused; };
+    std::vector<VaeWeightRow> rows[2];
+    std::vector<Src> src[2];
+    int max_rows = 1;
+    for (int half = 0; half < (has_encoder ? 2 : 1); ++half) {
+        rows[half] = vae_weight_table(h->shape, half != 0);
+        for (const VaeWeightRow& r : rows[half]) {
+            ACE_CHECK(r.kind != VAE_ROW_IM2COL || r.d.d1 * r.d.K <= VAE_IM2COL_COLS, "vae_finalize: audio_channels * 7 must fit 64 virtual channels");
+            Src s{{nullptr, nullptr, nullptr}, r.kind != VAE_ROW_SNAKE && h->raw.count(r.base + ".weight") != 0};
+            int k = 0;
+            for (const VaeRawTensor& t : vae_row_tensors(r, s.fused)) {
+                const auto it = h->raw.find(t.name);
+                if (it == h->raw.end()) { set_error("vae_finalize: missing tensor '" + t.name + "'"); return ACE355_ERR_STATE; }
+                if (it->second.n != t.n) {
+                    set_error("vae_finalize: wrong size for '" + t.name + "': got " + std::to_string(it->second.n) + ", expected " + std::to_string(t.n));
+                    return ACE355_ERR_INVALID;
+                }
+                s.t[k++] = it->second.p;
+            }
+            src[half].push_back(s);
+            max_rows = std::max(max_rows, vae_norm_rows(r));
         }
-        if ((rc = build_snake(h, "encoder.snake1", sh.enc_cl, &h->e_s_out))) return rc;
-        if ((rc = build_conv(h, "encoder.conv2", sh.eh, sh.enc_cl, 3, true, &h->e_conv2))) return rc;
     }
     ACE_HIP(hipDeviceSynchronize());
-    // raw weight_v / weight_g copies are no longer needed (biases are still referenced)
-    for (auto& kv : h->raw) {
-        const std::string& k = kv.first;
-        const bool keep = k.size() > 5 && k.compare(k.size() - 5, 5, ".bias") == 0;
-        if (!keep && kv.second.p) { hipFree(kv.second.p); kv.second.p = nullptr; }
+    h->finalized = false;
+    for (void* p : h->allocs) hipFree(p);
+    h->allocs.clear();
+    DevTmp tmp;
+    float* nrm = nullptr;
+    ALLOC(tmp.bag, nrm, (size_t)max_rows);
+    for (int half = 0; half < 2; ++half) {
+        h->conv[half].assign(rows[half].size(), ConvW());
+        h->snake[half].assign(rows[half].size(), SnakeP());
+        for (size_t i = 0; i < rows[half].size(); ++i) {
+            const int rc = build_row(h, half, (int)i, rows[half][i], src[half][i].t, src[half][i].fused, nrm);
+            if (rc) return rc;
+        }
     }
-    if (!h->scratch) ACE_HIP(hipMalloc((void**)&h->scratch, 1024));
+    ACE_HIP(hipDeviceSynchronize());
+    for (auto& kv : h->raw) hipFree(kv.second.p);
+    h->raw.clear();
+    h->has_encoder = has_encoder;
     h->finalized = true;
     return ACE355_OK;
 }
@@ -505,39 +331,27 @@ static int run_plan(ace355_vae* h, int enc, const VaePlan& p, int B, const bf16_
     ACE_CHECK(!tapped || h->taps[enc].rbegin()->first < (int)p.stages.size(), "vae tap: no such stage");
     int rc;
     if (tapped && (rc = tap_copy(h, enc, p.stages[0], 0, in, B, s))) return rc;
-    auto unit = [&](int block, int j) -> const ResUnitW& { return enc ? h->e_blocks[block].ru[j] : h->blocks[block].ru[j]; };
+    const VaeShape& sh = h->shape;
+    // a role to its slot of the weight table (vae_plan.h)
+    auto conv = [&](int role, int block, int unit) -> const ConvW& { return h->conv[enc][vae_weight_slot(sh, enc != 0, false, role, block, unit)]; };
+    auto snake = [&](int role, int block, int unit) -> const SnakeP* {
+        return role == ACE355_VAE_SNAKE_NONE ? nullptr : &h->snake[enc][vae_weight_slot(sh, enc != 0, true, role, block, unit)];
+    };
     auto buf = [&](int role) -> bf16_t* {
         return role == ACE355_VAE_BUF_NONE ? nullptr : role == ACE355_VAE_BUF_IN ? const_cast<bf16_t*>(in) : role == ACE355_VAE_BUF_OUT ? (bf16_t*)out : h->buf[role];
     };
     for (const VaeStep& st : p.steps) {
-        auto snake = [&](int which, int block) -> const SnakeP* {
-            switch (which) {
-                case ACE355_VAE_SNAKE_UNIT_S1: return &unit(block, st.unit).s1;
-                case ACE355_VAE_SNAKE_UNIT_S2: return &unit(block, st.unit).s2;
-                case ACE355_VAE_SNAKE_BLOCK: return enc ? &h->e_blocks[block].s1 : &h->blocks[block].s1;   // (encoder: tiled `stride` times)
-                case ACE355_VAE_SNAKE_FINAL: return enc ? &h->e_s_out : &h->s_out;
-                default: return nullptr;
-            }
-        };
-        const ConvW* W = nullptr;
-        switch (st.weight) {
-            case ACE355_VAE_W_CONV_IN: W = enc ? &h->e_conv1 : &h->conv1; break;
-            case ACE355_VAE_W_CONVT: W = &h->blocks[st.block].ct; break;
-            case ACE355_VAE_W_UNIT_C1: W = &unit(st.block, st.unit).c1; break;
-            case ACE355_VAE_W_UNIT_C2: W = &unit(st.block, st.unit).c2; break;
-            case ACE355_VAE_W_DOWN: W = &h->e_blocks[st.block].cd; break;
-            case ACE355_VAE_W_OUT: W = &h->conv2; break;
-            default: W = &h->e_conv2; break;
-        }
+        const ConvW& W = conv(st.weight, st.block, st.unit);
         ConvArgs a{};
         a.x = buf(st.src) + st.src_off; a.x_batch_stride = st.x_batch_stride; a.L_in = st.L_in; a.Cin = st.Cin;
         a.x_shift = st.x_shift; a.x_valid = st.x_valid;
-        a.w = W->w; a.bias = W->bias;
-        if (const SnakeP* sp = snake(st.in_snake, st.in_snake_block)) a.alpha = sp->ea, a.beta = sp->ib;
-        if (const SnakeP* sp = snake(st.out_snake, st.out_snake_block)) a.osnake_a = sp->ea, a.osnake_b = sp->ib;
-        if (st.fused) {
-            const ResUnitW& R = unit(st.block, st.unit);
-            a.w2 = R.c2.w; a.bias2 = R.c2.bias; a.alpha2 = R.s2.ea; a.beta2 = R.s2.ib;
+        a.w = W.w; a.bias = W.bias;
+        if (const SnakeP* sp = snake(st.in_snake, st.in_snake_block, st.unit)) a.alpha = sp->ea, a.beta = sp->ib;
+        if (const SnakeP* sp = snake(st.out_snake, st.out_snake_block, st.unit)) a.osnake_a = sp->ea, a.osnake_b = sp->ib;
+        if (st.fused) {   // the unit's second stage: snake2 and conv2
+            const ConvW& W2 = conv(ACE355_VAE_W_UNIT_C2, st.block, st.unit);
+            const SnakeP* s2 = snake(ACE355_VAE_SNAKE_UNIT_S2, st.block, st.unit);
+            a.w2 = W2.w; a.bias2 = W2.bias; a.alpha2 = s2->ea; a.beta2 = s2->ib;
         }
         a.res = buf(st.res); a.res_batch_stride = st.res_batch_stride;
         a.y = buf(st.dst); a.y_batch_stride = st.y_batch_stride;

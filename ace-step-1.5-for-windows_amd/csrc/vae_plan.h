@@ -1,7 +1,9 @@
 // vae_plan.h - the host side of the Oobleck VAE as data, in the shape of attn_plan.h: which conv_kernel instantiation and grid a conv launch
 // gets (ConvRequest -> ConvPlan, plan_conv), and the launches of one decode window / one encode group in order (VaeShape -> VaePlan,
 // plan_vae) with everything ConvArgs needs except pointers.  launch_conv (conv.hip) executes the first, vae.hip walks the second; the
-// public stage list, the buffer sizes, the window plan and the two stage-length recurrences are read off the same data.  Pure functions:
+// public stage list, the buffer sizes, the window plan and the two stage-length recurrences are read off the same data.  The weights of a
+// handle are data too (VaeShape -> vae_weight_table): the tensors ace355_vae_finalize asks for, how each is packed (vae_pack_index, shared
+// with the pack kernel) and the slot a step's role resolves to (vae_weight_slot).  Pure functions:
 // no HIP call, no global, no environment - ace355_conv_plan / ace355_vae_plan answer on a machine without a GPU, and the header compiles
 // with a plain host compiler.
 #pragma once
@@ -10,9 +12,11 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "../../include/ace355.h"
+#include "adapter_plan.h"   // ACE_HD
 
 namespace ace355 {
 
@@ -71,7 +75,8 @@ inline ConvPlan plan_conv(const ConvRequest& r, const ConvKnobs& kn) {
 }
 
 // ------------------------------------------------------------------------------------------------ the two halves' shapes
-// Widths, strides and pads of both halves, from the configuration alone (ace355_vae_finalize builds its weights from the same numbers).
+// Widths, strides and pads of both halves, from the configuration alone (ace355_vae_finalize builds its weights from the same numbers:
+// vae_weight_table below).
 struct VaeBlockShape { int cin, cout, stride, pad; };
 struct VaeShape {
     int nb, zc, audio, hop;            // blocks, latent channels, audio channels, product of the strides
@@ -117,6 +122,126 @@ inline long vae_down_len(long L, const VaeBlockShape& b) { return (L + 2 * b.pad
 inline long vae_latent_frames(const VaeShape& s, long L) {
     for (int i = 0; i < s.nb && L > 0; ++i) L = vae_down_len(L, s.enc[i]);
     return L > 0 ? L : -1;
+}
+
+// ------------------------------------------------------------------------------------------------ the weights of a handle
+// One row per conv and per Snake of a half, in state-dict order: what ace355_vae_finalize needs of the loaded tensors, how it packs them,
+// and the role a step names the result by.  config.py's weight_shapes() / encoder_weight_shapes() list the same tensors
+// (tests/test_vae_weights_cpu.py holds the two against each other).
+enum { VAE_ROW_PLAIN = 0, VAE_ROW_CONVT, VAE_ROW_STRIDED, VAE_ROW_IM2COL, VAE_ROW_SNAKE };
+constexpr int VAE_IM2COL_COLS = 64;   // virtual channels of the encoder's first conv: K * audio channels, zero-padded
+// raw weight(_v) [d0][d1][K]: PLAIN / STRIDED / IM2COL [Cout][Cin][K] (IM2COL: Cin = the audio channels), CONVT [Cin][Cout][K]; K = 2 s
+// for the two strided kinds (s = 0 otherwise).  Weight-norm is over dimension 0 for every kind.
+struct VaePackDims { int d0, d1, K, s; };
+struct VaeWeightRow {
+    std::string base;          // "decoder.block.2.res_unit1.conv1"
+    int kind;                  // VAE_ROW_*
+    VaePackDims d;             // SNAKE: d0 = channels, s = how often the pair is repeated (the strided conv's virtual channels), d1 = K = 1
+    int bias_reps;             // 0: no bias; 1: base.bias as loaded; s: repeated s times (one copy per phase filter of CONVT)
+    int role, block, unit;     // ACE355_VAE_W_* (ACE355_VAE_SNAKE_* for a SNAKE row) and where, as a step names it
+};
+struct VaeRawTensor { std::string name; long n; };
+struct VaePacked { int N, taps, Cin; long elems; };   // w[N][taps][Cin] as conv_kernel reads it
+
+inline int vae_norm_rows(const VaeWeightRow& r) { return r.d.d0; }
+inline long vae_norm_cols(const VaeWeightRow& r) { return (long)r.d.d1 * r.d.K; }
+inline VaePacked vae_packed(const VaeWeightRow& r) {
+    const VaePackDims& d = r.d;
+    VaePacked p = r.kind == VAE_ROW_CONVT     ? VaePacked{d.s * d.d1, 2, d.d0, 0}    // all s phase filters side by side, 2 taps each
+                  : r.kind == VAE_ROW_STRIDED ? VaePacked{d.d0, 2, d.s * d.d1, 0}    // 2 taps over s * Cin virtual channels
+                  : r.kind == VAE_ROW_IM2COL  ? VaePacked{d.d0, 1, VAE_IM2COL_COLS, 0}
+                                              : VaePacked{d.d0, d.K, d.d1, 0};
+    p.elems = (long)p.N * p.taps * p.Cin;
+    return p;
+}
+// The tensors a row is built from and their element counts: the weight first.  fused: a pre-fused base.weight stands in for the pair.
+inline std::vector<VaeRawTensor> vae_row_tensors(const VaeWeightRow& r, bool fused) {
+    if (r.kind == VAE_ROW_SNAKE) return {{r.base + ".alpha", r.d.d0}, {r.base + ".beta", r.d.d0}};
+    std::vector<VaeRawTensor> t{{r.base + (fused ? ".weight" : ".weight_v"), vae_norm_rows(r) * vae_norm_cols(r)}};
+    if (!fused) t.push_back({r.base + ".weight_g", vae_norm_rows(r)});
+    if (r.bias_reps) t.push_back({r.base + ".bias", r.kind == VAE_ROW_CONVT ? r.d.d1 : r.d.d0});
+    return t;
+}
+// Where element i of the raw weight lands in the packed one.  Injective; onto, except that IM2COL leaves columns >= K * d1 of a row (zero).
+//   PLAIN    w[co][k][ci]
+//   CONVT    w[r * Cout + co][tap][ci], k = r + s <-> tap 0 (x[i0 - 1]), k = r <-> tap 1 (x[i0])
+//   STRIDED  w[co][g][s' * Cin + ci], k = g * s + s'
+//   IM2COL   w[co][k * A + c]
+ACE_HD long vae_pack_index(int kind, const VaePackDims& d, long i) {
+    const int k = (int)(i % d.K);
+    const long t = i / d.K;
+    const int c1 = (int)(t % d.d1), c0 = (int)(t / d.d1);
+    switch (kind) {
+        case VAE_ROW_CONVT: return (((long)(k % d.s) * d.d1 + c1) * 2 + (k >= d.s ? 0 : 1)) * d.d0 + c0;
+        case VAE_ROW_STRIDED: return ((long)c0 * 2 + k / d.s) * ((long)d.s * d.d1) + (long)(k % d.s) * d.d1 + c1;
+        case VAE_ROW_IM2COL: return (long)c0 * VAE_IM2COL_COLS + k * d.d1 + c1;
+        default: return ((long)c0 * d.K + k) * d.d1 + c1;
+    }
+}
+
+// Position in vae_weight_table(sh, enc) of the row a step names: conv1, 14 rows per block, the final Snake, conv2.  -1: no such role.
+inline int vae_weight_slot(const VaeShape& sh, bool enc, bool snake, int role, int block, int unit) {
+    const int b0 = 1 + 14 * block, u0 = b0 + (enc ? 0 : 2) + 4 * unit, end = 1 + 14 * sh.nb;
+    if (snake) switch (role) {
+        case ACE355_VAE_SNAKE_UNIT_S1: return u0;
+        case ACE355_VAE_SNAKE_UNIT_S2: return u0 + 2;
+        case ACE355_VAE_SNAKE_BLOCK: return b0 + (enc ? 12 : 0);
+        case ACE355_VAE_SNAKE_FINAL: return end;
+        default: return -1;
+    }
+    switch (role) {
+        case ACE355_VAE_W_CONV_IN: return 0;
+        case ACE355_VAE_W_CONVT: return enc ? -1 : b0 + 1;
+        case ACE355_VAE_W_UNIT_C1: return u0 + 1;
+        case ACE355_VAE_W_UNIT_C2: return u0 + 3;
+        case ACE355_VAE_W_DOWN: return enc ? b0 + 13 : -1;
+        case ACE355_VAE_W_OUT: return enc ? -1 : end + 1;
+        case ACE355_VAE_W_HEAD: return enc ? end + 1 : -1;
+        default: return -1;
+    }
+}
+
+inline std::vector<VaeWeightRow> vae_weight_table(const VaeShape& sh, bool enc) {
+    std::vector<VaeWeightRow> t;
+    t.reserve(3 + 14 * sh.nb);
+    auto conv = [&](const std::string& base, int kind, int d0, int d1, int K, int s, int bias_reps, int role, int block, int unit) {
+        t.push_back(VaeWeightRow{base, kind, VaePackDims{d0, d1, K, s}, bias_reps, role, block, unit});
+    };
+    auto snake = [&](const std::string& base, int C, int reps, int role, int block, int unit) {
+        t.push_back(VaeWeightRow{base, VAE_ROW_SNAKE, VaePackDims{C, 1, 1, reps}, 0, role, block, unit});
+    };
+    auto unit = [&](const std::string& p, int b, int j, int C) {
+        const std::string r = p + ".res_unit" + std::to_string(j + 1);
+        snake(r + ".snake1", C, 1, ACE355_VAE_SNAKE_UNIT_S1, b, j);
+        conv(r + ".conv1", VAE_ROW_PLAIN, C, C, 7, 0, 1, ACE355_VAE_W_UNIT_C1, b, j);
+        snake(r + ".snake2", C, 1, ACE355_VAE_SNAKE_UNIT_S2, b, j);
+        conv(r + ".conv2", VAE_ROW_PLAIN, C, C, 1, 0, 1, ACE355_VAE_W_UNIT_C2, b, j);
+    };
+    if (!enc) {
+        conv("decoder.conv1", VAE_ROW_PLAIN, sh.dec_c0, sh.zc, 7, 0, 1, ACE355_VAE_W_CONV_IN, -1, -1);
+        for (int i = 0; i < sh.nb; ++i) {
+            const VaeBlockShape& S = sh.dec[i];
+            const std::string p = "decoder.block." + std::to_string(i);
+            snake(p + ".snake1", S.cin, 1, ACE355_VAE_SNAKE_BLOCK, i, -1);
+            conv(p + ".conv_t1", VAE_ROW_CONVT, S.cin, S.cout, 2 * S.stride, S.stride, S.stride, ACE355_VAE_W_CONVT, i, -1);
+            for (int j = 0; j < 3; ++j) unit(p, i, j, S.cout);
+        }
+        snake("decoder.snake1", sh.dec_cl, 1, ACE355_VAE_SNAKE_FINAL, -1, -1);
+        conv("decoder.conv2", VAE_ROW_PLAIN, sh.audio, sh.dec_cl, 7, 0, 0, ACE355_VAE_W_OUT, -1, -1);
+        return t;
+    }
+    // vae_model.py:148-187.  encoder_hidden_size = 2 * latent channels (mean | scale)
+    conv("encoder.conv1", VAE_ROW_IM2COL, sh.eh, sh.audio, 7, 0, 1, ACE355_VAE_W_CONV_IN, -1, -1);
+    for (int i = 0; i < sh.nb; ++i) {
+        const VaeBlockShape& S = sh.enc[i];
+        const std::string p = "encoder.block." + std::to_string(i);
+        for (int j = 0; j < 3; ++j) unit(p, i, j, S.cin);
+        snake(p + ".snake1", S.cin, S.stride, ACE355_VAE_SNAKE_BLOCK, i, -1);
+        conv(p + ".conv1", VAE_ROW_STRIDED, S.cout, S.cin, 2 * S.stride, S.stride, 1, ACE355_VAE_W_DOWN, i, -1);
+    }
+    snake("encoder.snake1", sh.enc_cl, 1, ACE355_VAE_SNAKE_FINAL, -1, -1);
+    conv("encoder.conv2", VAE_ROW_PLAIN, sh.eh, sh.enc_cl, 3, 0, 1, ACE355_VAE_W_HEAD, -1, -1);
+    return t;
 }
 
 // ------------------------------------------------------------------------------------------------ one window / one group as steps

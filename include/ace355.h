@@ -584,11 +584,13 @@ typedef struct ace355_vae_config {
 /* Replaces H/mlx_vae_init.py:12-96 (_init_mlx_vae) + models/mlx/vae_convert.py. */
 int ace355_vae_create(const ace355_vae_config* cfg, ace355_vae** out);
 void ace355_vae_destroy(ace355_vae* h);
-/* Names are AutoencoderOobleck.state_dict() keys of the decoder half:
- * "decoder.conv1.weight_g|weight_v|bias", "decoder.block.{i}.snake1.alpha|beta",
- * "decoder.block.{i}.conv_t1.*", "decoder.block.{i}.res_unit{1,2,3}.{snake1,conv1,snake2,conv2}.*",
- * "decoder.snake1.*", "decoder.conv2.weight_g|weight_v".  Weight-norm is fused at finalize
- * (w = g*v/(||v||+1e-9), vae_convert.py:18-34).  A pre-fused "<conv>.weight" is accepted too. */
+/* Names are AutoencoderOobleck.state_dict() keys, "decoder.*" and (optional) "encoder.*".  Which of them a handle needs, with which
+ * element counts, is one table: vae_weight_table (csrc/vae_plan.h), one row per conv ("<base>.weight_g|weight_v", "<base>.bias") and per
+ * Snake ("<base>.alpha|beta").  Any other key under the two prefixes is accepted and dropped.  Weight-norm is fused at finalize
+ * (w = g*v/(||v||+1e-9), vae_convert.py:18-34); a pre-fused "<base>.weight" is taken in place of the pair.
+ * ace355_vae_finalize checks every name and size first (ACE355_ERR_STATE "missing tensor", ACE355_ERR_INVALID "wrong size"; nothing is
+ * touched then), builds the packed weights and CONSUMES the loaded tensors: a tensor loaded afterwards un-finalizes the handle, and the
+ * next finalize needs the whole state dict again. */
 int ace355_vae_load_tensor(ace355_vae* h, const char* name, const void* data, int dtype, int64_t numel, int is_device);
 int ace355_vae_finalize(ace355_vae* h);
 /* Replaces vae.decode(z).sample at H/vae_decode_chunks.py:42,95 / H/generate_music_decode.py:172-177 and

@@ -36,8 +36,33 @@ def _build(cfg_kw, device, seed=1):
     (dict(), 2, 9),
 ])
 def test_decode_vs_oracle(gpu_device, cfg_kw, B, T):
-    from oracle import oobleck as o_vae
     cfg, w, vae = _build(cfg_kw, gpu_device)
+    _check_decode_vs_oracle(cfg_kw, cfg, w, vae, B, T)
+
+
+def test_decode_of_prefused_weights_vs_oracle(gpu_device):
+    """The small case of test_decode_vs_oracle on a handle that was given every conv as its pre-fused ``<conv>.weight`` (g v / (||v|| + 1e-9)
+    in fp32 on the CPU, the formula of tests/_vae_layers.py) in place of the weight_g / weight_v pair; the oracle keeps the pair."""
+    import ace355
+    from ace355 import weightgen
+    from ace355.vae import NativeVae
+    cfg_kw = dict(decoder_channels=64, channel_multiples=(1, 2, 4), downsampling_ratios=(2, 4, 6))
+    cfg = ace355.VaeConfig(**cfg_kw)
+    w = weightgen.make_vae_weights(cfg.weight_shapes(), seed=1, mode="test")
+    fused = {k: t for k, t in w.items() if not k.endswith((".weight_g", ".weight_v"))}
+    for k in w:
+        if k.endswith(".weight_v"):
+            v, g = w[k].float(), w[k[:-1] + "g"].float().reshape(-1, 1, 1)
+            nrm = v.double().reshape(v.shape[0], -1).pow(2).sum(1).sqrt().float().reshape(-1, 1, 1)
+            fused[k[:-2]] = (g * v) / (nrm + torch.tensor(1e-9, dtype=torch.float32))
+    assert len(fused) < len(w) and not any(k.endswith(("_g", "_v")) for k in fused)
+    vae = NativeVae(cfg, gpu_device)
+    vae.load_state_dict(fused)
+    _check_decode_vs_oracle(cfg_kw, cfg, w, vae, 2, 37)
+
+
+def _check_decode_vs_oracle(cfg_kw, cfg, w, vae, B, T):
+    from oracle import oobleck as o_vae
     assert vae.hop == cfg.hop
     g = torch.Generator().manual_seed(T)
     z = torch.randn(B, 64, T, generator=g)
