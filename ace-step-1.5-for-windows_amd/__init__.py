@@ -8,11 +8,12 @@ Layout:
   cond.py      NativeCondEncoder: lyric / timbre encoders + sequence packing
   lmhints.py   audio-code parsing, FSQ index decode, NativeDetokenizer
   textenc.py   NativeTextEncoder: the caption text encoder (Qwen3Model, causal) and its embed_tokens gather
+  lm.py        NativeCausalLM: the 5 Hz LM's forward (Qwen3ForCausalLM): prefill, KV-cached decode steps, last-position logits
   audio_out.py normalize_audio, AudioSaver: GPU normalise / PCM conversion + threaded FLAC / WAV writers
   backend.py   NativeDitMixin / NativeVaeMixin / NativeHandler: the reference's handler seam
   dist.py      one-process-per-GPU data-parallel runner (RCCL broadcast of conditioning)
   weightgen.py deterministic synthetic weights (no checkpoints exist on the boxes)
 """
-from .config import CondConfig, DetokConfig, DitConfig, TextEncoderConfig, VaeConfig  # noqa: F401
+from .config import CondConfig, DetokConfig, DitConfig, LmConfig, TextEncoderConfig, VaeConfig  # noqa: F401
 
-__all__ = ["CondConfig", "DetokConfig", "DitConfig", "TextEncoderConfig", "VaeConfig"]
+__all__ = ["CondConfig", "DetokConfig", "DitConfig", "LmConfig", "TextEncoderConfig", "VaeConfig"]

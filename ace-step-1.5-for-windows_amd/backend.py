@@ -471,6 +471,37 @@ class NativeTextEncoderMixin:
             return False
 
 
+class NativeLmMixin:
+    """For the reference's ``LLMHandler``.  Required host attributes: ``llm`` (the loaded ``Qwen3ForCausalLM``), ``device``; optional
+    ``offload_to_cpu``, ``native_lm_max_positions`` (cache positions: prompt + generated tokens, default 8192)."""
+
+    use_native_lm: bool = False
+
+    def _init_native_lm(self) -> bool:
+        """Swap ``self.llm`` for ``modswap.NativeCausalLMSwap`` after the model is loaded: ``_forward_pass``'s prefill and decode steps
+        then run natively, and everything else (``generate``, the sampling code around the logits) is untouched.  Same policy as
+        ``_init_native_text_encoder``: refused under CPU offload or off a CUDA device, any failure is logged and leaves the PyTorch
+        module in place.  Never raises."""
+        try:
+            if getattr(self, "offload_to_cpu", False) or not str(getattr(self, "device", "cpu")).startswith("cuda"):
+                logger.info("[native-lm] CPU offload active or no GPU device; keeping the PyTorch path")
+                self.use_native_lm = False
+                return False
+            if getattr(self, "llm", None) is None:
+                raise RuntimeError("no LM loaded")
+            from . import modswap
+            wrapper = modswap.swap_in_lm(self, self.device, max_positions=int(getattr(self, "native_lm_max_positions", 8192)))
+            self.use_native_lm = True
+            cfg = object.__getattribute__(wrapper, "_native").cfg
+            logger.info("[native-lm] packed for gfx950 (%d layers, hidden %d, vocabulary %d)", cfg.num_hidden_layers, cfg.hidden_size,
+                        cfg.vocab_size)
+            return True
+        except Exception as exc:
+            logger.warning("[native-lm] init failed (%s: %s); PyTorch path stays active", type(exc).__name__, exc)
+            self.use_native_lm = False
+            return False
+
+
 class _ModelShell:
     """What the mixins read from ``self.model``: decoder state dict, null embedding, config."""
 

@@ -221,6 +221,31 @@ class TextEncoderConfig:
 
 
 @dataclass
+class LmConfig(TextEncoderConfig):
+    """Fields of transformers' ``Qwen3Config`` that ``Qwen3ForCausalLM`` (the reference's 5 Hz LM, 0.6B / 1.7B) uses: the text encoder's
+    stack plus the head.  ``vocab_size`` is whatever the checkpoint says (Qwen3's vocabulary plus the audio-code tokens)."""
+
+    tie_word_embeddings: bool = True
+
+    @classmethod
+    def from_reference(cls, cfg) -> "LmConfig":
+        """From a ``Qwen3Config``.  Refuses what ``TextEncoderConfig.from_reference`` refuses (sliding-window layers, ``attention_bias``,
+        non-default RoPE) and the head layouts the kernels do not serve (Qwen3-4B's 32 / 8 heads): ``NotImplementedError``."""
+        base = TextEncoderConfig.from_reference(cfg)
+        if base.head_dim != 128 or base.num_attention_heads != 2 * base.num_key_value_heads:
+            raise NotImplementedError(f"ace355: LM head layout {base.num_attention_heads} / {base.num_key_value_heads} heads of "
+                                      f"{base.head_dim} (only 2 q heads per kv head, head_dim 128)")
+        return cls(**base.__dict__, tie_word_embeddings=bool(getattr(cfg, "tie_word_embeddings", False)))
+
+    def weight_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """Names/shapes of ``Qwen3ForCausalLM.state_dict()``; a tied checkpoint's ``lm_head.weight`` is the embedding table and is not listed."""
+        s = {"model." + k: v for k, v in TextEncoderConfig.weight_shapes(self).items()}
+        if not self.tie_word_embeddings:
+            s["lm_head.weight"] = (self.vocab_size, self.hidden_size)
+        return s
+
+
+@dataclass
 class DetokConfig:
     """Fields of ``AceStepConfig`` used by ``AudioTokenDetokenizer`` (modeling_acestep_v15_base.py:862-994)."""
 

@@ -97,17 +97,37 @@ int alloc_encoder(EncBase* h, EncoderW& E, int n_layers, int in_dim);
 // "<prefix>layers.<i>.<one of the 11 layer keys>" -> its packed destination
 bool resolve_encoder_layer(const EncBase& h, EncLayerW& L, const std::string& key_after_index, PackDest* d);
 bool resolve_encoder_layers(const EncBase& h, EncoderW& E, const std::string& name, size_t prefix_len, PackDest* d);
+// KV cache of a causal stack that is run in steps (lm.hip): bf16 [layer][K | V][max_seqs][kv head][max_pos][128], K as the QKV epilogue
+// leaves it (head-normed, rotated, head-pair dim order), V in natural order.  Handed to encoder_layers, rows s of the call sit at positions
+// pos0 + s: their K / V are stored, and a step with pos0 > 0 (S == 1) attends the cache instead of the QKV rows.
+struct KvCache {
+    bf16_t* kv = nullptr;
+    int max_seqs = 0, max_pos = 0;
+    const int* first_dev = nullptr;   // [N]: first visible key of each sequence (left padding), device
+    int pos0 = 0;
+    float *part_o = nullptr, *part_ml = nullptr;   // decode attention's per-chunk partials (lm_plan.h): [N][HQ][LM_MAX_SPLITS][128 | 2]
+    long slab(int kvh_count) const { return (long)max_seqs * kvh_count * max_pos * 128; }   // elements of one layer's K (or V)
+};
+
 // Grow-only workspace: a request beyond what is held syncs the stream, frees everything and reallocates at the max of old and new.
 // in_elems (in_bf), emb_rows (emb, x D), seqs (vmean, kvlen_dev) and vt_elems (vt) may be 0: that buffer is not needed.
 int ensure_workspace(EncBase* h, long rows, long in_elems, long emb_rows, int seqs, long vt_elems, hipStream_t s);
 // n_layers x encoder layer + final RMSNorm over N sequences of S tokens, on the fp32 stream h->h ([N*S, D], already embedded).
-// kv_len_dev: per-sequence valid key count or null (bidirectional only); out: [N*S, D] bf16.
-int encoder_layers(EncBase* h, const EncoderW& E, int N, int S, const int* kv_len_dev, bf16_t* out, hipStream_t s);
+// kv_len_dev: per-sequence valid key count or null (bidirectional only); out: [N*S, D] bf16.  cache (causal stacks only, null: none): see
+// KvCache; the rope table then covers cache->max_pos.
+int encoder_layers(EncBase* h, const EncoderW& E, int N, int S, const int* kv_len_dev, bf16_t* out, hipStream_t s,
+                   const KvCache* cache = nullptr);
 void free_encoder(EncBase* h);   // free_base + the workspace
 
-// textenc.hip
+// textenc.hip.  k_first_dev (null: none): per-sequence first visible key; query rows below it store zeros.
 int launch_causal_attention(const bf16_t* qkv, int ld, int k_col0, int v_col0, bf16_t* out, int o_ld, int N, int S, int Hkv, float scale,
-                            hipStream_t s);
+                            hipStream_t s, const int* k_first_dev = nullptr);
 int launch_embed_rows(const bf16_t* table, const int* ids_dev, float* out_f32, bf16_t* out_bf, long rows, int D, hipStream_t s);
+
+// lm.hip.  Rows n * S + s of the QKV workspace -> layer `layer` of the cache at position pos0 + s.
+int launch_kv_store(const bf16_t* qkv, int ld, int k_col0, int v_col0, const KvCache& c, int layer, int N, int S, int Hkv, hipStream_t s);
+// One query row per (sequence, q head) (row n of the QKV workspace) over keys [first[n], len) of the cache; out [N, 2 Hkv * 128] bf16.
+int launch_decode_attention(const bf16_t* qkv, int ld, const KvCache& c, int layer, int len, bf16_t* out, int N, int Hkv, float scale,
+                            hipStream_t s);
 
 }  // namespace ace355

@@ -179,13 +179,16 @@ int ensure_workspace(EncBase* h, long rows, long in_elems, long emb_rows, int se
     return 0;
 }
 
-int encoder_layers(EncBase* h, const EncoderW& E, int N, int S, const int* kv_len_dev, bf16_t* out, hipStream_t s) {
+int encoder_layers(EncBase* h, const EncoderW& E, int N, int S, const int* kv_len_dev, bf16_t* out, hipStream_t s, const KvCache* cache) {
     const int M = N * S, D = h->D, F = h->F, QD = h->QD, KVD = h->KVD, QKV = QD + 2 * KVD;
     const int Sp = ((S + 63) / 64) * 64;
     const float eps = h->eps;
     const float scale = 1.0f / sqrtf(128.0f);
-    int rc = ensure_rope(h, S, s);
+    ACE_CHECK(!cache || (h->causal && cache->pos0 >= 0 && cache->pos0 + S <= cache->max_pos && (cache->pos0 == 0 || S == 1)),
+              "encoder_layers: KV cache position");
+    int rc = ensure_rope(h, cache ? cache->max_pos : S, s);
     if (rc) return rc;
+    const long rope0 = cache ? (long)cache->pos0 * 64 : 0;   // row s of the call is position pos0 + s
     GemmEpilogue ep{};
     for (int li = 0; li < E.n_layers; ++li) {
         const EncLayerW& W = E.layers[li];
@@ -193,12 +196,19 @@ int encoder_layers(EncBase* h, const EncoderW& E, int N, int S, const int* kv_le
         rc = launch_rmsnorm_mod(h->h, W.n_in, h->xn, M, D, eps, nullptr, nullptr, nullptr, nullptr, 0, S, s);
         if (rc) return rc;
         ep = GemmEpilogue{4, nullptr, nullptr, nullptr, 0, S};  // q / k head-norm + RoPE in the epilogue, as in the DiT
-        ep.hn_wq = W.qn, ep.hn_wk = W.kn, ep.hn_cos = h->rope_cos, ep.hn_sin = h->rope_sin;
+        ep.hn_wq = W.qn, ep.hn_wk = W.kn, ep.hn_cos = h->rope_cos + rope0, ep.hn_sin = h->rope_sin + rope0;
         ep.hn_q_cols = QD, ep.hn_qk_cols = QD + KVD, ep.hn_eps = eps;
         rc = launch_gemm(h->xn, D, W.wqkv, D, h->qkv, QKV, M, QKV, D, ep, s);
         if (rc) return rc;
         if (h->causal) {   // (a causal stack may have more layers than sliding_layer_mask has bits: the mask is not read here)
-            rc = launch_causal_attention(h->qkv, QKV, QD, QD + KVD, h->ao, QD, N, S, h->KVH, scale, s);
+            if (cache) {
+                rc = launch_kv_store(h->qkv, QKV, QD, QD + KVD, *cache, li, N, S, h->KVH, s);
+                if (rc) return rc;
+            }
+            if (cache && cache->pos0 > 0)
+                rc = launch_decode_attention(h->qkv, QKV, *cache, li, cache->pos0 + 1, h->ao, N, h->KVH, scale, s);
+            else
+                rc = launch_causal_attention(h->qkv, QKV, QD, QD + KVD, h->ao, QD, N, S, h->KVH, scale, s, cache ? cache->first_dev : nullptr);
             if (rc) return rc;
         } else {
             const bool sliding = (h->sliding_layer_mask >> li) & 1ull;

@@ -1,0 +1,438 @@
+// lm.hip - the 5 Hz LM's forward behind ace355.h: transformers' Qwen3ForCausalLM as LLMHandler._forward_pass calls
+// it (llm_inference.py:416-438) = the text encoder's stack (encoder.hip: encoder_layers, causal) run in steps over a KV cache, and the LM
+// head on the last column.  Prefill is the text encoder's pass with a per-sequence first visible key (textenc.hip, FIRST) plus the cache
+// store; a decode step is the same layer code at M = N rows, S = 1, with the attention below reading the cache.
+//
+// This file holds the cache store, the decode attention with its merge, the LM head, and the handle.  The cut of a cache into chunks is
+// lm_plan.h's, a function of the length alone.  No atomics anywhere: every result has one summation order, so the same calls give the
+// same bits, and a sequence's bits do not depend on the other sequences of the batch.
+#include <math.h>
+
+#include <string>
+#include <vector>
+
+#include "encoder.h"
+#include "lm_plan.h"
+
+using namespace ace355;
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ KV store
+// The K and V columns of QKV row n * S + s -> cache[K | V][n][kv head][pos0 + s][128]; one thread = one 16-byte piece.
+__global__ __launch_bounds__(256) void kv_store_kernel(const bf16_t* __restrict__ qkv, int ld, int k_col0, int v_col0, bf16_t* __restrict__ kc,
+                                                       bf16_t* __restrict__ vc, long seq_stride, int max_pos, int pos0, int S, int Hkv,
+                                                       long total) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int ch = (int)(idx & 15), is_v = (int)((idx >> 4) & 1);
+    long t = idx >> 5;
+    const int hk = (int)(t % Hkv);
+    t /= Hkv;
+    const int s = (int)(t % S);
+    const long n = t / S;
+    const uint4 v = ldg16(qkv + (n * S + s) * ld + (is_v ? v_col0 : k_col0) + hk * 128 + ch * 8);
+    bf16_t* dst = (is_v ? vc : kc) + n * seq_stride + ((long)hk * max_pos + pos0 + s) * 128 + ch * 8;
+    *reinterpret_cast<uint4*>(dst) = v;
+}
+
+// ------------------------------------------------------------------------------------------------ decode attention
+// One query row per (sequence, q head): out[n][hq] = softmax_{first[n] <= j < len}(scale q[n][hq] . K[n][hq/2][j]) V[n][hq/2][j].
+//
+// Bound by the K / V bytes, so VALU dot products: a workgroup takes one (chunk of keys, kv head, sequence) and BOTH q heads of that kv
+// head, and reads every K / V row of its chunk once.  256 threads = 16 key groups x 16 lanes; a lane holds 8 of the 128 head dims
+// (one 16-byte load per row), a key group walks the chunk's keys kg, kg + 16, ... with its own online softmax (running max, row sum and
+// un-normalised O for both heads).  The 16 groups are then merged through LDS in group order, and the workgroup leaves un-normalised
+// fp32 O, the max and the row sum of its chunk; decode_merge_kernel combines a sequence's chunks in chunk order, as attn.hip's kv_split
+// merge does.  Keys outside [first, len) get -inf; a group or a chunk without a visible key carries max -inf / sum 0 and is skipped by
+// the merges, so no exponential is ever taken of -inf - -inf.
+struct DecodeArgs {
+    const bf16_t* qkv;   // row n: this step's q heads (head-normed, rotated), row stride ld
+    int ld;
+    const bf16_t *kc, *vc;   // this layer's K / V: [n][kv head][max_pos][128]
+    long seq_stride;
+    int max_pos;
+    const int* first;
+    int len, chunk, Hkv;
+    float scale_log2;
+    float *part_o, *part_ml;   // [n][hq][LM_MAX_SPLITS][128], [..][2]
+};
+
+__device__ __forceinline__ void unpack8(uint4 v, float* f) {
+    f[0] = bf_lo(v.x); f[1] = bf_hi(v.x); f[2] = bf_lo(v.y); f[3] = bf_hi(v.y);
+    f[4] = bf_lo(v.z); f[5] = bf_hi(v.z); f[6] = bf_lo(v.w); f[7] = bf_hi(v.w);
+}
+
+__global__ __launch_bounds__(256) void decode_attn_kernel(DecodeArgs a) {
+    constexpr int G = LM_DECODE_KEY_GROUPS;
+    __shared__ float go[G][2][128];
+    __shared__ float gm[2][G], gl[2][G];
+    const int c = blockIdx.x, kvh = blockIdx.y, n = blockIdx.z;
+    const int tid = threadIdx.x, kg = tid >> 4, dc = tid & 15;
+    const int first = a.first[n];
+    const int k_lo = c * a.chunk, k_hi = min(a.len, k_lo + a.chunk);
+    const int Hq = 2 * a.Hkv;
+    const long pbase = ((long)n * Hq + 2 * kvh) * LM_MAX_SPLITS + c;   // head 2 kvh; head 2 kvh + 1 is LM_MAX_SPLITS further on
+
+    float q[2][8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) unpack8(ldg16(a.qkv + (long)n * a.ld + (2 * kvh + h) * 128 + dc * 8), q[h]);
+    float m[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f}, o[2][8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[h][e] = 0.f;
+
+    const bf16_t* kb = a.kc + n * a.seq_stride + (long)kvh * a.max_pos * 128 + dc * 8;
+    const bf16_t* vb = a.vc + n * a.seq_stride + (long)kvh * a.max_pos * 128 + dc * 8;
+    // rounds of 16 keys that hold a visible one (uniform over the workgroup; a skipped round would have changed nothing)
+    const int r_lo = first > k_lo ? (first - k_lo) / G : 0, r_hi = (k_hi - k_lo + G - 1) / G;
+    for (int r = r_lo; r < r_hi; ++r) {
+        const int key = k_lo + r * G + kg;
+        const long row = (long)min(key, a.len - 1) * 128;   // (rows < len are written; a clamped key is masked)
+        float kf[8], vf[8];
+        unpack8(ldg16(kb + row), kf);
+        unpack8(ldg16(vb + row), vf);
+        float s[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            float d = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) d += q[h][e] * kf[e];
+#pragma unroll
+            for (int x = 8; x > 0; x >>= 1) d += __shfl_xor(d, x, 64);   // over the key group's 16 lanes: every lane the same bits
+            s[h] = d * a.scale_log2;
+        }
+        const bool visible = key >= first && key < k_hi;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float sv = visible ? s[h] : -INFINITY;
+            const float m_new = fmaxf(m[h], sv);
+            const bool any = m_new > -INFINITY;
+            const float alpha = any ? __builtin_amdgcn_exp2f(m[h] - m_new) : 1.f;
+            const float p = any ? __builtin_amdgcn_exp2f(sv - m_new) : 0.f;
+            m[h] = m_new;
+            l[h] = l[h] * alpha + p;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[h][e] = o[h][e] * alpha + p * vf[e];
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) go[kg][h][dc * 8 + e] = o[h][e];
+        if (dc == 0) { gm[h][kg] = m[h]; gl[h][kg] = l[h]; }
+    }
+    __syncthreads();
+    // thread -> (head, dim): the 16 groups in group order
+    const int h = tid >> 7, d = tid & 127;
+    float M = -INFINITY;
+#pragma unroll
+    for (int g = 0; g < G; ++g) M = fmaxf(M, gm[h][g]);
+    float acc = 0.f, L = 0.f;
+    if (M > -INFINITY) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float w = gm[h][g] > -INFINITY ? __builtin_amdgcn_exp2f(gm[h][g] - M) : 0.f;
+            acc += w * go[g][h][d];
+            L += w * gl[h][g];
+        }
+    }
+    const long p = pbase + (long)h * LM_MAX_SPLITS;
+    a.part_o[p * 128 + d] = acc;
+    if (d == 0) { a.part_ml[p * 2] = M; a.part_ml[p * 2 + 1] = L; }
+}
+
+// out[n][hq][2t, 2t + 1] from the chunks' partials, in chunk order.  (Every sequence has a visible key - first < P <= len - so L > 0;
+// the guard only keeps a broken invariant from becoming a NaN.)
+__global__ __launch_bounds__(64) void decode_merge_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml, int splits,
+                                                          bf16_t* __restrict__ out, int o_ld) {
+    const int hq = blockIdx.x, n = blockIdx.y, t = threadIdx.x;
+    const long base = ((long)n * gridDim.x + hq) * LM_MAX_SPLITS;
+    float M = -INFINITY;
+    for (int c = 0; c < splits; ++c) M = fmaxf(M, part_ml[(base + c) * 2]);
+    float a0 = 0.f, a1 = 0.f, L = 0.f;
+    for (int c = 0; c < splits; ++c) {
+        const float mc = part_ml[(base + c) * 2];
+        if (!(mc > -INFINITY)) continue;
+        const float w = __builtin_amdgcn_exp2f(mc - M);
+        const float2 o = *reinterpret_cast<const float2*>(part_o + (base + c) * 128 + 2 * t);
+        a0 += w * o.x;
+        a1 += w * o.y;
+        L += w * part_ml[(base + c) * 2 + 1];
+    }
+    const float inv = L > 0.f ? 1.0f / L : 0.f;
+    *reinterpret_cast<uint32_t*>(out + (long)n * o_ld + hq * 128 + 2 * t) = pack_bf2(a0 * inv, a1 * inv);
+}
+
+// ------------------------------------------------------------------------------------------------ LM head
+// logits[m][v] = sum_k x[m][k] W[v][k]: x = Mr <= 16 bf16 rows (row stride x_stride: the last column of every sequence, read where the
+// final norm left it), W bf16 [V, D], fp32 accumulators and fp32 out [Mr, V].  One wave per vocabulary row, all rows of x at once, so W
+// is streamed exactly once per call; V needs no padding.  The shape of elementwise.hip's small_linear_kernel, with bf16 strided input.
+template <int MT>
+__global__ __launch_bounds__(256) void lm_head_kernel(const bf16_t* __restrict__ x, long x_stride, const bf16_t* __restrict__ W,
+                                                      float* __restrict__ out, int Mr, int V, int D) {
+    const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (v >= V) return;
+    float acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = 0.f;
+    const bf16_t* wr = W + (long)v * D;
+    for (int k0 = lane * 8; k0 < D; k0 += 512) {
+        float wf[8];
+        unpack8(ldg16(wr + k0), wf);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            if (m < Mr) {
+                float xf[8];
+                unpack8(ldg16(x + m * x_stride + k0), xf);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[m] += wf[e] * xf[e];
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = wave_sum(acc[m]);
+    if (lane == 0) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+            if (m < Mr) out[(long)m * V + v] = acc[m];
+    }
+}
+
+int launch_lm_head(const bf16_t* x, long x_stride, const bf16_t* W, float* out, int Mr, int V, int D, hipStream_t s) {
+    ACE_CHECK(Mr > 0 && Mr <= LM_MAX_SEQS && V > 0 && D % 8 == 0 && x_stride % 8 == 0, "lm head: sizes");
+    hipLaunchKernelGGL(lm_head_kernel<LM_MAX_SEQS>, dim3((V + 3) / 4), dim3(256), 0, s, x, x_stride, W, out, Mr, V, D);
+    ACE_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+int ace355::launch_kv_store(const bf16_t* qkv, int ld, int k_col0, int v_col0, const KvCache& c, int layer, int N, int S, int Hkv,
+                            hipStream_t s) {
+    ACE_CHECK(c.kv && N > 0 && N <= c.max_seqs && S > 0 && c.pos0 >= 0 && c.pos0 + S <= c.max_pos && layer >= 0, "kv store: cache bounds");
+    ACE_CHECK(ld % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0, "kv store: 16-byte rows");
+    const long slab = c.slab(Hkv), total = (long)N * S * Hkv * 32;
+    bf16_t* kc = c.kv + (long)layer * 2 * slab;
+    hipLaunchKernelGGL(kv_store_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, ld, k_col0, v_col0, kc, kc + slab,
+                       (long)Hkv * c.max_pos * 128, c.max_pos, c.pos0, S, Hkv, total);
+    ACE_LAUNCH_CHECK();
+    return 0;
+}
+
+int ace355::launch_decode_attention(const bf16_t* qkv, int ld, const KvCache& c, int layer, int len, bf16_t* out, int N, int Hkv, float scale,
+                                    hipStream_t s) {
+    ACE_CHECK(c.kv && c.first_dev && c.part_o && c.part_ml && N > 0 && N <= c.max_seqs && Hkv > 0 && len > 0 && len <= c.max_pos &&
+                  layer >= 0, "decode attention: cache bounds");
+    ACE_CHECK(ld % 8 == 0, "decode attention: 16-byte rows");
+    const LmDecodePlan p = plan_lm_decode(len);
+    ACE_CHECK(p.splits >= 1 && p.splits <= LM_MAX_SPLITS && p.chunk % LM_DECODE_KEY_GROUPS == 0, "decode attention: plan");
+    const long slab = c.slab(Hkv);
+    const bf16_t* kc = c.kv + (long)layer * 2 * slab;
+    DecodeArgs a{qkv, ld, kc, kc + slab, (long)Hkv * c.max_pos * 128, c.max_pos, c.first_dev, len, p.chunk, Hkv,
+                 scale * 1.4426950408889634f, c.part_o, c.part_ml};
+    hipLaunchKernelGGL(decode_attn_kernel, dim3(p.splits, Hkv, N), dim3(256), 0, s, a);
+    ACE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(decode_merge_kernel, dim3(2 * Hkv, N), dim3(64), 0, s, c.part_o, c.part_ml, p.splits, out, 2 * Hkv * 128);
+    ACE_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the handle
+struct ace355_lm : EncBase {
+    ace355_lm_config cfg;
+    bf16_t* embed = nullptr;   // [vocab][D]
+    bf16_t* head = nullptr;    // [vocab][D]; the embedding table when the checkpoint ties them
+    EncoderW enc;
+    int* ids_dev = nullptr;
+    long ids_cap = 0;
+    int* first_dev = nullptr;  // [max_seqs]
+    KvCache cache;             // allocated at the first prefill, kept for the handle's life
+    int n_seqs = 0, length = 0;
+};
+
+namespace {
+
+bool lm_resolve(ace355_lm* h, const std::string& name, PackDest* d) {
+    const long D = h->D, V = h->cfg.vocab_size;
+    if (name == "lm_head.weight") {
+        *d = pack_rows(h->head, 1, V, D, D, 0);
+        d->ignore = h->cfg.tie_word_embeddings != 0;   // the same tensor as the embedding table: one copy
+        return true;
+    }
+    if (name.compare(0, 6, "model.") != 0) return false;
+    if (name == "model.embed_tokens.weight") { *d = pack_rows(h->embed, 1, V, D, D, 0); return true; }
+    if (name == "model.norm.weight") { *d = pack_rows(h->enc.norm, 0, 1, D, D, 0); return true; }
+    return resolve_encoder_layers(*h, h->enc, name, 6, d);
+}
+
+int lm_check_ids(const ace355_lm* h, const int32_t* ids, long n, const char* who) {
+    for (long i = 0; i < n; ++i) {
+        if (ids[i] < 0 || ids[i] >= h->cfg.vocab_size) {
+            set_error(std::string(who) + ": token id " + std::to_string(ids[i]) + " at position " + std::to_string(i) + " outside [0, " +
+                      std::to_string(h->cfg.vocab_size) + ")");
+            return ACE355_ERR_INVALID;
+        }
+    }
+    return 0;
+}
+
+int lm_refuse(const std::string& msg) {
+    set_error(msg);
+    return ACE355_ERR_INVALID;
+}
+
+// checked host ids -> the handle's device buffer (the caller's array may be reused as soon as this returns)
+int lm_upload_ids(ace355_lm* h, const int32_t* ids, long n, hipStream_t s) {
+    if (n > h->ids_cap) {
+        ACE_HIP(hipStreamSynchronize(s));
+        if (h->ids_dev) hipFree(h->ids_dev);
+        h->ids_dev = nullptr;
+        h->ids_cap = 0;
+        ACE_HIP(hipMalloc((void**)&h->ids_dev, sizeof(int) * n + 256));
+        h->ids_cap = n;
+    }
+    ACE_HIP(hipMemcpyAsync(h->ids_dev, ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    ACE_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int lm_ensure_cache(ace355_lm* h) {
+    if (h->cache.kv) return 0;
+    KvCache& c = h->cache;
+    c.max_seqs = h->cfg.max_seqs;
+    c.max_pos = h->cfg.max_positions;
+    ALLOC(h->allocs, c.kv, (size_t)h->cfg.num_layers * 2 * c.slab(h->KVH));
+    ALLOC(h->allocs, c.part_o, (size_t)c.max_seqs * h->HQ * LM_MAX_SPLITS * 128);
+    ALLOC(h->allocs, c.part_ml, (size_t)c.max_seqs * h->HQ * LM_MAX_SPLITS * 2);
+    ALLOC(h->allocs, h->first_dev, (size_t)c.max_seqs);
+    c.first_dev = h->first_dev;
+    return 0;
+}
+
+// the stack over N x S rows at position pos0 (h->h embedded from ids_dev), and the head on every sequence's last row
+int lm_run(ace355_lm* h, int N, int S, int pos0, float* logits_dev, hipStream_t s) {
+    const long M = (long)N * S;
+    int rc = ensure_workspace(h, M, 0, 0, 0, 0, s);
+    if (!rc) rc = launch_embed_rows(h->embed, h->ids_dev, h->h, nullptr, M, h->D, s);
+    if (rc) return rc;
+    h->cache.pos0 = pos0;
+    rc = encoder_layers(h, h->enc, N, S, nullptr, h->xn, s, &h->cache);   // final norm of every row -> xn (bf16 [M, D])
+    if (rc) return rc;
+    return launch_lm_head(h->xn + (long)(S - 1) * h->D, (long)S * h->D, h->head, logits_dev, N, h->cfg.vocab_size, h->D, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ace355_lm_create(const ace355_lm_config* cfg, ace355_lm** out) {
+    ACE_CHECK(cfg && out, "lm_create: null argument");
+    if (cfg->head_dim != 128 || cfg->num_kv_heads <= 0 || cfg->num_heads != 2 * cfg->num_kv_heads) {
+        set_error("lm_create: only head_dim 128 with num_heads == 2 * num_kv_heads is supported");
+        return ACE355_ERR_UNSUPPORTED;
+    }
+    ACE_CHECK(cfg->hidden_size > 0 && cfg->hidden_size % 256 == 0 && cfg->intermediate_size > 0 && cfg->intermediate_size % 64 == 0,
+              "lm_create: hidden/intermediate size");
+    ACE_CHECK(cfg->num_layers >= 0 && cfg->num_layers <= 256 && cfg->vocab_size > 0, "lm_create: layer count / vocabulary");
+    ACE_CHECK(cfg->max_seqs >= 1 && cfg->max_seqs <= LM_MAX_SEQS, "lm_create: max_seqs must be 1 .. 16");
+    ACE_CHECK(cfg->max_positions >= 1 && cfg->max_positions <= LM_MAX_POSITIONS, "lm_create: max_positions must be 1 .. 16384");
+    static_assert(LM_MAX_SEQS == ACE355_LM_MAX_SEQS && LM_MAX_POSITIONS == ACE355_LM_MAX_POSITIONS, "lm_plan.h and ace355.h agree");
+    ace355_lm* h = new ace355_lm();
+    h->cfg = *cfg;
+    enc_init(h, cfg->hidden_size, cfg->intermediate_size, cfg->num_heads, cfg->num_kv_heads, 0, 0, cfg->rms_norm_eps, cfg->rope_theta);
+    h->causal = true;
+    const bool tied = cfg->tie_word_embeddings != 0;
+    int rc = dev_alloc(h->allocs, &h->embed, (size_t)cfg->vocab_size * h->D);
+    if (!rc && !tied) rc = dev_alloc(h->allocs, &h->head, (size_t)cfg->vocab_size * h->D);
+    if (!rc) rc = alloc_encoder(h, h->enc, cfg->num_layers, 0);
+    if (rc) { ace355_lm_destroy(h); return rc; }
+    if (tied) h->head = h->embed;
+    h->expected_tensors = 2 + (tied ? 0 : 1) + (size_t)cfg->num_layers * 11;
+    *out = h;
+    return ACE355_OK;
+}
+
+void ace355_lm_destroy(ace355_lm* h) {
+    if (!h) return;
+    hipDeviceSynchronize();
+    free_encoder(h);
+    if (h->ids_dev) hipFree(h->ids_dev);
+    delete h;
+}
+
+int ace355_lm_load_tensor(ace355_lm* h, const char* name, const void* data, int dtype, int64_t numel, int is_device) {
+    ACE_CHECK(h && name && data, "lm_load_tensor: null argument");
+    ACE_CHECK(dtype == ACE355_DTYPE_F32 || dtype == ACE355_DTYPE_BF16, "lm_load_tensor: dtype");
+    PackDest d;
+    if (!lm_resolve(h, name, &d)) return unknown_tensor("lm_load_tensor", name);
+    return load_packed(h, d, name, data, dtype, numel, is_device, "lm_load_tensor");
+}
+
+int ace355_lm_finalize(ace355_lm* h) {
+    ACE_CHECK(h, "lm_finalize: null handle");
+    return finalize_loaded(h, "lm_finalize");
+}
+
+int ace355_lm_prefill(ace355_lm* h, const int32_t* ids_host, const int32_t* first_host, int N, int P, float* logits_dev, void* stream) {
+    ACE_CHECK(h && ids_host && first_host && logits_dev, "lm_prefill: null argument");
+    if (!h->finalized) { set_error("lm_prefill: call ace355_lm_finalize first"); return ACE355_ERR_STATE; }
+    ACE_CHECK(N > 0 && P > 0, "lm_prefill: sizes");
+    if (N > h->cfg.max_seqs)
+        return lm_refuse("lm_prefill: " + std::to_string(N) + " sequences, the handle holds max_seqs = " + std::to_string(h->cfg.max_seqs));
+    if (P > h->cfg.max_positions)
+        return lm_refuse("lm_prefill: " + std::to_string(P) + " positions, the handle holds max_positions = " +
+                         std::to_string(h->cfg.max_positions));
+    if ((long)N * P > ACE355_LM_MAX_TOKENS)
+        return lm_refuse("lm_prefill: N * P = " + std::to_string((long)N * P) + " tokens in one prefill, at most " +
+                         std::to_string(ACE355_LM_MAX_TOKENS));
+    for (int n = 0; n < N; ++n)
+        if (first_host[n] < 0 || first_host[n] >= P)
+            return lm_refuse("lm_prefill: first[" + std::to_string(n) + "] = " + std::to_string(first_host[n]) + " outside [0, " +
+                             std::to_string(P) + ")");
+    int rc = lm_check_ids(h, ids_host, (long)N * P, "lm_prefill");
+    if (rc) return rc;
+    // nothing was refused: from here on the previous generation is gone
+    hipStream_t s = (hipStream_t)stream;
+    h->length = 0;
+    h->n_seqs = 0;
+    rc = lm_ensure_cache(h);
+    if (!rc) rc = lm_upload_ids(h, ids_host, (long)N * P, s);
+    if (rc) return rc;
+    ACE_HIP(hipMemcpyAsync(h->first_dev, first_host, sizeof(int) * N, hipMemcpyHostToDevice, s));
+    ACE_HIP(hipStreamSynchronize(s));   // `first_host` is caller memory
+    rc = lm_run(h, N, P, 0, logits_dev, s);
+    if (rc) return rc;
+    h->n_seqs = N;
+    h->length = P;
+    return ACE355_OK;
+}
+
+int ace355_lm_decode(ace355_lm* h, const int32_t* ids_host, float* logits_dev, void* stream) {
+    ACE_CHECK(h && ids_host && logits_dev, "lm_decode: null argument");
+    if (h->length <= 0 || h->n_seqs <= 0) return lm_refuse("lm_decode: no prefill to continue from");
+    if (h->length >= h->cfg.max_positions)
+        return lm_refuse("lm_decode: the cache is full (length " + std::to_string(h->length) + " = max_positions)");
+    int rc = lm_check_ids(h, ids_host, h->n_seqs, "lm_decode");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = lm_upload_ids(h, ids_host, h->n_seqs, s);
+    if (!rc) rc = lm_run(h, h->n_seqs, 1, h->length, logits_dev, s);
+    if (rc) { h->length = 0; h->n_seqs = 0; return rc; }   // a failed launch: the cache is not trustworthy
+    h->length += 1;
+    return ACE355_OK;
+}
+
+int ace355_lm_length(ace355_lm* h) { return h ? h->length : -1; }
+
+int ace355_lm_decode_plan(int length, int32_t* chunk_out, int32_t* splits_out) {
+    ACE_CHECK(length >= 1 && length <= LM_MAX_POSITIONS && chunk_out && splits_out, "lm_decode_plan: length must be 1 .. 16384");
+    const LmDecodePlan p = plan_lm_decode(length);
+    *chunk_out = p.chunk;
+    *splits_out = p.splits;
+    return ACE355_OK;
+}
+
+}  // extern "C"

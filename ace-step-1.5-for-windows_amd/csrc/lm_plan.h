@@ -1,0 +1,28 @@
+// lm_plan.h - the launch decision of the LM's decode attention (lm.hip) as data, in the shape of attn_plan.h / gemm_plan.h: how the keys
+// [0, len) of one sequence are cut into chunks, one workgroup per (sequence, kv head, chunk), merged afterwards in chunk order.
+// plan_lm_decode is a pure function of the current length ALONE: it reads no global, no environment, makes no HIP call, and does not see
+// the number of sequences - so the bits of a sequence's logits do not depend on how many others decode beside it.
+#pragma once
+
+namespace ace355 {
+
+constexpr int LM_MAX_SEQS = 16;            // lm_batch_chunk_size 8, doubled by CFG
+constexpr int LM_MAX_POSITIONS = 16384;    // the longest cache a handle may be created for (the last regime below ends here)
+constexpr int LM_MAX_SPLITS = 64;          // chunks of one sequence at LM_MAX_POSITIONS
+constexpr int LM_DECODE_KEY_GROUPS = 16;   // keys a workgroup of decode_attn_kernel has in flight (16 lanes x 8 dims each)
+
+struct LmDecodePlan {
+    int chunk;    // keys per workgroup, a multiple of LM_DECODE_KEY_GROUPS
+    int splits;   // chunks of one sequence = ceil(len / chunk) <= LM_MAX_SPLITS; chunk c holds keys [c * chunk, min(len, (c + 1) * chunk))
+};
+
+// Three regimes: short caches are cut finely so that a two-sequence CFG pair still spreads over the chip (2 x 8 kv heads x splits
+// workgroups), long ones coarsely so that the merge stays short.  A workgroup reads chunk x 512 bytes of K and V: 32 / 64 / 128 KB.
+inline LmDecodePlan plan_lm_decode(int len) {
+    LmDecodePlan p{};
+    p.chunk = len <= 256 ? 64 : len <= 1024 ? 128 : 256;
+    p.splits = len > 0 ? (len + p.chunk - 1) / p.chunk : 0;
+    return p;
+}
+
+}  // namespace ace355

@@ -30,6 +30,11 @@ namespace {
 // only, where masked scores are -inf, so their probabilities are exactly 0.  Reads past the sequence end are clamped to row S - 1 (real,
 // finite data whose probability is 0 for every stored row), rows >= S are not stored.  Everything else is fixed-order: bit-reproducible.
 //
+// FIRST (the LM's left-padded batches, lm.hip): sequence n sees keys k_first[n] <= j <= s only.  Key tiles wholly below k_first[n] are
+// skipped, the tile that holds it gets a per-element predicate like the diagonal one, and a query row with no visible key (a pad row)
+// has a running max of -inf throughout: its exponentials are taken against 0 instead, its row sum stays 0, and it stores zeros.  Without
+// FIRST the kernel is the text encoder's, instruction for instruction.
+//
 // MFMA 16x16x32 bf16 on transposed problems, so that the score accumulator IS the B operand of the PV product with no lane movement:
 //   S^T[key][q] = K Q^T:   A = K rows (lane l: key l&15, dims 8(l>>4) .. + 7 of a 32-dim chunk), B = Q rows (q l&15, the same dims)
 //                          C: lane l, reg r = S^T[key 4(l>>4) + r][q l&15]
@@ -47,12 +52,14 @@ struct CausalArgs {
     int o_ld;
     int S, Hkv;
     float scale_log2;   // softmax scale * log2(e)
+    const int* k_first; // FIRST only: [N]
 };
 
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
+template <bool FIRST>
 __global__ __launch_bounds__(CA_THREADS) void causal_gqa_attn_kernel(CausalArgs a) {
     __shared__ __attribute__((aligned(16))) bf16_t Ks[CA_KB * CA_LDK];
     __shared__ __attribute__((aligned(16))) bf16_t Vt[128 * CA_LDV];
@@ -73,8 +80,10 @@ __global__ __launch_bounds__(CA_THREADS) void causal_gqa_attn_kernel(CausalArgs 
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
+    int first = 0;
+    if constexpr (FIRST) first = a.k_first[n];
 
-    for (int kt = 0; kt <= qb; ++kt) {
+    for (int kt = first / CA_KB; kt <= qb; ++kt) {
         __syncthreads();   // the previous tile's LDS reads are done
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -110,14 +119,19 @@ __global__ __launch_bounds__(CA_THREADS) void causal_gqa_attn_kernel(CausalArgs 
             for (int r = 0; r < 4; ++r) {
                 float v = sc[mt][r] * a.scale_log2;
                 if (diag && kt * CA_KB + mt * 16 + g * 4 + r > q_abs) v = -INFINITY;
+                if constexpr (FIRST) {
+                    if (kt * CA_KB + mt * 16 + g * 4 + r < first) v = -INFINITY;
+                }
                 sc[mt][r] = v;
                 mx = fmaxf(mx, v);
             }
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);   // finite: key 0 of tile 0 is visible to every query
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        float m_new = fmaxf(m_run, mx);   // finite: key 0 of tile 0 is visible to every query (FIRST: to every row that is not a pad)
+        const float m_old = m_run;
         m_run = m_new;
+        if constexpr (FIRST) m_new = m_new == -INFINITY ? 0.f : m_new;   // a pad row so far: exp2(-inf - 0) = 0, never -inf - -inf
+        const float alpha = __builtin_amdgcn_exp2f(m_old - m_new);
         float ps = 0.f;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
@@ -147,7 +161,8 @@ __global__ __launch_bounds__(CA_THREADS) void causal_gqa_attn_kernel(CausalArgs 
     l_run += __shfl_xor(l_run, 16, 64);
     l_run += __shfl_xor(l_run, 32, 64);
     if (q_abs >= S) return;
-    const float inv = 1.0f / l_run;
+    float inv = 1.0f / l_run;
+    if constexpr (FIRST) inv = l_run > 0.f ? inv : 0.f;   // a pad row: zeros
     bf16_t* op = a.out + (row0 + q_abs) * a.o_ld + hq * 128 + g * 4;
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt)
@@ -176,11 +191,13 @@ __global__ __launch_bounds__(128) void embed_rows_kernel(const bf16_t* __restric
 }  // namespace
 
 int ace355::launch_causal_attention(const bf16_t* qkv, int ld, int k_col0, int v_col0, bf16_t* out, int o_ld, int N, int S, int Hkv, float scale,
-                                    hipStream_t s) {
+                                    hipStream_t s, const int* k_first_dev) {
     ACE_CHECK(N > 0 && S > 0 && Hkv > 0 && N <= 65535 && Hkv <= 65535, "causal attention: sizes");
     ACE_CHECK(ld % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0 && o_ld % 4 == 0, "causal attention: 16-byte rows");
-    CausalArgs a{qkv, ld, k_col0, v_col0, out, o_ld, S, Hkv, scale * 1.4426950408889634f};
-    hipLaunchKernelGGL(causal_gqa_attn_kernel, dim3((S + CA_QB - 1) / CA_QB, Hkv, N), dim3(CA_THREADS), 0, s, a);
+    CausalArgs a{qkv, ld, k_col0, v_col0, out, o_ld, S, Hkv, scale * 1.4426950408889634f, k_first_dev};
+    const dim3 grid((S + CA_QB - 1) / CA_QB, Hkv, N);
+    if (k_first_dev) hipLaunchKernelGGL(causal_gqa_attn_kernel<true>, grid, dim3(CA_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(causal_gqa_attn_kernel<false>, grid, dim3(CA_THREADS), 0, s, a);
     ACE_LAUNCH_CHECK();
     return 0;
 }

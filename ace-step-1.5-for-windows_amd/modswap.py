@@ -125,6 +125,45 @@ def swap_in_text_encoder(parent, device, attr: str = "text_encoder") -> NativeTe
     return wrapper
 
 
+class NativeCausalLMSwap(NativeModuleSwap):
+    """``NativeModuleSwap`` for the 5 Hz LM (``LLMHandler.llm``, a ``Qwen3ForCausalLM``), whose forward carries state from call to call.
+    The dispatch is on ``past_key_values``: none -> native prefill; the native LM's own token -> native decode; anything else (a cache
+    the kept module returned) -> the kept module.  A prefill the native LM refuses (ValueError / RuntimeError / NotImplementedError) runs
+    on the kept module, which returns its own cache, so the steps that follow route to it by themselves.  An error inside a native decode
+    step propagates: there is no PyTorch cache to continue from.  ``generate``, ``config``, ``generation_config``, ``device`` and every
+    other attribute are the kept module's (base class ``__getattr__``), so the non-CFG ``generate()`` path is unchanged."""
+
+    def forward(self, input_ids=None, attention_mask=None, past_key_values=None, **kwargs):
+        from .lm import KvToken
+        if past_key_values is not None and not isinstance(past_key_values, KvToken):
+            return self._reference(input_ids=input_ids, attention_mask=attention_mask, past_key_values=past_key_values, **kwargs)
+        if past_key_values is not None:
+            out = self._native(input_ids=input_ids, attention_mask=attention_mask, past_key_values=past_key_values, **kwargs)
+            self.native_calls += 1
+            return out
+        try:
+            out = self._native(input_ids=input_ids, attention_mask=attention_mask, **kwargs)
+            self.native_calls += 1
+            return out
+        except (ValueError, RuntimeError, NotImplementedError) as exc:
+            self.native_failures += 1
+            if self.native_failures <= 3:
+                logger.warning("[native-%s] %s: %s; running this generation on the PyTorch module", self._swap_name, type(exc).__name__, exc)
+            return self._reference(input_ids=input_ids, attention_mask=attention_mask, **kwargs)
+
+
+def swap_in_lm(parent, device, attr: str = "llm", max_positions: int = 8192) -> NativeCausalLMSwap:
+    """``parent.<attr> = NativeCausalLMSwap(NativeCausalLM.from_reference(parent.<attr>), parent.<attr>)``; logits in the module's own
+    dtype.  Raises whatever ``from_reference`` raises (the caller logs and keeps the PyTorch module)."""
+    from .lm import NativeCausalLM
+    ref = getattr(parent, attr)
+    if isinstance(ref, NativeModuleSwap):  # re-entry
+        ref = ref._reference
+    wrapper = NativeCausalLMSwap(NativeCausalLM.from_reference(ref, device, max_positions=max_positions), ref, attr)
+    setattr(parent, attr, wrapper)
+    return wrapper
+
+
 def swap_in(parent: torch.nn.Module, attr: str, native_cls, device, out_dtype: torch.dtype = torch.float32) -> NativeModuleSwap:
     """``parent.<attr> = NativeModuleSwap(native_cls.from_reference(parent.<attr>), parent.<attr>)``; returns the wrapper.
     Raises whatever ``from_reference`` raises (caller logs and keeps the PyTorch module, like ``_init_native_dit``)."""

@@ -66,6 +66,13 @@ class TextEncConfigC(C.Structure):
     ]
 
 
+class LmConfigC(C.Structure):
+    _fields_ = TextEncConfigC._fields_ + [("tie_word_embeddings", C.c_int32), ("max_seqs", C.c_int32), ("max_positions", C.c_int32)]
+
+
+LM_MAX_SEQS, LM_MAX_POSITIONS, LM_MAX_TOKENS = 16, 16384, 65536   # ACE355_LM_MAX_*
+
+
 class VaeConfigC(C.Structure):
     _fields_ = [
         ("decoder_channels", C.c_int32), ("decoder_input_channels", C.c_int32), ("audio_channels", C.c_int32),
@@ -316,6 +323,14 @@ SIGNATURES = {
     "ace355_textenc_finalize": (C.c_int, [C.c_void_p]),
     "ace355_textenc_encode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ace355_textenc_embed": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64, C.c_void_p, C.c_void_p]),
+    "ace355_lm_create": (C.c_int, [C.POINTER(LmConfigC), C.POINTER(C.c_void_p)]),
+    "ace355_lm_destroy": (None, [C.c_void_p]),
+    "ace355_lm_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int64, C.c_int]),
+    "ace355_lm_finalize": (C.c_int, [C.c_void_p]),
+    "ace355_lm_prefill": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ace355_lm_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "ace355_lm_length": (C.c_int, [C.c_void_p]),
+    "ace355_lm_decode_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ace355_peak_normalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "ace355_latent_check": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_void_p]),
     "ace355_normalize_audio": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
@@ -424,6 +439,14 @@ def attn_plan(N: int, Sq: int, Skv: int, Hq: int, Hkv: int, window: int = -1, **
     out = AttnPlanInfoC()
     check(lib().ace355_attn_plan(C.byref(rq), C.byref(out)), "attn_plan")
     return {**{n: int(getattr(out, n)) for n, _t in AttnPlanInfoC._fields_}, "kernel": ATTN_KERNELS[out.kernel]}
+
+
+def lm_decode_plan(length: int) -> dict:
+    """`ace355_lm_decode_plan` (include/ace355.h): how the LM's decode attention cuts a cache of ``length`` keys - keys per workgroup
+    (``chunk``) and chunks per sequence (``splits``).  A function of the length alone; no GPU, no handle."""
+    chunk, splits = C.c_int32(), C.c_int32()
+    check(lib().ace355_lm_decode_plan(int(length), C.byref(chunk), C.byref(splits)), "lm_decode_plan")
+    return {"chunk": chunk.value, "splits": splits.value}
 
 
 def conv_plan(B: int, M: int, N: int, Cin: int, taps: int, **bits) -> dict:

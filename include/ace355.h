@@ -791,6 +791,58 @@ int ace355_textenc_encode(ace355_textenc* h, const int32_t* ids_host, int N, int
 int ace355_textenc_embed(ace355_textenc* h, const int32_t* ids_host, int64_t n, void* out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 5 Hz LM forward: transformers' Qwen3ForCausalLM (0.6B / 1.7B) as LLMHandler._forward_pass calls it
+ * (llm_inference.py:416-438) = the text encoder's stack + a KV cache + the LM head, for left-padded batches of N <= 16 sequences
+ * that advance one token per step.  Only the forward: the caller samples from the returned last-position logits.
+ *
+ * Positions are padded column indices (no position_ids are passed, so pads are not subtracted): the token in column j has RoPE
+ * position j, and the query in column i of sequence n sees keys first[n] <= j <= i, first[n] = number of leading pad columns.
+ * Pad columns' K / V are stored and never visible; their outputs are zeros or finite and never read.
+ * Cache: bf16 [layer][K|V][max_seqs][kv head][max_positions][128], allocated at the first prefill, kept for the handle's life.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ace355_lm ace355_lm;
+
+#define ACE355_LM_MAX_SEQS 16         /* lm_batch_chunk_size 8, doubled by CFG */
+#define ACE355_LM_MAX_POSITIONS 16384 /* largest max_positions */
+#define ACE355_LM_MAX_TOKENS 65536    /* N * P of one prefill */
+
+typedef struct ace355_lm_config {
+    int32_t hidden_size;        /* 1024 (0.6B), 2048 (1.7B) */
+    int32_t intermediate_size;  /* 3072, 6144 */
+    int32_t num_layers;         /* 28 */
+    int32_t num_heads;          /* 16: must be 2 * num_kv_heads */
+    int32_t num_kv_heads;       /* 8 */
+    int32_t head_dim;           /* 128 (only value supported) */
+    int32_t vocab_size;         /* Qwen3's vocabulary plus the audio-code tokens: whatever the checkpoint says */
+    float rms_norm_eps;         /* 1e-6 */
+    float rope_theta;           /* 1e6 */
+    int32_t tie_word_embeddings; /* 1: the head reads embed_tokens.weight; "lm_head.weight" is accepted and dropped */
+    int32_t max_seqs;           /* 1 .. ACE355_LM_MAX_SEQS */
+    int32_t max_positions;      /* 1 .. ACE355_LM_MAX_POSITIONS: prompt + generated tokens */
+} ace355_lm_config;
+
+/* ACE355_ERR_UNSUPPORTED for head_dim != 128 or num_heads != 2 * num_kv_heads (Qwen3-4B, 32 / 8 heads, stays on PyTorch). */
+int ace355_lm_create(const ace355_lm_config* cfg, ace355_lm** out);
+void ace355_lm_destroy(ace355_lm* h);
+/* name = a key of Qwen3ForCausalLM.state_dict(): "model.embed_tokens.weight", "model.layers.<i>.*", "model.norm.weight",
+ * "lm_head.weight".  Same contract as ace355_dit_load_tensor. */
+int ace355_lm_load_tensor(ace355_lm* h, const char* name, const void* data, int dtype, int64_t numel, int is_device);
+int ace355_lm_finalize(ace355_lm* h);
+/* Step 0: resets the cache, runs ids host int32 [N, P] (first host int32 [N]: leading pad columns per sequence), stores every
+ * layer's K / V, leaves the length at P and writes the logits of column P - 1: logits dev f32 [N, vocab].  ACE355_ERR_INVALID
+ * before anything is launched, with the handle unchanged, for ids outside [0, vocab), first[n] outside [0, P), N > max_seqs,
+ * P > max_positions, N * P > ACE355_LM_MAX_TOKENS.  ids and first are copied before the call returns. */
+int ace355_lm_prefill(ace355_lm* h, const int32_t* ids_host, const int32_t* first_host, int N, int P, float* logits_dev, void* stream);
+/* Step t > 0: one more position for all N sequences of the prefill, ids host int32 [N]; logits dev f32 [N, vocab].  Refused like
+ * prefill for bad ids, without a prefill and at length == max_positions. */
+int ace355_lm_decode(ace355_lm* h, const int32_t* ids_host, float* logits_dev, void* stream);
+/* Positions held by the cache (0 before the first prefill); < 0 for a null handle. */
+int ace355_lm_length(ace355_lm* h);
+/* The decode attention's cut of a cache of `length` keys (csrc/lm_plan.h): keys per workgroup and chunks per sequence.  A pure
+ * function of the length alone - no GPU, no handle. */
+int ace355_lm_decode_plan(int length, int32_t* chunk_out, int32_t* splits_out);
+
+/* ------------------------------------------------------------------------------------------
  * Audio-token detokenizer of the LM-hint path: AudioTokenDetokenizer.forward,
  * base.py:886-994, as called by _decode_audio_codes_to_latents (handler/audio_codes.py:49-66) and by
  * prepare_condition (base.py:1646-1647).  Input = the quantizer's output for the 5 Hz audio codes, output =
