@@ -35,6 +35,7 @@ logger = logging.getLogger("ace355")
 
 MAX_BATCH_SIZE = 8  # handler/service_generate_request.py:12
 _ALIGN_POST_ENV = os.environ.get("ACE355_ALIGN_POST", "") == "1"   # read once: the default of NativeDitMixin.native_lyric_post
+_LM_SAMPLER_ENV = os.environ.get("ACE355_LM_SAMPLER", "") == "1"   # read once: the default of NativeLmMixin.use_native_lm_sampler
 
 
 class NativeDitMixin:
@@ -500,6 +501,53 @@ class NativeLmMixin:
             logger.warning("[native-lm] init failed (%s: %s); PyTorch path stays active", type(exc).__name__, exc)
             self.use_native_lm = False
             return False
+
+    # ------------------------------------------------------------------ token selection (opt-in)
+    # The reference's loops call _apply_top_k_filter, _apply_top_p_filter and _sample_tokens in that order on one tensor
+    # (llm_inference.py:2380-2384, :2496-2500, :3646-3650).  With ``use_native_lm_sampler`` the two filters only note what they were asked
+    # for and ``_sample_tokens`` does all three in one native call (ace355.lmsample): same distribution, a different draw per seed, which
+    # is why it is opt-in; ACE355_LM_SAMPLER=1 turns it on for every host.  Off, or for a tensor that is not on the GPU, nothing changes.
+    use_native_lm_sampler: bool = _LM_SAMPLER_ENV
+    _lm_sampler_record = None      # [tensor, k, p]: filters deferred for exactly this tensor object
+    _lm_sampler_failures = 0
+
+    def _lm_sampler_takes(self, logits) -> bool:
+        return bool(self.use_native_lm_sampler) and isinstance(logits, torch.Tensor) and logits.is_cuda
+
+    def _lm_sampler_note(self, logits):
+        rec = self._lm_sampler_record
+        if rec is None or rec[0] is not logits:   # a record for a different tensor is dropped, never applied
+            rec = self._lm_sampler_record = [logits, None, None]
+        return rec
+
+    def _apply_top_k_filter(self, logits, top_k):
+        if not self._lm_sampler_takes(logits):
+            return super()._apply_top_k_filter(logits, top_k)
+        self._lm_sampler_record = None   # top-k opens a step: whatever was noted before belongs to another one
+        self._lm_sampler_note(logits)[1] = top_k
+        return logits
+
+    def _apply_top_p_filter(self, logits, top_p):
+        if not self._lm_sampler_takes(logits):
+            return super()._apply_top_p_filter(logits, top_p)
+        self._lm_sampler_note(logits)[2] = top_p
+        return logits
+
+    def _sample_tokens(self, logits, temperature):
+        rec, self._lm_sampler_record = self._lm_sampler_record, None
+        if not self._lm_sampler_takes(logits):
+            return super()._sample_tokens(logits, temperature)
+        top_k, top_p = (rec[1], rec[2]) if rec is not None and rec[0] is logits else (None, None)   # else: the caller filtered elsewhere
+        try:
+            from .lmsample import select_tokens
+            return select_tokens(logits, top_k, top_p, temperature)
+        except Exception as exc:
+            if self._lm_sampler_failures < 3:
+                logger.warning("[native-lm-sampler] %s: %s; this step runs on the PyTorch path", type(exc).__name__, exc)
+            self._lm_sampler_failures += 1
+            logits = super()._apply_top_k_filter(logits, top_k)   # the deferred filters first
+            logits = super()._apply_top_p_filter(logits, top_p)
+            return super()._sample_tokens(logits, temperature)
 
 
 class _ModelShell:

@@ -25,4 +25,24 @@ inline LmDecodePlan plan_lm_decode(int len) {
     return p;
 }
 
+// ------------------------------------------------------------------------------------------------ token selection (lm_sample.hip)
+// How one row of V logits is cut over workgroups: chunk c holds ids [c * chunk, min(V, (c + 1) * chunk)), per-chunk partials are combined
+// in chunk order.  A pure function of V ALONE (not of the number of rows), so a row's sums have one order whatever runs beside it.  One
+// regime: 8192 ids (32 KB) per workgroup - a row of the real vocabulary (217 205) is 27 workgroups, 16 rows are 432.
+constexpr int LM_PICK_MAX_V = 1 << 20;
+constexpr int LM_PICK_CHUNK = 8192;
+constexpr int LM_PICK_MAX_CHUNKS = LM_PICK_MAX_V / LM_PICK_CHUNK;   // 128
+
+struct LmPickPlan {
+    int chunk;    // ids per workgroup
+    int chunks;   // ceil(V / chunk) <= LM_PICK_MAX_CHUNKS; 0 for V outside 1 .. LM_PICK_MAX_V
+};
+
+inline LmPickPlan plan_lm_pick(int V) {
+    LmPickPlan p{};
+    p.chunk = LM_PICK_CHUNK;
+    p.chunks = V >= 1 && V <= LM_PICK_MAX_V ? (V + p.chunk - 1) / p.chunk : 0;
+    return p;
+}
+
 }  // namespace ace355

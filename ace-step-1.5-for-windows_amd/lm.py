@@ -10,8 +10,9 @@ and reads ``outputs.logits[:, -1, :]`` and ``outputs.past_key_values`` only.  Th
 handle's KV cache, and a native one-row decode step, each returning the last column's logits.  No ``position_ids`` are passed, so
 positions are the padded column indices and the first visible key of a row is its count of leading zeros.
 
-Only the forward is native.  The CFG combine, repetition penalty, top-k / top-p, the constrained logits processor and sampling stay the
-reference's torch code, run on the logits returned here.  It is not an ``nn.Module``: ``modswap.NativeCausalLMSwap`` wraps it and keeps
+Only the forward is native here.  The CFG combine, repetition penalty and the constrained logits processor stay the reference's torch
+code, run on the logits returned here; top-k / top-p and the draw have a native counterpart in ``ace355.lmsample`` (opt-in at the seam:
+``NativeLmMixin.use_native_lm_sampler``).  It is not an ``nn.Module``: ``modswap.NativeCausalLMSwap`` wraps it and keeps
 the reference module as the fallback.
 """
 from __future__ import annotations

@@ -71,6 +71,11 @@ class LmConfigC(C.Structure):
 
 
 LM_MAX_SEQS, LM_MAX_POSITIONS, LM_MAX_TOKENS = 16, 16384, 65536   # ACE355_LM_MAX_*
+LM_PICK_MAX_V = 1 << 20   # ace355_lm_pick's largest row
+
+
+class LmPickParamsC(C.Structure):
+    _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float), ("temperature", C.c_float), ("reserved", C.c_int32)]
 
 
 class VaeConfigC(C.Structure):
@@ -331,6 +336,10 @@ SIGNATURES = {
     "ace355_lm_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "ace355_lm_length": (C.c_int, [C.c_void_p]),
     "ace355_lm_decode_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ace355_lm_pick_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ace355_lm_pick_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ace355_lm_pick": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(LmPickParamsC), C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ace355_peak_normalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "ace355_latent_check": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_void_p]),
     "ace355_normalize_audio": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
@@ -447,6 +456,14 @@ def lm_decode_plan(length: int) -> dict:
     chunk, splits = C.c_int32(), C.c_int32()
     check(lib().ace355_lm_decode_plan(int(length), C.byref(chunk), C.byref(splits)), "lm_decode_plan")
     return {"chunk": chunk.value, "splits": splits.value}
+
+
+def lm_pick_plan(V: int) -> dict:
+    """`ace355_lm_pick_plan` (include/ace355.h): how the token selection cuts a row of ``V`` logits - ids per workgroup (``chunk``) and
+    chunks per row (``chunks``).  A function of V alone; no GPU."""
+    chunk, chunks = C.c_int32(), C.c_int32()
+    check(lib().ace355_lm_pick_plan(int(V), C.byref(chunk), C.byref(chunks)), "lm_pick_plan")
+    return {"chunk": chunk.value, "chunks": chunks.value}
 
 
 def conv_plan(B: int, M: int, N: int, Cin: int, taps: int, **bits) -> dict:

@@ -843,6 +843,36 @@ int ace355_lm_length(ace355_lm* h);
 int ace355_lm_decode_plan(int length, int32_t* chunk_out, int32_t* splits_out);
 
 /* ------------------------------------------------------------------------------------------
+ * 5 Hz LM token selection: top-k, top-p and the draw on logits that already exist, i.e. what
+ * LLMHandler._apply_top_k_filter, _apply_top_p_filter and _sample_tokens (llm_inference.py:367-399) do in that order.  No handle,
+ * no state; the logits are only read.
+ *
+ * A row is V fp32 logits, each finite or -inf (-0.0 == +0.0).  A row with a NaN, a +inf or no finite entry yields token -1, kept
+ * count 0 and an all-zero mask.
+ *   top-k (0 < top_k < V): t = the k-th largest value counted with multiplicity; x survives iff x >= t (t == -inf removes nothing).
+ *   top-p (0 < top_p < 1), over the survivors: m_i = exp(x_i - max), Z = sum; walk in descending value, equal values in ascending id;
+ *     position 0 is kept, position j >= 1 iff the mass of positions 0 .. j-1 is <= top_p * Z.
+ *   kept = finite and survives both.
+ *   temperature <= 0: the largest kept logit, lowest id on a tie.  temperature T > 0: w_i = exp((x_i - max) / T) over the kept
+ *     entries, total W; in ascending id with running sum S the token is the first kept id with S > u * W, else the last kept id with
+ *     a non-zero weight: inverse-CDF sampling of softmax(filtered / T) with the caller's u in [0, 1).
+ * Exponentials and sums are fp64, summed in an order that depends on V alone; a row's results do not depend on B, on the other rows
+ * or on the run.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ace355_lm_pick_params { int32_t top_k; float top_p; float temperature; int32_t reserved; } ace355_lm_pick_params;
+/* Bytes of workspace ace355_lm_pick needs for B rows of V logits.  Pure; 0 for B outside 1 .. ACE355_LM_MAX_SEQS or V outside
+ * 1 .. 1 << 20. */
+size_t ace355_lm_pick_workspace_bytes(int B, int V);
+/* The cut of a row over workgroups (csrc/lm_plan.h): ids per chunk and chunks per row.  A pure function of V alone - no GPU. */
+int ace355_lm_pick_plan(int V, int32_t* chunk_out, int32_t* chunks_out);
+/* logits dev f32, row b at logits + b * row_stride; u dev f32 [B] (may be NULL when temperature <= 0); tokens dev int64 [B];
+ * kept dev int32 [B] or NULL; keep dev uint8 [B, V] or NULL; workspace dev, 8-byte aligned.  ACE355_ERR_INVALID before any HIP call
+ * for B outside 1 .. ACE355_LM_MAX_SEQS, V outside 1 .. 1 << 20, row_stride < V, a null required pointer, u == NULL with
+ * temperature > 0, or a workspace smaller than ace355_lm_pick_workspace_bytes(B, V). */
+int ace355_lm_pick(const float* logits_dev, int64_t row_stride, int B, int V, const ace355_lm_pick_params* p, const float* u_dev,
+                   int64_t* tokens_dev, int32_t* kept_dev, uint8_t* keep_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Audio-token detokenizer of the LM-hint path: AudioTokenDetokenizer.forward,
  * base.py:886-994, as called by _decode_audio_codes_to_latents (handler/audio_codes.py:49-66) and by
  * prepare_condition (base.py:1646-1647).  Input = the quantizer's output for the 5 Hz audio codes, output =
