@@ -10,6 +10,7 @@ Layout:
   textenc.py   NativeTextEncoder: the caption text encoder (Qwen3Model, causal) and its embed_tokens gather
   lm.py        NativeCausalLM: the 5 Hz LM's forward (Qwen3ForCausalLM): prefill, KV-cached decode steps, last-position logits
   lmsample.py  select_tokens / filter_logits_: top-k, top-p and the draw on the LM's logits in one native call
+  lmlogits.py  shape_logits / SeenTokens / step_plan / generate_with_cfg: the LM's logits stage and its device-resident CFG loop
   audio_out.py normalize_audio, AudioSaver: GPU normalise / PCM conversion + threaded FLAC / WAV writers
   backend.py   NativeDitMixin / NativeVaeMixin / NativeHandler: the reference's handler seam
   dist.py      one-process-per-GPU data-parallel runner (RCCL broadcast of conditioning)

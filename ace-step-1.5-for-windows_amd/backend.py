@@ -36,6 +36,7 @@ logger = logging.getLogger("ace355")
 MAX_BATCH_SIZE = 8  # handler/service_generate_request.py:12
 _ALIGN_POST_ENV = os.environ.get("ACE355_ALIGN_POST", "") == "1"   # read once: the default of NativeDitMixin.native_lyric_post
 _LM_SAMPLER_ENV = os.environ.get("ACE355_LM_SAMPLER", "") == "1"   # read once: the default of NativeLmMixin.use_native_lm_sampler
+_LM_LOOP_ENV = os.environ.get("ACE355_LM_LOOP", "") == "1"         # read once: the default of NativeLmMixin.use_native_lm_loop
 
 
 class NativeDitMixin:
@@ -548,6 +549,65 @@ class NativeLmMixin:
             logits = super()._apply_top_k_filter(logits, top_k)   # the deferred filters first
             logits = super()._apply_top_p_filter(logits, top_p)
             return super()._sample_tokens(logits, temperature)
+
+    # ------------------------------------------------------------------ the CFG loop (opt-in)
+    # With ``use_native_lm_loop`` (ACE355_LM_LOOP=1 for every host) ``_generate_with_cfg_custom`` is ace355.lmlogits.generate_with_cfg:
+    # the logits stage between forward and selection is one native launch, and a codes-phase token goes forward -> stage -> selection
+    # -> next forward without the host reading it.  The flag implies the native selection whatever ``use_native_lm_sampler`` says: the
+    # distribution is the reference's, the draw for a given seed is ace355.lmsample's (one torch.rand(B) per step), not
+    # torch.multinomial's.  The call goes to the reference's loop, untouched, when the flag is off, ``self.llm`` is not the native
+    # swap, the ids are not on a CUDA device, the attention mask is not left-padded, or the request exceeds the native handle
+    # (2B > max_seqs, P + max_new_tokens > max_positions, 2B * P > 65536, vocabulary > 1 << 20).  With the flag on, each such reason
+    # is logged once per handler (``[native-lm-loop] ...``), so a loop that never runs natively does not go unnoticed.
+    use_native_lm_loop: bool = _LM_LOOP_ENV
+    _lm_loop_stats = None   # of the last native call: {"steps", "native_steps", "sync_free_steps", "token_reads"}
+
+    _lm_loop_reasons_logged = frozenset()
+
+    def _lm_loop_native(self, batch_input_ids, batch_attention_mask, max_new_tokens):
+        """``(the NativeCausalLM the loop would run on, None)``, or ``(None, why)`` when the call belongs to the reference's loop
+        (``why`` is None with the flag off: nothing was asked for)."""
+        if not self.use_native_lm_loop:
+            return None, None
+        if not isinstance(batch_input_ids, torch.Tensor) or not batch_input_ids.is_cuda or batch_input_ids.dim() != 2:
+            return None, "the input ids are not a [2B, P] tensor on a CUDA device"
+        from . import lm as _lm, modswap, native
+        llm = getattr(self, "llm", None)
+        if isinstance(llm, modswap.NativeCausalLMSwap):
+            llm = object.__getattribute__(llm, "_native")
+        if not isinstance(llm, _lm.NativeCausalLM):
+            return None, "self.llm is not the native LM (see _init_native_lm)"
+        if batch_input_ids.device != llm.device:
+            return None, f"the input ids are on {batch_input_ids.device}, the native LM on {llm.device}"
+        N, P = batch_input_ids.shape
+        if N < 2 or N % 2 or P < 1:
+            return None, f"{N} x {P} input ids are not conditional + unconditional rows"
+        if N > llm.max_seqs or P + int(max_new_tokens) > llm.max_positions or N * P > native.LM_MAX_TOKENS:
+            return None, (f"{N} sequences of {P} + {int(max_new_tokens)} positions exceed the native handle ({llm.max_seqs} sequences, "
+                          f"{llm.max_positions} positions, {native.LM_MAX_TOKENS} prefill tokens)")
+        if llm.cfg.vocab_size > native.LM_PICK_MAX_V:
+            return None, f"a vocabulary of {llm.cfg.vocab_size} exceeds {native.LM_PICK_MAX_V}"
+        if batch_attention_mask is not None:
+            if tuple(batch_attention_mask.shape) != (N, P):
+                return None, "the attention mask does not have the ids' shape"
+            try:
+                _lm.left_pad_first(batch_attention_mask)
+            except NotImplementedError as exc:
+                return None, str(exc)
+        return llm, None
+
+    def _generate_with_cfg_custom(self, batch_input_ids, batch_attention_mask, max_new_tokens, temperature, cfg_scale, top_k, top_p,
+                                  repetition_penalty, pad_token_id, streamer, constrained_processor=None):
+        llm, why = self._lm_loop_native(batch_input_ids, batch_attention_mask, max_new_tokens)
+        if llm is None:
+            if why is not None and why not in self._lm_loop_reasons_logged:   # once per reason and handler
+                self._lm_loop_reasons_logged = self._lm_loop_reasons_logged | {why}
+                logger.info("[native-lm-loop] %s; this request runs the reference's loop", why)
+            return super()._generate_with_cfg_custom(batch_input_ids, batch_attention_mask, max_new_tokens, temperature, cfg_scale, top_k,
+                                                     top_p, repetition_penalty, pad_token_id, streamer, constrained_processor)
+        from .lmlogits import generate_with_cfg
+        return generate_with_cfg(self, llm, batch_input_ids, batch_attention_mask, max_new_tokens, temperature, cfg_scale, top_k, top_p,
+                                 repetition_penalty, pad_token_id, streamer, constrained_processor)
 
 
 class _ModelShell:

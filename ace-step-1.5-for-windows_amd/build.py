@@ -11,12 +11,14 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libace355.so")
-SOURCES = ["gemm.hip", "attn.hip", "elementwise.hip", "conv.hip", "dit.hip", "vae.hip", "cond.hip", "audio_out.hip", "api.hip", "lora.hip", "lokr.hip", "dora.hip", "xattn_probs.hip", "textenc.hip", "encoder.hip", "align_post.hip", "lm.hip", "lm_sample.hip"]
+SOURCES = ["gemm.hip", "attn.hip", "elementwise.hip", "conv.hip", "dit.hip", "vae.hip", "cond.hip", "audio_out.hip", "api.hip", "lora.hip", "lokr.hip", "dora.hip", "xattn_probs.hip", "textenc.hip", "encoder.hip", "align_post.hip", "lm.hip", "lm_sample.hip", "lm_shape.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 # gemm.hip: MFMA results stay in architectural VGPRs.  Left to itself the register allocator moves the 16x16x32 accumulators of the
 # one-wave-per-SIMD kernels (3-4 LDS stages: 512 registers available) to AGPRs and then ROTATES them through v_accvgpr_read/write every
 # K step (104 moves and 31 s_nops in a 32-MFMA loop: 1435 instead of 857 cycles per K step, profiles/r04/r04_m16_gemm_clk_inpass.txt).
-FILE_FLAGS = {"gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+FILE_FLAGS = {"gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+              # lm_shape.hip restates a chain of separate torch kernels bit for bit: u + s * (c - u) must not become an fma
+              "lm_shape.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -4,8 +4,9 @@
 // store; a decode step is the same layer code at M = N rows, S = 1, with the attention below reading the cache.
 //
 // This file holds the cache store, the decode attention with its merge, the LM head, and the handle.  The cut of a cache into chunks is
-// lm_plan.h's, a function of the length alone.  No atomics anywhere: every result has one summation order, so the same calls give the
-// same bits, and a sequence's bits do not depend on the other sequences of the batch.
+// lm_plan.h's, a function of the length alone.  No atomics in the forward: every result has one summation order, so the same calls give
+// the same bits, and a sequence's bits do not depend on the other sequences of the batch.  (The one atomic of the file is an integer count
+// of replaced ids in lm_tokens_kernel.)
 #include <math.h>
 
 #include <string>
@@ -251,6 +252,8 @@ struct ace355_lm : EncBase {
     int* first_dev = nullptr;  // [max_seqs]
     KvCache cache;             // allocated at the first prefill, kept for the handle's life
     int n_seqs = 0, length = 0;
+    unsigned long long* bad_dev = nullptr;   // out-of-range tokens ace355_lm_decode_tokens replaced; allocated with the cache
+    hipStream_t tokens_stream = nullptr;     // the stream of the last ace355_lm_decode_tokens
 };
 
 namespace {
@@ -299,7 +302,7 @@ int lm_upload_ids(ace355_lm* h, const int32_t* ids, long n, hipStream_t s) {
     return 0;
 }
 
-int lm_ensure_cache(ace355_lm* h) {
+int lm_ensure_cache(ace355_lm* h, hipStream_t s) {
     if (h->cache.kv) return 0;
     KvCache& c = h->cache;
     c.max_seqs = h->cfg.max_seqs;
@@ -309,7 +312,21 @@ int lm_ensure_cache(ace355_lm* h) {
     ALLOC(h->allocs, c.part_ml, (size_t)c.max_seqs * h->HQ * LM_MAX_SPLITS * 2);
     ALLOC(h->allocs, h->first_dev, (size_t)c.max_seqs);
     c.first_dev = h->first_dev;
+    ALLOC(h->allocs, h->bad_dev, 1);
+    // on the prefill's stream, which the prefill synchronises before it returns: cleared before any stream can count or read
+    ACE_HIP(hipMemsetAsync(h->bad_dev, 0, sizeof(unsigned long long), s));
     return 0;
+}
+
+// ids[n] = tokens[n % B] for the N <= 16 sequences of a decode step (one wave); a token outside [0, vocab) becomes id 0 and is counted
+__global__ __launch_bounds__(64) void lm_tokens_kernel(const int64_t* __restrict__ tokens, int B, int N, int vocab, int* __restrict__ ids,
+                                                       unsigned long long* __restrict__ bad) {
+    const int n = threadIdx.x;
+    if (n >= N) return;
+    const int64_t t = tokens[n % B];
+    const bool ok = t >= 0 && t < vocab;
+    ids[n] = ok ? (int)t : 0;
+    if (!ok) atomicAdd(bad, 1ull);
 }
 
 // the stack over N x S rows at position pos0 (h->h embedded from ids_dev), and the head on every sequence's last row
@@ -398,7 +415,7 @@ int ace355_lm_prefill(ace355_lm* h, const int32_t* ids_host, const int32_t* firs
     hipStream_t s = (hipStream_t)stream;
     h->length = 0;
     h->n_seqs = 0;
-    rc = lm_ensure_cache(h);
+    rc = lm_ensure_cache(h, s);
     if (!rc) rc = lm_upload_ids(h, ids_host, (long)N * P, s);
     if (rc) return rc;
     ACE_HIP(hipMemcpyAsync(h->first_dev, first_host, sizeof(int) * N, hipMemcpyHostToDevice, s));
@@ -423,6 +440,37 @@ int ace355_lm_decode(ace355_lm* h, const int32_t* ids_host, float* logits_dev, v
     if (rc) { h->length = 0; h->n_seqs = 0; return rc; }   // a failed launch: the cache is not trustworthy
     h->length += 1;
     return ACE355_OK;
+}
+
+int ace355_lm_decode_tokens(ace355_lm* h, const int64_t* tokens_dev, int B, float* logits_dev, void* stream) {
+    ACE_CHECK(h && tokens_dev && logits_dev, "lm_decode_tokens: null argument");
+    if (h->length <= 0 || h->n_seqs <= 0) return lm_refuse("lm_decode_tokens: no prefill to continue from");
+    if (h->length >= h->cfg.max_positions)
+        return lm_refuse("lm_decode_tokens: the cache is full (length " + std::to_string(h->length) + " = max_positions)");
+    if (B < 1 || h->n_seqs % B != 0)
+        return lm_refuse("lm_decode_tokens: B = " + std::to_string(B) + " tokens for " + std::to_string(h->n_seqs) +
+                         " sequences (n_seqs must be a multiple of B)");
+    ACE_CHECK(h->ids_dev && h->ids_cap >= h->n_seqs && h->bad_dev, "lm_decode_tokens: the handle's id buffer");
+    static_assert(LM_MAX_SEQS <= 64, "lm_tokens_kernel is one wave");
+    hipStream_t s = (hipStream_t)stream;
+    h->tokens_stream = s;
+    hipLaunchKernelGGL(lm_tokens_kernel, dim3(1), dim3(64), 0, s, tokens_dev, B, h->n_seqs, h->cfg.vocab_size, h->ids_dev, h->bad_dev);
+    ACE_LAUNCH_CHECK();   // (nothing of the cache has been touched yet: the handle stays as it was)
+    int rc = lm_run(h, h->n_seqs, 1, h->length, logits_dev, s);
+    if (rc) { h->length = 0; h->n_seqs = 0; return rc; }   // a failed launch: the cache is not trustworthy
+    h->length += 1;
+    return ACE355_OK;
+}
+
+int64_t ace355_lm_bad_tokens(ace355_lm* h) {
+    if (!h) return -1;
+    if (!h->bad_dev) return 0;
+    unsigned long long n = 0;
+    hipStream_t s = h->tokens_stream;
+    if (hipMemcpyAsync(&n, h->bad_dev, sizeof(n), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
+    if (hipMemsetAsync(h->bad_dev, 0, sizeof(n), s) != hipSuccess) return -1;
+    if (hipStreamSynchronize(s) != hipSuccess) return -1;
+    return (int64_t)n;
 }
 
 int ace355_lm_length(ace355_lm* h) { return h ? h->length : -1; }

@@ -10,9 +10,10 @@ and reads ``outputs.logits[:, -1, :]`` and ``outputs.past_key_values`` only.  Th
 handle's KV cache, and a native one-row decode step, each returning the last column's logits.  No ``position_ids`` are passed, so
 positions are the padded column indices and the first visible key of a row is its count of leading zeros.
 
-Only the forward is native here.  The CFG combine, repetition penalty and the constrained logits processor stay the reference's torch
-code, run on the logits returned here; top-k / top-p and the draw have a native counterpart in ``ace355.lmsample`` (opt-in at the seam:
-``NativeLmMixin.use_native_lm_sampler``).  It is not an ``nn.Module``: ``modswap.NativeCausalLMSwap`` wraps it and keeps
+Only the forward is native here.  By default the CFG combine, repetition penalty and the constrained logits processor stay the
+reference's torch code, run on the logits returned here; top-k / top-p and the draw have a native counterpart in ``ace355.lmsample``
+(opt-in at the seam: ``NativeLmMixin.use_native_lm_sampler``), and the rest of the loop body in ``ace355.lmlogits`` (opt-in:
+``NativeLmMixin.use_native_lm_loop``), which drives ``decode_tokens`` below.  It is not an ``nn.Module``: ``modswap.NativeCausalLMSwap`` wraps it and keeps
 the reference module as the fallback.
 """
 from __future__ import annotations
@@ -74,6 +75,10 @@ class NativeCausalLM(native.Owner):
                  max_seqs: int = native.LM_MAX_SEQS, out_dtype: torch.dtype = torch.float32):
         self.cfg = cfg
         self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            # "cuda" (what LLMHandler.initialize stores) means the current device; tensors report theirs with an index, and
+            # torch.device("cuda") != torch.device("cuda:0"), so the handle names the device it is really on
+            self.device = torch.device("cuda", torch.cuda.current_device())
         self.out_dtype = out_dtype
         self.max_positions, self.max_seqs = int(max_positions), int(max_seqs)
         self._generation = 0
@@ -149,6 +154,37 @@ class NativeCausalLM(native.Owner):
         self._generation += 1
         self._decode(host, out)
         return out
+
+    def decode_tokens(self, tokens: torch.Tensor) -> torch.Tensor:
+        """``decode`` for ids that stay on the GPU: ``tokens`` int64 ``[B]`` on this device, ``N % B == 0``, sequence ``n`` takes
+        ``tokens[n % B]`` (the CFG loop's ``next_tokens.repeat(2, 1)``).  Nothing is read back and the stream is not synchronised; an id
+        outside the vocabulary is embedded as id 0 and counted (``bad_tokens``)."""
+        if self._first is None:
+            raise ValueError("ace355: LM decode without a prefill")
+        N = len(self._first)
+        if not isinstance(tokens, torch.Tensor) or tokens.dtype != torch.int64 or tokens.device != self.device or tokens.dim() != 1:
+            raise ValueError(f"ace355: decode_tokens takes an int64 [B] tensor on {self.device}")
+        B = tokens.shape[0]
+        if B < 1 or N % B != 0:
+            raise ValueError(f"ace355: {B} tokens for {N} sequences (N must be a multiple of B)")
+        if self.length >= self.max_positions:
+            raise ValueError(f"ace355: the LM cache is full ({self.max_positions} positions)")
+        if not tokens.is_contiguous():
+            tokens = tokens.contiguous()
+        out = torch.empty(N, self.cfg.vocab_size, device=self.device, dtype=torch.float32)
+        self._generation += 1
+        with torch.cuda.device(self.device):
+            native.check(self._lib.ace355_lm_decode_tokens(self._h, tokens.data_ptr(), B, native.ptr(out), native.current_stream_ptr()),
+                         "lm_decode_tokens")
+        return out
+
+    def bad_tokens(self) -> int:
+        """Out-of-vocabulary ids ``decode_tokens`` has replaced since the last call of this method (one synchronisation; clears)."""
+        with torch.cuda.device(self.device):
+            n = int(self._lib.ace355_lm_bad_tokens(self._h))
+        if n < 0:
+            raise RuntimeError(f"ace355 native call failed (lm_bad_tokens): {native.last_error()}")
+        return n
 
     # ------------------------------------------------------------------ Qwen3ForCausalLM.forward for what _forward_pass passes
     def __call__(self, input_ids=None, attention_mask=None, past_key_values=None, use_cache=True, *args, output_hidden_states=None,

@@ -78,6 +78,14 @@ class LmPickParamsC(C.Structure):
     _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float), ("temperature", C.c_float), ("reserved", C.c_int32)]
 
 
+class LmShapeParamsC(C.Structure):
+    _fields_ = [("cfg_scale", C.c_float), ("eos_id", C.c_int32), ("eos_mode", C.c_int32), ("has_temperature", C.c_int32),
+                ("temperature", C.c_float), ("penalty", C.c_float), ("mask", C.c_void_p), ("seen", C.c_void_p)]
+
+
+LM_EOS_NONE, LM_EOS_BLOCK, LM_EOS_FORCE = 0, 1, 2   # ace355_lm_shape_params.eos_mode
+
+
 class VaeConfigC(C.Structure):
     _fields_ = [
         ("decoder_channels", C.c_int32), ("decoder_input_channels", C.c_int32), ("audio_channels", C.c_int32),
@@ -340,6 +348,11 @@ SIGNATURES = {
     "ace355_lm_pick_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ace355_lm_pick": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(LmPickParamsC), C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ace355_lm_shape": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                  C.POINTER(LmShapeParamsC), C.c_void_p]),
+    "ace355_lm_seen_mark": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ace355_lm_decode_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ace355_lm_bad_tokens": (C.c_int64, [C.c_void_p]),
     "ace355_peak_normalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "ace355_latent_check": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_void_p]),
     "ace355_normalize_audio": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),

@@ -873,6 +873,53 @@ int ace355_lm_pick(const float* logits_dev, int64_t row_stride, int B, int V, co
                    int64_t* tokens_dev, int32_t* kept_dev, uint8_t* keep_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 5 Hz LM logits stage: what the reference's CFG loop does to the logits between its forward and its
+ * token selection (llm_inference.py:2482-2493): the CFG combine, the CODES_GENERATION / COMPLETED / disabled branches of
+ * MetadataConstrainedLogitsProcessor.__call__ with _apply_temperature_scaling, then transformers' RepetitionPenaltyLogitsProcessor.
+ * No handle, no state, one launch.
+ *
+ * For every row b and id v, in this order, every operation rounded to fp32 on its own (never contracted into an fma):
+ *   1. x = u + cfg_scale * (c - u) with c = cond[b][v], u = uncond[b][v]; x = c when uncond is NULL.
+ *   2. x = x + mask[v] when mask is given (a real add: -0.0 + 0.0 is +0.0, NaN propagates).
+ *   3. eos_mode 1 (block): x = -inf at v == eos_id.  eos_mode 2 (force): x = -inf at every v != eos_id; eos_id keeps step 2's value.
+ *   4. x = x / temperature when has_temperature (IEEE division, correctly rounded).  The caller maps the reference's T <= 0 to 1e-6.
+ *   5. when penalty != 1 and bit v & 31 of seen[b][v >> 5] is set: x = x < 0 ? x * penalty : x / penalty.
+ *   out[b][v] = x.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ace355_lm_shape_params {
+    float cfg_scale;         /* read only when uncond is given */
+    int32_t eos_id;          /* read only when eos_mode != 0 */
+    int32_t eos_mode;        /* 0 none, 1 block, 2 force */
+    int32_t has_temperature; /* 0: step 4 is skipped */
+    float temperature;       /* > 0 when has_temperature */
+    float penalty;           /* finite, > 0; 1 = off */
+    const float* mask;       /* dev f32 [V], or NULL */
+    const uint32_t* seen;    /* dev u32 [B, (V + 31) / 32], rows dense; NULL iff penalty == 1 */
+} ace355_lm_shape_params;
+/* cond, uncond (or NULL), out: dev f32, row b at base + b * stride, each stride >= V, rows only 4-byte aligned; out may be cond
+ * (an element is read before it is written, by the same thread) and must not overlap anything else.  ACE355_ERR_INVALID before any
+ * HIP call for B outside 1 .. ACE355_LM_MAX_SEQS, V outside 1 .. 1 << 20, a stride < V, a null cond / out / params, eos_mode outside
+ * 0 .. 2, eos_mode != 0 with eos_id outside [0, V), a penalty that is not finite or <= 0, seen == NULL with penalty != 1, a NaN
+ * cfg_scale with uncond given, has_temperature with temperature <= 0 or NaN. */
+int ace355_lm_shape(const float* cond_dev, int64_t cond_stride, const float* uncond_dev, int64_t uncond_stride, float* out_dev,
+                    int64_t out_stride, int B, int V, const ace355_lm_shape_params* p, void* stream);
+/* ids dev int64, row b at ids + b * row_stride, T ids per row: sets bit v & 31 of seen[b][v >> 5] for every id v in [0, V) with an
+ * integer atomic OR (commutative: the result does not depend on order); ids outside [0, V) are ignored.  Bits are only ever set:
+ * the caller zeroes the bitmap (dev u32 [B, (V + 31) / 32]).  ACE355_ERR_INVALID before any HIP call for B outside
+ * 1 .. ACE355_LM_MAX_SEQS, V outside 1 .. 1 << 20, T outside 1 .. ACE355_LM_MAX_POSITIONS, row_stride < T, a null pointer. */
+int ace355_lm_seen_mark(const int64_t* ids_dev, int64_t row_stride, int B, int T, int V, uint32_t* seen_dev, void* stream);
+/* ace355_lm_decode with ids that never visit the host: tokens dev int64 [B], n_seqs % B == 0, sequence n takes tokens[n % B] (the
+ * reference's next_tokens.repeat(2, 1)).  One small kernel writes the handle's id buffer, the rest is ace355_lm_decode's; the call
+ * makes no stream synchronisation.  A token outside [0, vocab) cannot be refused on the host: id 0 is embedded in its place and a
+ * device counter is bumped (ace355_lm_bad_tokens).  Refused like ace355_lm_decode without a prefill and at length ==
+ * max_positions, and for B < 1 or n_seqs % B != 0, before anything is launched and with the handle unchanged. */
+int ace355_lm_decode_tokens(ace355_lm* h, const int64_t* tokens_dev, int B, float* logits_dev, void* stream);
+/* How many out-of-range tokens ace355_lm_decode_tokens has replaced since the last call of this function.  Read and cleared on the
+ * stream of the last ace355_lm_decode_tokens call, with one synchronisation of that stream.  0 when that call was never made;
+ * < 0 for a null handle or a HIP error. */
+int64_t ace355_lm_bad_tokens(ace355_lm* h);
+
+/* ------------------------------------------------------------------------------------------
  * Audio-token detokenizer of the LM-hint path: AudioTokenDetokenizer.forward,
  * base.py:886-994, as called by _decode_audio_codes_to_latents (handler/audio_codes.py:49-66) and by
  * prepare_condition (base.py:1646-1647).  Input = the quantizer's output for the 5 Hz audio codes, output =
