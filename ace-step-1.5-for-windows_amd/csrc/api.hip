@@ -10,6 +10,7 @@
 #include "adapter_plan.h"
 #include "attn_plan.h"
 #include "dit_plan.h"
+#include "encoder_plan.h"
 #include "vae_plan.h"
 #include "gemm_plan.h"
 #include <dlfcn.h>
@@ -182,6 +183,21 @@ int ace355_dit_pass_plan(const ace355_dit_config* cfg, const ace355_dit_pass_req
     rq.cfg = *cfg;
     if (rq.mx_copies < 0) rq.mx_copies = dit_mx_copies(*cfg);
     const DitPassPlan p = dit_pass_plan_query(rq);
+    ACE_CHECK(!p.error, p.error);
+    for (int i = 0; i < std::min(capacity, p.info.n_steps); ++i) steps_out[i] = p.steps[i];
+    *n_out = p.info.n_steps;
+    *info_out = p.info;
+    return ACE355_OK;
+}
+
+int ace355_encoder_pass_plan(const ace355_encoder_pass_request* r, ace355_encoder_step_info* steps_out, int capacity, int32_t* n_out,
+                             ace355_encoder_pass_info* info_out) {
+    ACE_CHECK(r && n_out && info_out && capacity >= 0 && (steps_out || capacity == 0), "encoder_pass_plan: null pointer");
+    ACE_CHECK(r->hidden_size > 0 && r->hidden_size <= (1 << 16) && r->intermediate_size > 0 && r->intermediate_size <= (1 << 18) && r->num_heads > 0 &&
+              r->num_heads <= 1024 && r->num_kv_heads > 0 && r->num_kv_heads <= r->num_heads && r->num_layers >= 0 && r->num_layers <= 256,
+              "encoder_pass_plan: configuration");
+    ACE_CHECK(r->N > 0 && r->S > 0 && (long)r->N * r->S < (1L << 31), "encoder_pass_plan: N > 0, S > 0, N * S below 2^31");
+    const EncPassPlan p = plan_encoder_pass(*r);
     ACE_CHECK(!p.error, p.error);
     for (int i = 0; i < std::min(capacity, p.info.n_steps); ++i) steps_out[i] = p.steps[i];
     *n_out = p.info.n_steps;

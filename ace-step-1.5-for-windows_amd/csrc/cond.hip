@@ -84,11 +84,11 @@ bool resolve(ace355_cond* h, const std::string& name, PackDest* d) {
 }
 
 // embed (Linear with bias, base.py:623 / :1070) then the layers.  in_bf: [N*S, in_dim] bf16.
-int encoder_stack(EncBase* h, const EncoderW& E, const bf16_t* in_bf, int N, int S, const int* kv_len_dev, bf16_t* out, hipStream_t s) {
+int encoder_stack(EncBase* h, const EncoderW& E, const bf16_t* in_bf, const EncPassRequest& rq, const int* kv_len_dev, bf16_t* out, hipStream_t s) {
     GemmEpilogue ep{1, E.b_embed, nullptr, nullptr, 0, 0};
-    int rc = launch_gemm(in_bf, E.in_dim, E.w_embed, E.in_dim, h->h, h->D, N * S, h->D, E.in_dim, ep, s);
+    int rc = launch_gemm(in_bf, E.in_dim, E.w_embed, E.in_dim, h->h, h->D, rq.N * rq.S, h->D, E.in_dim, ep, s);
     if (rc) return rc;
-    return encoder_layers(h, E, N, S, kv_len_dev, out, s);
+    return run_encoder_pass(h, E, rq, kv_len_dev, out, s);
 }
 
 // the three branch outputs, grown like the workspace
@@ -182,10 +182,10 @@ int ace355_cond_encode(ace355_cond* h, const float* text_dev, const int32_t* tex
         max_cnt = std::max(max_cnt, ++cnt[refer_item[i]]);
     }
     const int Lout = Ll + max_cnt + Lt;
-    const long rows = std::max<long>({(long)B * Ll, (long)Nref * Tref, (long)B * Lt});
+    const EncPassRequest passes[2] = {enc_request(*h, h->lyric, B, Ll, true), enc_request(*h, h->timbre, Nref, Tref)};
+    const long rows = std::max<long>({(long)B * Ll, (long)Nref * Tref, (long)B * Lt});   // of the three branch outputs
     const long in_elems = std::max<long>({(long)B * Ll * TD, (long)Nref * Tref * AD, (long)B * Lt * TD});
-    const long vt_elems = std::max<long>((long)B * (((Ll + 63) / 64) * 64), (long)Nref * (((Tref + 63) / 64) * 64)) * h->KVD;
-    int rc = ensure_workspace(h, rows, in_elems, 0, std::max(B, Nref), vt_elems, s);
+    int rc = ensure_workspace(h, plan_encoder_workspace(passes, 2, in_elems, 0), s);
     if (!rc) rc = ensure_outputs(h, rows, s);
     if (rc) return rc;
 
@@ -201,13 +201,13 @@ int ace355_cond_encode(ace355_cond* h, const float* text_dev, const int32_t* tex
     if (rc) return rc;
     ACE_HIP(hipMemcpyAsync(h->kvlen_dev, lyric_len, sizeof(int) * B, hipMemcpyHostToDevice, s));
     ACE_HIP(hipStreamSynchronize(s));  // lyric_len is caller memory
-    rc = encoder_stack(h, h->lyric, h->in_bf, B, Ll, h->kvlen_dev, h->lyric_out, s);
+    rc = encoder_stack(h, h->lyric, h->in_bf, passes[0], h->kvlen_dev, h->lyric_out, s);
     if (rc) return rc;
 
     // timbre encoder: no padding mask, token 0 of every reference clip (base.py:1549, :1175)
     rc = launch_f32_to_bf16(refer_dev, h->in_bf, (long)Nref * Tref * AD, s);
     if (rc) return rc;
-    rc = encoder_stack(h, h->timbre, h->in_bf, Nref, Tref, nullptr, h->timbre_out, s);
+    rc = encoder_stack(h, h->timbre, h->in_bf, passes[1], nullptr, h->timbre_out, s);
     if (rc) return rc;
 
     // pack_sequences twice (base.py:1553-1554) with prefix masks = a segmented row gather per batch item:
@@ -314,8 +314,8 @@ int ace355_detok_run(ace355_detok* h, const float* x_dev, int B, int T5, float* 
     hipStream_t s = (hipStream_t)stream;
     const int D = h->D, P = h->cfg.pool_window_size, OD = h->cfg.out_dim;
     const long R5 = (long)B * T5, R = R5 * P;  // 5 Hz tokens, 25 Hz rows: R5 sequences of P tokens
-    const long vt_elems = R5 * h->KVD * (((P + 63) / 64) * 64);
-    int rc = ensure_workspace(h, R, R5 * D, R5, (int)R5, vt_elems, s);
+    const EncPassRequest rq = enc_request(*h, h->enc, (int)R5, P);
+    int rc = ensure_workspace(h, plan_encoder_workspace(&rq, 1, R5 * D, R5), s);
     if (rc) return rc;
     // embed_tokens (base.py:888), then one copy per frame of the window + its special token (:889-894)
     rc = launch_f32_to_bf16(x_dev, h->in_bf, R5 * D, s);
@@ -326,7 +326,7 @@ int ace355_detok_run(ace355_detok* h, const float* x_dev, int B, int T5, float* 
     rc = launch_expand_add(h->emb, h->special, h->h, R5, P, D, s);
     if (rc) return rc;
     // (b t) sequences of P tokens through the encoder layers + norm (:896-987), proj_out (:989), unfold (:991) is a view
-    rc = encoder_layers(h, h->enc, (int)R5, P, nullptr, h->xn, s);
+    rc = run_encoder_pass(h, h->enc, rq, nullptr, h->xn, s);
     if (rc) return rc;
     ep = GemmEpilogue{1, h->b_out, nullptr, nullptr, 0, 0};
     return launch_gemm(h->xn, D, h->w_out, D, out_dev, OD, (int)R, OD, D, ep, s);
@@ -407,9 +407,9 @@ int ace355_tok_run(ace355_tok* h, const float* x_dev, int B, int T5, float* out_
     ACE_CHECK(B > 0 && T5 > 0 && (long)B * T5 <= (1L << 20), "tok_run: sizes");
     hipStream_t s = (hipStream_t)stream;
     const int D = h->D, P = h->cfg.pool_window_size, A = h->cfg.out_dim, S = P + 1;
-    const long R5 = (long)B * T5, R = R5 * P, RS = R5 * S;  // 5 Hz tokens, 25 Hz frames, rows of the (P + 1)-token sequences
-    const long vt_elems = R5 * h->KVD * (((S + 63) / 64) * 64);
-    int rc = ensure_workspace(h, RS, R * h->in_pad, R, (int)R5, vt_elems, s);
+    const long R5 = (long)B * T5, R = R5 * P;  // 5 Hz tokens = sequences of S = P + 1 tokens, 25 Hz frames
+    const EncPassRequest rq = enc_request(*h, h->enc, (int)R5, S);
+    int rc = ensure_workspace(h, plan_encoder_workspace(&rq, 1, R * h->in_pad, R), s);
     if (rc) return rc;
     if (R > h->proj_rows) {
         ACE_HIP(hipStreamSynchronize(s));
@@ -430,7 +430,7 @@ int ace355_tok_run(ace355_tok* h, const float* x_dev, int B, int T5, float* out_
     // [special | P frames] per window (:769-771), the (b t) sequences through the layers + norm (:773-853), token 0 of each (:856-858)
     rc = launch_prepend_special(h->emb, h->special, h->h, R5, P, D, s);
     if (rc) return rc;
-    rc = encoder_layers(h, h->enc, (int)R5, S, nullptr, h->xn, s);
+    rc = run_encoder_pass(h, h->enc, rq, nullptr, h->xn, s);
     if (rc) return rc;
     return launch_take_token0(h->xn, out_dev, R5, S, D, s);
 }

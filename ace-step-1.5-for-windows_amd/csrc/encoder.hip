@@ -131,15 +131,21 @@ bool resolve_encoder_layers(const EncBase& h, EncoderW& E, const std::string& na
     return parse_layer_index(name, prefix_len, E.n_layers, &li, &rest) && resolve_encoder_layer(h, E.layers[li], rest, d);
 }
 
-static int ensure_rope(EncBase* h, int S, hipStream_t s) {
-    if (S <= h->rope_S) return 0;
-    int cap = 512;
-    while (cap < S) cap *= 2;
-    ALLOC(h->allocs, h->rope_cos, (size_t)cap * 64);
-    ALLOC(h->allocs, h->rope_sin, (size_t)cap * 64);
-    int rc = launch_rope_table(h->rope_cos, h->rope_sin, cap, h->theta, s);
+EncPassRequest enc_request(const EncBase& h, const EncoderW& E, int N, int S, bool has_kv_len, const KvCache* cache, int pos0) {
+    EncPassRequest r{};
+    r.hidden_size = h.D; r.intermediate_size = h.F; r.num_heads = h.HQ; r.num_kv_heads = h.KVH; r.num_layers = E.n_layers;
+    r.sliding_window = h.sliding_window; r.sliding_layer_mask = h.sliding_layer_mask; r.causal = h.causal;
+    r.N = N; r.S = S; r.has_kv_len = has_kv_len;
+    if (cache) { r.has_cache = 1; r.pos0 = pos0; r.max_pos = cache->max_pos; r.max_seqs = cache->max_seqs; r.has_first = cache->first_dev != nullptr; }
+    return r;
+}
+
+static int grow_rope(EncBase* h, size_t cap, hipStream_t s) {
+    ALLOC(h->allocs, h->rope_cos, cap * 64);
+    ALLOC(h->allocs, h->rope_sin, cap * 64);
+    int rc = launch_rope_table(h->rope_cos, h->rope_sin, (int)cap, h->theta, s);
     if (rc) return rc;
-    h->rope_S = cap;
+    h->ws.rope_rows = (long)cap;
     if (!h->sk_cnt) {
         ALLOC(h->allocs, h->sk_cnt, SK_CNT_INTS);
         ACE_HIP(hipMemsetAsync(h->sk_cnt, 0, SK_CNT_INTS * sizeof(int), s));
@@ -148,99 +154,95 @@ static int ensure_rope(EncBase* h, int S, hipStream_t s) {
     return 0;
 }
 
-int ensure_workspace(EncBase* h, long rows, long in_elems, long emb_rows, int seqs, long vt_elems, hipStream_t s) {
-    if (rows <= h->ws_rows && in_elems <= h->ws_in && emb_rows <= h->ws_emb && seqs <= h->ws_seqs && vt_elems <= h->ws_vt) return 0;
+int ensure_workspace(EncBase* h, const EncWorkspacePlan& want, hipStream_t s) {
+    if (want.need.within(h->ws)) return 0;
+    if (want.need.rope_rows > h->ws.rope_rows)
+        if (int rc = grow_rope(h, want.rope, s)) return rc;
+    if (want.need.within(h->ws)) return 0;   // only the tables were short
     ACE_HIP(hipStreamSynchronize(s));
     for (void* p : h->ws_allocs) hipFree(p);
     h->ws_allocs.clear();
-    const long R = std::max(rows, h->ws_rows), I = std::max(in_elems, h->ws_in), E = std::max(emb_rows, h->ws_emb),
-               V = std::max(vt_elems, h->ws_vt);
-    const int Q = std::max(seqs, h->ws_seqs);
-    const long D = h->D, QKV = h->QD + 2 * h->KVD;
-    h->ws_rows = h->ws_in = h->ws_emb = h->ws_vt = 0;
-    h->ws_seqs = 0;
-    ALLOC(h->ws_allocs, h->h, (size_t)R * D);
-    ALLOC(h->ws_allocs, h->xn, (size_t)R * D);
-    ALLOC(h->ws_allocs, h->qkv, (size_t)(R + 64) * QKV);  // +64 rows: the last K tile's DMA rows are clamped, not skipped
-    ALLOC(h->ws_allocs, h->ao, (size_t)R * h->QD);
-    ALLOC(h->ws_allocs, h->act, (size_t)R * h->F);
-    if (I) ALLOC(h->ws_allocs, h->in_bf, (size_t)I);
-    if (E) ALLOC(h->ws_allocs, h->emb, (size_t)E * D);
-    if (V) ALLOC(h->ws_allocs, h->vt, (size_t)V);
-    if (Q) {
-        ALLOC(h->ws_allocs, h->vmean, (size_t)Q * h->KVD);
-        ALLOC(h->ws_allocs, h->kvlen_dev, (size_t)Q);
+    const EncWorkspaceNeed need = want.need.max_with(h->ws);
+    h->ws = EncWorkspaceNeed{};
+    h->ws.rope_rows = need.rope_rows;
+    const EncWorkspacePlan w = enc_workspace_sizes(h->D, h->F, h->HQ, h->KVH, need);
+    ALLOC(h->ws_allocs, h->h, w.h);
+    ALLOC(h->ws_allocs, h->xn, w.xn);
+    ALLOC(h->ws_allocs, h->qkv, w.qkv);
+    ALLOC(h->ws_allocs, h->ao, w.ao);
+    ALLOC(h->ws_allocs, h->act, w.act);
+    if (w.in_bf) ALLOC(h->ws_allocs, h->in_bf, w.in_bf);
+    if (w.emb) ALLOC(h->ws_allocs, h->emb, w.emb);
+    if (w.vt) ALLOC(h->ws_allocs, h->vt, w.vt);
+    if (w.vmean) {
+        ALLOC(h->ws_allocs, h->vmean, w.vmean);
+        ALLOC(h->ws_allocs, h->kvlen_dev, w.kvlen);
     }
-    h->ws_rows = R;
-    h->ws_in = I;
-    h->ws_emb = E;
-    h->ws_seqs = Q;
-    h->ws_vt = V;
+    h->ws = need;
     return 0;
 }
 
-int encoder_layers(EncBase* h, const EncoderW& E, int N, int S, const int* kv_len_dev, bf16_t* out, hipStream_t s, const KvCache* cache) {
-    const int M = N * S, D = h->D, F = h->F, QD = h->QD, KVD = h->KVD, QKV = QD + 2 * KVD;
-    const int Sp = ((S + 63) / 64) * 64;
-    const float eps = h->eps;
-    const float scale = 1.0f / sqrtf(128.0f);
-    ACE_CHECK(!cache || (h->causal && cache->pos0 >= 0 && cache->pos0 + S <= cache->max_pos && (cache->pos0 == 0 || S == 1)),
-              "encoder_layers: KV cache position");
-    int rc = ensure_rope(h, cache ? cache->max_pos : S, s);
-    if (rc) return rc;
-    const long rope0 = cache ? (long)cache->pos0 * 64 : 0;   // row s of the call is position pos0 + s
-    GemmEpilogue ep{};
-    for (int li = 0; li < E.n_layers; ++li) {
-        const EncLayerW& W = E.layers[li];
-        // self attention (base.py:414-427)
-        rc = launch_rmsnorm_mod(h->h, W.n_in, h->xn, M, D, eps, nullptr, nullptr, nullptr, nullptr, 0, S, s);
-        if (rc) return rc;
-        ep = GemmEpilogue{4, nullptr, nullptr, nullptr, 0, S};  // q / k head-norm + RoPE in the epilogue, as in the DiT
-        ep.hn_wq = W.qn, ep.hn_wk = W.kn, ep.hn_cos = h->rope_cos + rope0, ep.hn_sin = h->rope_sin + rope0;
-        ep.hn_q_cols = QD, ep.hn_qk_cols = QD + KVD, ep.hn_eps = eps;
-        rc = launch_gemm(h->xn, D, W.wqkv, D, h->qkv, QKV, M, QKV, D, ep, s);
-        if (rc) return rc;
-        if (h->causal) {   // (a causal stack may have more layers than sliding_layer_mask has bits: the mask is not read here)
-            if (cache) {
-                rc = launch_kv_store(h->qkv, QKV, QD, QD + KVD, *cache, li, N, S, h->KVH, s);
-                if (rc) return rc;
-            }
-            if (cache && cache->pos0 > 0)
-                rc = launch_decode_attention(h->qkv, QKV, *cache, li, cache->pos0 + 1, h->ao, N, h->KVH, scale, s);
-            else
-                rc = launch_causal_attention(h->qkv, QKV, QD, QD + KVD, h->ao, QD, N, S, h->KVH, scale, s, cache ? cache->first_dev : nullptr);
-            if (rc) return rc;
-        } else {
-            const bool sliding = (h->sliding_layer_mask >> li) & 1ull;
-            rc = launch_transpose_v(h->qkv, QKV, QD + KVD, N, S, h->KVH, h->vt, Sp, s);
-            if (rc) return rc;
-            if (kv_len_dev) {
-                rc = launch_vmean(h->qkv, QKV, QD + KVD, N, S, h->KVH, h->vmean, s);
-                if (rc) return rc;
-            }
-            AttnArgs a = attn_args_rows(h->qkv, QKV, h->qkv + QD, QKV, h->vt, Sp, h->ao, N, S, S, h->HQ, h->KVH,
-                                        sliding ? h->sliding_window : -1, scale);
-            a.kv_len = kv_len_dev;
-            a.vmean = kv_len_dev ? h->vmean : nullptr;
-            rc = launch_attention(a, s);
-            if (rc) return rc;
+// One step = one launcher call; the step names the buffers, the handle and the call have the pointers.
+int run_encoder_pass(EncBase* h, const EncoderW& E, const EncPassRequest& rq, const int* kv_len_dev, bf16_t* out, hipStream_t s,
+                     const KvCache* cache) {
+    EncPassPlan& p = h->plan;
+    plan_encoder_pass(rq, p);
+    ACE_CHECK(!p.error, p.error);
+    ACE_CHECK(rq.num_layers == E.n_layers && !rq.has_kv_len == !kv_len_dev && !rq.has_cache == !cache && out, "encoder pass: the request is not this call's");
+    ACE_CHECK(enc_pass_need(rq).within(h->ws), "encoder pass: the workspace does not hold this pass");
+    const float eps = h->eps, scale = 1.0f / sqrtf(128.0f);
+    auto buf = [&](int b) -> void* {
+        switch (b) {
+        case ACE355_ENC_BUF_H: return h->h;
+        case ACE355_ENC_BUF_XN: return h->xn;
+        case ACE355_ENC_BUF_QKV: return h->qkv;
+        case ACE355_ENC_BUF_AO: return h->ao;
+        case ACE355_ENC_BUF_ACT: return h->act;
+        case ACE355_ENC_BUF_VT: return h->vt;
+        case ACE355_ENC_BUF_VMEAN: return h->vmean;
+        case ACE355_ENC_BUF_OUT: return out;
+        default: return nullptr;
         }
-        ep = GemmEpilogue{2, nullptr, nullptr, nullptr, 0, S};  // h += o_proj(attn)
-        ep.sk_cnt = h->sk_cnt;
-        rc = launch_gemm(h->ao, QD, W.wo, QD, h->h, D, M, D, QD, ep, s);
-        if (rc) return rc;
-        // SwiGLU MLP (base.py:430-433)
-        rc = launch_rmsnorm_mod(h->h, W.n_post, h->xn, M, D, eps, nullptr, nullptr, nullptr, nullptr, 0, S, s);
-        if (rc) return rc;
-        ep = GemmEpilogue{3, nullptr, nullptr, nullptr, 0, 0};
-        rc = launch_gemm(h->xn, D, W.wgu, D, h->act, F, M, 2 * F, D, ep, s);
-        if (rc) return rc;
-        ep = GemmEpilogue{2, nullptr, nullptr, nullptr, 0, S};
-        ep.sk_cnt = h->sk_cnt;
-        rc = launch_gemm(h->act, F, W.wdown, F, h->h, D, M, D, F, ep, s);
+    };
+    for (const EncStep& st : p.steps) {
+        const EncLayerW* W = st.layer >= 0 ? &E.layers[st.layer] : nullptr;
+        const bf16_t* qkv = h->qkv;
+        int rc = 0;
+        switch (st.kind) {
+        case ACE355_ENC_STEP_RMSNORM:
+            rc = launch_rmsnorm_mod(h->h, st.norm == 0 ? W->n_in : st.norm == 1 ? W->n_post : E.norm, (bf16_t*)buf(st.dst), st.M, st.N, eps, nullptr,
+                                    nullptr, nullptr, nullptr, 0, st.rows_per_seq, s);
+            break;
+        case ACE355_ENC_STEP_GEMM: {
+            const bf16_t* w[4] = {W->wqkv, W->wo, W->wgu, W->wdown};
+            GemmEpilogue ep{st.mode, nullptr, nullptr, nullptr, 0, st.rows_per_seq};
+            if (st.mode == 4) {
+                ep.hn_wq = W->qn, ep.hn_wk = W->kn, ep.hn_cos = h->rope_cos + (long)st.rope_row0 * 64, ep.hn_sin = h->rope_sin + (long)st.rope_row0 * 64;
+                ep.hn_q_cols = st.hn_q_cols, ep.hn_qk_cols = st.hn_qk_cols, ep.hn_eps = eps;
+            }
+            if (st.sk_cnt) ep.sk_cnt = h->sk_cnt;
+            rc = launch_gemm((const bf16_t*)buf(st.src), st.lda, w[st.proj], st.ldw, buf(st.dst), st.ldc, st.M, st.N, st.K, ep, s);
+            break;
+        }
+        case ACE355_ENC_STEP_KV_STORE: rc = launch_kv_store(qkv, st.ld, st.k_col0, st.v_col0, *cache, st.layer, st.seqs, st.Sq, st.Hkv, st.pos0, s); break;
+        case ACE355_ENC_STEP_DECODE_ATTN: rc = launch_decode_attention(qkv, st.ld, *cache, st.layer, st.len, h->ao, st.seqs, st.Hkv, scale, s); break;
+        case ACE355_ENC_STEP_CAUSAL_ATTN:
+            rc = launch_causal_attention(qkv, st.ld, st.k_col0, st.v_col0, h->ao, st.o_ld, st.seqs, st.Sq, st.Hkv, scale, s, st.first ? cache->first_dev : nullptr);
+            break;
+        case ACE355_ENC_STEP_TRANSPOSE_V: rc = launch_transpose_v(qkv, st.ld, st.v_col0, st.seqs, st.Sq, st.Hkv, h->vt, st.Sp, s); break;
+        case ACE355_ENC_STEP_VMEAN: rc = launch_vmean(qkv, st.ld, st.v_col0, st.seqs, st.Sq, st.Hkv, h->vmean, s); break;
+        case ACE355_ENC_STEP_ATTN: {
+            AttnArgs a = attn_args_rows(qkv, st.ld, qkv + st.k_col0, st.ld, h->vt, st.Sp, h->ao, st.seqs, st.Sq, st.Skv, st.Hq, st.Hkv, st.window, scale);
+            a.kv_len = st.kv_len ? kv_len_dev : nullptr;
+            a.vmean = st.kv_len ? h->vmean : nullptr;
+            rc = launch_attention(a, s);
+            break;
+        }
+        default: ACE_CHECK(false, "encoder pass: unknown step kind");
+        }
         if (rc) return rc;
     }
-    return launch_rmsnorm_mod(h->h, E.norm, out, M, D, eps, nullptr, nullptr, nullptr, nullptr, 0, S, s);
+    return 0;
 }
 
 void free_encoder(EncBase* h) {

@@ -1,5 +1,5 @@
 // lm.hip - the 5 Hz LM's forward behind ace355.h: transformers' Qwen3ForCausalLM as LLMHandler._forward_pass calls
-// it (llm_inference.py:416-438) = the text encoder's stack (encoder.hip: encoder_layers, causal) run in steps over a KV cache, and the LM
+// it (llm_inference.py:416-438) = the text encoder's stack (encoder.hip: run_encoder_pass, causal) run in steps over a KV cache, and the LM
 // head on the last column.  Prefill is the text encoder's pass with a per-sequence first visible key (textenc.hip, FIRST) plus the cache
 // store; a decode step is the same layer code at M = N rows, S = 1, with the attention below reading the cache.
 //
@@ -211,14 +211,14 @@ int launch_lm_head(const bf16_t* x, long x_stride, const bf16_t* W, float* out, 
 
 }  // namespace
 
-int ace355::launch_kv_store(const bf16_t* qkv, int ld, int k_col0, int v_col0, const KvCache& c, int layer, int N, int S, int Hkv,
+int ace355::launch_kv_store(const bf16_t* qkv, int ld, int k_col0, int v_col0, const KvCache& c, int layer, int N, int S, int Hkv, int pos0,
                             hipStream_t s) {
-    ACE_CHECK(c.kv && N > 0 && N <= c.max_seqs && S > 0 && c.pos0 >= 0 && c.pos0 + S <= c.max_pos && layer >= 0, "kv store: cache bounds");
+    ACE_CHECK(c.kv && N > 0 && N <= c.max_seqs && S > 0 && pos0 >= 0 && pos0 + S <= c.max_pos && layer >= 0, "kv store: cache bounds");
     ACE_CHECK(ld % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0, "kv store: 16-byte rows");
     const long slab = c.slab(Hkv), total = (long)N * S * Hkv * 32;
     bf16_t* kc = c.kv + (long)layer * 2 * slab;
     hipLaunchKernelGGL(kv_store_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, ld, k_col0, v_col0, kc, kc + slab,
-                       (long)Hkv * c.max_pos * 128, c.max_pos, c.pos0, S, Hkv, total);
+                       (long)Hkv * c.max_pos * 128, c.max_pos, pos0, S, Hkv, total);
     ACE_LAUNCH_CHECK();
     return 0;
 }
@@ -331,12 +331,10 @@ __global__ __launch_bounds__(64) void lm_tokens_kernel(const int64_t* __restrict
 
 // the stack over N x S rows at position pos0 (h->h embedded from ids_dev), and the head on every sequence's last row
 int lm_run(ace355_lm* h, int N, int S, int pos0, float* logits_dev, hipStream_t s) {
-    const long M = (long)N * S;
-    int rc = ensure_workspace(h, M, 0, 0, 0, 0, s);
-    if (!rc) rc = launch_embed_rows(h->embed, h->ids_dev, h->h, nullptr, M, h->D, s);
-    if (rc) return rc;
-    h->cache.pos0 = pos0;
-    rc = encoder_layers(h, h->enc, N, S, nullptr, h->xn, s, &h->cache);   // final norm of every row -> xn (bf16 [M, D])
+    const EncPassRequest rq = enc_request(*h, h->enc, N, S, false, &h->cache, pos0);
+    int rc = ensure_workspace(h, plan_encoder_workspace(&rq, 1, 0, 0), s);
+    if (!rc) rc = launch_embed_rows(h->embed, h->ids_dev, h->h, nullptr, (long)N * S, h->D, s);
+    if (!rc) rc = run_encoder_pass(h, h->enc, rq, nullptr, h->xn, s, &h->cache);   // final norm of every row -> xn (bf16 [M, D])
     if (rc) return rc;
     return launch_lm_head(h->xn + (long)(S - 1) * h->D, (long)S * h->D, h->head, logits_dev, N, h->cfg.vocab_size, h->D, s);
 }

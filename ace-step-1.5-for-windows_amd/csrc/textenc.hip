@@ -2,7 +2,7 @@
 // (Qwen3-Embedding-0.6B, init_service_loader.py:146-161) = token embedding, num_layers pre-norm decoder layers with CAUSAL self-attention,
 // final RMSNorm; and its embed_tokens row gather for the lyric ids (conditioning_embed.py:71-79).
 //
-// The decoder layer is the shared encoder stack (encoder.hip: encoder_layers, EncBase::causal) with two differences: the attention is
+// The decoder layer is the shared encoder stack (encoder.hip: run_encoder_pass, EncBase::causal) with two differences: the attention is
 // causal (a kernel of its own below, causal_gqa_attn_kernel; attn.hip is untouched), and the input is a gather from the [vocab, hidden]
 // table, not a Linear.  This file holds that kernel, the gather, the handle's two non-layer keys and create / encode / embed.
 //
@@ -301,11 +301,12 @@ int ace355_textenc_encode(ace355_textenc* h, const int32_t* ids_host, int N, int
     ACE_CHECK(N > 0 && S > 0 && N <= 65535 && (long)N * S <= ACE355_TEXTENC_MAX_TOKENS, "textenc_encode: sizes");
     hipStream_t s = (hipStream_t)stream;
     const long M = (long)N * S;
+    const EncPassRequest rq = enc_request(*h, h->enc, N, S);
     int rc = tx_upload_ids(h, ids_host, M, "textenc_encode", s);
-    if (!rc) rc = ensure_workspace(h, M, 0, 0, 0, 0, s);   // the five per-row buffers only: no V^T, no input Linear
+    if (!rc) rc = ensure_workspace(h, plan_encoder_workspace(&rq, 1, 0, 0), s);   // the five per-row buffers only: no V^T, no input Linear
     if (!rc) rc = launch_embed_rows(h->embed, h->ids_dev, h->h, nullptr, M, h->D, s);
     if (rc) return rc;
-    return encoder_layers(h, h->enc, N, S, nullptr, (bf16_t*)out_dev, s);
+    return run_encoder_pass(h, h->enc, rq, nullptr, (bf16_t*)out_dev, s);
 }
 
 int ace355_textenc_embed(ace355_textenc* h, const int32_t* ids_host, int64_t n, void* out_dev, void* stream) {

@@ -190,6 +190,42 @@ DIT_PATHS = ("bf16", "mx_quant", "mx")
 DIT_BUFS = {-1: None, 0: "xin", 1: "h", 2: "xn", 3: "qkv", 4: "ao", 5: "act", 6: "aq", 7: "xq", 8: "vt", 9: "vpad", 10: "slot_kv", 11: "tap", 12: "maps"}
 
 
+class EncoderPassRequestC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("hidden_size", "intermediate_size", "num_heads", "num_kv_heads", "num_layers", "sliding_window", "causal",
+                                         "N", "S", "has_kv_len", "has_cache", "pos0", "max_pos", "max_seqs", "has_first", "reserved")] + [
+        ("sliding_layer_mask", C.c_uint64)]
+
+
+class EncoderStepInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "kind", "layer", "src", "dst", "M", "N", "K", "norm", "proj", "lda", "ldw", "ldc", "mode", "rows_per_seq", "hn_q_cols", "hn_qk_cols",
+        "rope_row0", "sk_cnt", "seqs", "Sq", "Skv", "Hq", "Hkv", "ld", "k_col0", "v_col0", "o_ld", "Sp", "window", "kv_len", "first", "pos0", "len",
+        "chunk", "splits", "reserved")] + [("flops", C.c_double)]
+
+
+# ACE355_ENC_STEP_* / _PROJ_* / _BUF_* of include/ace355.h, by name
+ENC_STEPS = ("rmsnorm", "gemm", "kv_store", "causal_attn", "decode_attn", "transpose_v", "vmean", "attn")
+ENC_PROJS = ("qkv", "o", "gate_up", "down")
+ENC_NORMS = ("input", "post_attention", "final")
+ENC_BUFS = {-1: None, 0: "h", 1: "xn", 2: "qkv", 3: "ao", 4: "act", 5: "vt", 6: "vmean", 7: "cache", 8: "out"}
+# the fields of a step that each kind's launcher takes
+ENC_STEP_FIELDS = {
+    "rmsnorm": ("M", "N", "norm", "rows_per_seq"),
+    "gemm": ("M", "N", "K", "proj", "lda", "ldw", "ldc", "mode", "rows_per_seq", "hn_q_cols", "hn_qk_cols", "rope_row0", "sk_cnt", "flops"),
+    "kv_store": ("seqs", "Sq", "Hkv", "ld", "k_col0", "v_col0", "pos0"),
+    "causal_attn": ("seqs", "Sq", "Hkv", "ld", "k_col0", "v_col0", "o_ld", "first"),
+    "decode_attn": ("seqs", "Hkv", "ld", "len", "chunk", "splits", "first"),
+    "transpose_v": ("seqs", "Sq", "Hkv", "ld", "v_col0", "Sp"),
+    "vmean": ("seqs", "Sq", "Hkv", "ld", "v_col0"),
+    "attn": ("seqs", "Sq", "Skv", "Hq", "Hkv", "ld", "k_col0", "Sp", "window", "kv_len"),
+}
+
+
+class EncoderPassInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("M", "Sp", "QKV", "rope_rows", "n_steps")] + [("calls", C.c_int32 * len(ENC_STEPS)), ("reserved", C.c_int32),
+                                                                                        ("gemm_flops", C.c_double)]
+
+
 class LoraTermC(C.Structure):
     _fields_ = [("name", C.c_char_p), ("A_dev", C.c_void_p), ("B_dev", C.c_void_p), ("rank", C.c_int32), ("scale", C.c_float)]
 
@@ -344,6 +380,8 @@ SIGNATURES = {
     "ace355_lm_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "ace355_lm_length": (C.c_int, [C.c_void_p]),
     "ace355_lm_decode_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ace355_encoder_pass_plan": (C.c_int, [C.POINTER(EncoderPassRequestC), C.POINTER(EncoderStepInfoC), C.c_int, C.POINTER(C.c_int32),
+                                           C.POINTER(EncoderPassInfoC)]),
     "ace355_lm_pick_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ace355_lm_pick_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ace355_lm_pick": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(LmPickParamsC), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -469,6 +507,35 @@ def lm_decode_plan(length: int) -> dict:
     chunk, splits = C.c_int32(), C.c_int32()
     check(lib().ace355_lm_decode_plan(int(length), C.byref(chunk), C.byref(splits)), "lm_decode_plan")
     return {"chunk": chunk.value, "splits": splits.value}
+
+
+def encoder_pass_plan(hidden_size: int, intermediate_size: int, num_heads: int, num_kv_heads: int, num_layers: int, N: int, S: int, **fields) -> dict:
+    """`ace355_encoder_pass_plan` (include/ace355.h): the launcher calls of one pass of the encoder stack over ``N`` sequences of ``S`` rows,
+    in launch order, as the cond / detok / tok / textenc / lm handles would make them.  ``fields``: the other ace355_encoder_pass_request
+    fields (causal, sliding_window, sliding_layer_mask, has_kv_len, has_cache with pos0 / max_pos / max_seqs / has_first); left out, they are
+    0: a bidirectional stack without windows, key counts or cache.  A refusal raises with the stack's or the launcher's text.  Steps: kinds,
+    projections, norms and buffers by name, each with the fields its launcher takes; ``calls``: launcher calls per kind."""
+    rq = EncoderPassRequestC(hidden_size=hidden_size, intermediate_size=intermediate_size, num_heads=num_heads, num_kv_heads=num_kv_heads,
+                             num_layers=num_layers, N=N, S=S)
+    for k, v in fields.items():
+        assert hasattr(rq, k), k
+        setattr(rq, k, int(v))
+    n, info = C.c_int32(), EncoderPassInfoC()
+    check(lib().ace355_encoder_pass_plan(C.byref(rq), None, 0, C.byref(n), C.byref(info)), "encoder_pass_plan")
+    steps = (EncoderStepInfoC * n.value)()
+    check(lib().ace355_encoder_pass_plan(C.byref(rq), steps, n.value, C.byref(n), C.byref(info)), "encoder_pass_plan")
+    out = {k: getattr(info, k) for k in ("M", "Sp", "QKV", "rope_rows", "n_steps", "gemm_flops")}
+    out["calls"] = {ENC_STEPS[i]: int(c) for i, c in enumerate(info.calls)}
+    out["steps"] = []
+    for st in steps:
+        kind = ENC_STEPS[st.kind]
+        r = {"kind": kind, "layer": st.layer, "src": ENC_BUFS[st.src], "dst": ENC_BUFS[st.dst], **{k: getattr(st, k) for k in ENC_STEP_FIELDS[kind]}}
+        if kind == "gemm":
+            r["proj"] = ENC_PROJS[st.proj]
+        if kind == "rmsnorm":
+            r["norm"] = ENC_NORMS[st.norm]
+        out["steps"].append(r)
+    return out
 
 
 def lm_pick_plan(V: int) -> dict:

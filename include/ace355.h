@@ -842,6 +842,79 @@ int ace355_lm_length(ace355_lm* h);
  * function of the length alone - no GPU, no handle. */
 int ace355_lm_decode_plan(int length, int32_t* chunk_out, int32_t* splits_out);
 
+/* One pass of the encoder stack behind ace355_cond (two stacks), ace355_detok, ace355_tok, ace355_textenc and ace355_lm as data, in
+ * launch order: plan_encoder_pass of csrc/encoder_plan.h, which those handles execute step by step.  One step is one call of a launcher
+ * with everything it takes except pointers; buffers appear as roles.  No GPU, no handle. */
+#define ACE355_ENC_STEP_RMSNORM 0       /* launch_rmsnorm_mod: h -> xn (norm 0: input_layernorm, 1: post_attention_layernorm), h -> out (2: the final norm) */
+#define ACE355_ENC_STEP_GEMM 1          /* launch_gemm */
+#define ACE355_ENC_STEP_KV_STORE 2      /* launch_kv_store: the K / V columns of the QKV rows -> the cache at positions pos0 .. pos0 + Sq - 1 */
+#define ACE355_ENC_STEP_CAUSAL_ATTN 3   /* launch_causal_attention over the QKV rows */
+#define ACE355_ENC_STEP_DECODE_ATTN 4   /* launch_decode_attention over `len` keys of the cache */
+#define ACE355_ENC_STEP_TRANSPOSE_V 5   /* launch_transpose_v */
+#define ACE355_ENC_STEP_VMEAN 6         /* launch_vmean */
+#define ACE355_ENC_STEP_ATTN 7          /* launch_attention (bidirectional) */
+#define ACE355_ENC_STEP_KINDS 8
+#define ACE355_ENC_PROJ_QKV 0
+#define ACE355_ENC_PROJ_O 1
+#define ACE355_ENC_PROJ_GATE_UP 2
+#define ACE355_ENC_PROJ_DOWN 3
+#define ACE355_ENC_BUF_NONE (-1)
+#define ACE355_ENC_BUF_H 0              /* residual stream f32 [M][D]: the pass's input, embedded by the caller */
+#define ACE355_ENC_BUF_XN 1             /* normed rows bf16 [M][D] */
+#define ACE355_ENC_BUF_QKV 2            /* q | k | v rows bf16 [M + 64][QKV] */
+#define ACE355_ENC_BUF_AO 3             /* attention output bf16 [M][QD] */
+#define ACE355_ENC_BUF_ACT 4            /* SwiGLU output bf16 [M][F] */
+#define ACE355_ENC_BUF_VT 5             /* V^T bf16 [N][KVH][128][Sp] */
+#define ACE355_ENC_BUF_VMEAN 6          /* mean V row bf16 [N][KVH][128] */
+#define ACE355_ENC_BUF_CACHE 7          /* the handle's KV cache */
+#define ACE355_ENC_BUF_OUT 8            /* the call's output bf16 [M][D] */
+typedef struct ace355_encoder_pass_request {
+    int32_t hidden_size, intermediate_size, num_heads, num_kv_heads, num_layers;
+    int32_t sliding_window;
+    int32_t causal;                          /* 1: the text encoder's and the LM's stack; 0: bidirectional */
+    int32_t N, S;                            /* sequences, rows per sequence */
+    int32_t has_kv_len;                      /* a per-sequence key count is given (bidirectional only) */
+    int32_t has_cache;                       /* a KV cache is given (causal only), with ... */
+    int32_t pos0, max_pos, max_seqs;         /* ... the position of the call's first row, and the cache's capacity */
+    int32_t has_first;                       /* ... and per-sequence first visible keys (left padding) */
+    int32_t reserved;
+    uint64_t sliding_layer_mask;             /* bit l: layer l is sliding (bidirectional only; a causal stack does not read it) */
+} ace355_encoder_pass_request;
+typedef struct ace355_encoder_step_info {
+    int32_t kind, layer;                     /* ACE355_ENC_STEP_*; layer -1: the final norm */
+    int32_t src, dst;                        /* ACE355_ENC_BUF_*: the row operand read, the buffer written */
+    int32_t M, N, K;                         /* GEMM sizes; a norm: M rows of N columns */
+    int32_t norm;                            /* rmsnorm: which weight (see ACE355_ENC_STEP_RMSNORM); -1 otherwise */
+    int32_t proj;                            /* GEMM: ACE355_ENC_PROJ_*; -1 otherwise */
+    int32_t lda, ldw, ldc, mode;             /* GEMM: leading dimensions and GemmEpilogue::mode */
+    int32_t rows_per_seq;                    /* norms and GEMMs */
+    int32_t hn_q_cols, hn_qk_cols;           /* mode 4: the head-norm columns */
+    int32_t rope_row0;                       /* mode 4: row of the rope tables that row 0 of every sequence takes (= pos0) */
+    int32_t sk_cnt;                          /* mode 2: the handle's split-K counters are bound */
+    /* kv_store, the attentions, transpose_v, vmean */
+    int32_t seqs, Sq, Skv;
+    int32_t Hq, Hkv;
+    int32_t ld, k_col0, v_col0, o_ld;        /* row stride of the QKV rows, first K / V column, row stride of the output */
+    int32_t Sp;                              /* transpose_v, attention: the V^T row pitch */
+    int32_t window;                          /* attention: the layer's window, -1: none */
+    int32_t kv_len, first;                   /* attention: key counts (and vmean) bound; causal: first visible keys bound */
+    int32_t pos0;                            /* kv_store */
+    int32_t len, chunk, splits;              /* decode attention: keys, and plan_lm_decode(len) */
+    int32_t reserved;
+    double flops;                            /* GEMM: 2 M N K */
+} ace355_encoder_step_info;
+typedef struct ace355_encoder_pass_info {
+    int32_t M, Sp, QKV;                      /* rows, padded V^T pitch, QKV width */
+    int32_t rope_rows;                       /* rows of the rope tables the pass needs */
+    int32_t n_steps;
+    int32_t calls[ACE355_ENC_STEP_KINDS];    /* launcher calls per kind */
+    int32_t reserved;
+    double gemm_flops;
+} ace355_encoder_pass_info;
+/* A refusal is ACE355_ERR_INVALID with the text the stack or its launchers give.  steps_out may be NULL or shorter than the plan. */
+int ace355_encoder_pass_plan(const ace355_encoder_pass_request* request, ace355_encoder_step_info* steps_out, int capacity,
+                             int32_t* n_out, ace355_encoder_pass_info* info_out);
+
 /* ------------------------------------------------------------------------------------------
  * 5 Hz LM token selection: top-k, top-p and the draw on logits that already exist, i.e. what
  * LLMHandler._apply_top_k_filter, _apply_top_p_filter and _sample_tokens (llm_inference.py:367-399) do in that order.  No handle,

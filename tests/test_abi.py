@@ -43,6 +43,8 @@ def test_struct_layouts_match_header(tmp_path):
                "ace355_conv_request": native.ConvRequestC, "ace355_conv_plan_info": native.ConvPlanInfoC,
                "ace355_vae_step_info": native.VaeStepInfoC, "ace355_vae_plan_info": native.VaePlanInfoC,
                "ace355_dit_pass_request": native.DitPassRequestC, "ace355_dit_step_info": native.DitStepInfoC, "ace355_dit_pass_info": native.DitPassInfoC,
+               "ace355_encoder_pass_request": native.EncoderPassRequestC, "ace355_encoder_step_info": native.EncoderStepInfoC,
+               "ace355_encoder_pass_info": native.EncoderPassInfoC,
                "ace355_adapter_target_info": native.AdapterTargetInfoC, "ace355_adapter_launch_info": native.AdapterLaunchInfoC, "ace355_adapter_kron_info": native.AdapterKronInfoC,
                "ace355_adapter_factor_info": native.AdapterFactorInfoC, "ace355_adapter_dora_info": native.AdapterDoraInfoC,
                "ace355_adapter_plan_rows": native.AdapterPlanRowsC, "ace355_adapter_plan_info": native.AdapterPlanInfoC}
