@@ -52,6 +52,64 @@ ALL_SPLITS = {1, 2, 4, 8}
 # tests/test_cond_gpu.py::test_attention_key_padding_mask's shapes (ace355_attention_masked)
 MASKED_ROWS = [(3, 300, 300, 2, 1, 128), (2, 200, 200, 4, 2, 16), (2, 129, 129, 2, 2, -1)]
 
+# tests/test_attention_keys_gpu.py's rows (the softmax weights read back one by one through a one-hot V, tests/_attn_keys.py): small
+# shapes, each with the launch it was chosen for and, where it needs them, options: "krot" = the K rotation mode the case runs under
+# (ace355_gemm_set_k_rotation), "lens" = the key-padding mask's lengths (ace355_attention_masked), "pairs" = the (n, h) the fp64 reference
+# is computed for (all of them when left out).
+def _lens(N, cycle):
+    return tuple(cycle[i % len(cycle)] for i in range(N))
+
+
+KEY_ROWS = [
+    # attn3_kernel<4>: ragged block and tile, a narrow band, the product's window with a group size of 3, a single key
+    ((1, 70, 70, 2, 1, -1), ("attn3", 4, 1), {}), ((1, 200, 200, 2, 1, 16), ("attn3", 4, 1), {}), ((1, 300, 300, 3, 1, 128), ("attn3", 4, 1), {}),
+    ((1, 64, 1, 2, 1, -1), ("attn3", 4, 1), {}),
+    # attn3_kernel<8>: 1030 = 4 x 256 + 6, a ragged fifth block of 6 rows; the banded row's reference covers 8 (n, h) with both end
+    # sequences and the first and last head, at full Sq x Skv (every other head is still held to the zeros outside the band)
+    ((4, 1030, 130, 32, 32, -1), ("attn3", 8, 1), {}),
+    ((4, 1030, 1030, 32, 32, 40), ("attn3", 8, 1), {"pairs": ((0, 0), (0, 31), (3, 0), (3, 31), (1, 7), (2, 13), (1, 20), (2, 26))}),
+    # attn_gqa_kernel<6>; Hkv = 16: two KV heads per XCD slot (hg = 2); Hkv = 3: the generic workgroup order, a grid of 232 for 225 units
+    ((28, 100, 130, 16, 8, -1), ("gqa", 6, 1), {}), ((28, 200, 200, 16, 8, 16), ("gqa", 6, 1), {}), ((14, 100, 130, 32, 16, -1), ("gqa", 6, 1), {}),
+    ((75, 100, 130, 6, 3, -1), ("gqa", 6, 1), {}),
+    # attn_gqa_kernel<4>
+    ((14, 150, 130, 16, 8, -1), ("gqa", 4, 1), {}), ((14, 150, 150, 16, 8, 16), ("gqa", 4, 1), {}), ((38, 150, 150, 6, 3, 16), ("gqa", 4, 1), {}),
+    # attn_rot_kernel<3>
+    ((8, 100, 130, 16, 8, -1), ("rot", 3, 1), {}), ((8, 100, 100, 16, 8, 16), ("rot", 3, 1), {}), ((22, 100, 130, 6, 3, -1), ("rot", 3, 1), {}),
+    ((4, 100, 130, 32, 16, -1), ("rot", 3, 1), {}),
+    # attn_gqa_kernel<3>: K rotation mode 0 keeps the key-split kernel off
+    ((8, 100, 130, 16, 8, -1), ("gqa", 3, 1), {"krot": 0}), ((8, 100, 100, 16, 8, 16), ("gqa", 3, 1), {"krot": 0}),
+    # split-KV on attn3_kernel<4>: 4 parts; 9 tiles in 4 parts of 3 (part 3 empty); 8 parts; banded in 4 parts (the edge blocks walk 6 and 7
+    # tiles in parts of 2: part 3 empty); 2 parts (72 workgroups x 9 tiles, group size 3, three sequences)
+    ((1, 100, 520, 8, 4, -1), ("attn3", 4, 4), {}), ((1, 200, 550, 4, 2, -1), ("attn3", 4, 4), {}), ((1, 100, 1030, 16, 8, -1), ("attn3", 4, 8), {}),
+    ((1, 700, 700, 2, 1, 200), ("attn3", 4, 4), {}), ((3, 100, 520, 24, 8, -1), ("attn3", 4, 2), {}),
+    # key-padding masks on every kernel: each row's lengths hold Skv, 0, values that are no multiple of 64 and, on the banded rows, one
+    # short enough that the later queries of a live sequence see no key at all (the uniform rule beside ordinary rows)
+    ((3, 300, 300, 2, 1, 128), ("attn3", 4, 1), {"lens": (300, 100, 0)}),
+    ((28, 100, 100, 16, 8, -1), ("gqa", 6, 1), {"lens": _lens(28, (100, 0, 37, 64, 99, 1, 65))}),
+    ((14, 150, 150, 16, 8, 16), ("gqa", 4, 1), {"lens": _lens(14, (150, 0, 37, 100, 128, 1, 149))}),
+    ((8, 100, 100, 16, 8, 16), ("rot", 3, 1), {"lens": (100, 0, 37, 64, 70, 1, 99, 50)}),
+    ((8, 100, 100, 16, 8, 16), ("gqa", 3, 1), {"lens": (100, 0, 37, 64, 70, 1, 99, 50), "krot": 0}),
+]
+
+
+def key_row_id(row):
+    shape, (kernel, nw, kv_split), opts = row
+    return "-".join(["x".join(str(d) for d in shape), f"{kernel}{nw}" + (f"split{kv_split}" if kv_split > 1 else "")]
+                    + (["masked"] if "lens" in opts else []) + ([f"krot{opts['krot']}"] if "krot" in opts else []))
+
+
+def key_row_plan(row):
+    """The row's plan as the GPU test asks for it: under the scratch the unit hooks lend and, for the moment, the row's K rotation mode."""
+    from ace355 import native
+    shape, _form, opts = row
+    prev = native.gemm_set_k_rotation(opts["krot"]) if "krot" in opts else None
+    try:
+        return native.attn_plan(*shape, part_floats=native.ATTN_HOOK_PART_FLOATS, **({"has_kv_len": 1} if "lens" in opts else {}))
+    finally:
+        if prev is not None:
+            native.gemm_set_k_rotation(prev)
+
+
 HQ, HKV, WINDOW, L_COND = 16, 8, 128, 769   # the DiT at full size; 769 condition tokens as in the GPU tests' cross-attention shapes
 
 
@@ -83,6 +141,9 @@ def table_requests():
     add = lambda group, items: rows.extend((f"{group}: {n}", r) for n, r in items)
     add("test_attention", [(str(s), request(s, part_floats=PART)) for s, _form in ATTENTION_ROWS])
     add("test_attention_key_padding_mask", [(str(s), request(s, part_floats=PART, has_kv_len=1)) for s in MASKED_ROWS])
+    # (the table holds this process's plans: a row that runs under another K rotation mode is its default-mode twin here)
+    add("test_attention_keys", [(str(s) + (" masked" if "lens" in o else ""), request(s, part_floats=PART, **({"has_kv_len": 1} if "lens" in o else {})))
+                                for s, _form, o in KEY_ROWS if "krot" not in o])
     for songs in (1, 2, 4, 8):   # (by default a 2-song request runs as two chains of one song: the first group's launches)
         add(f"{songs} song{'s' if songs > 1 else ''}, CFG, T = 750", dit_launches(songs, 750))
     add("dual-chain sampler, 4 songs per chain, 128 CUs, T = 750", dit_launches(4, 750, cu_slots=128))

@@ -63,6 +63,38 @@ def test_the_gpu_test_rows_reach_every_kernel_form_and_split(table):
     assert forms == cases.ALL_FORMS and splits == cases.ALL_SPLITS, (forms, splits)
 
 
+def test_the_key_rows_reach_every_form_band_split_mask_and_workgroup_order(table):
+    """tests/test_attention_keys_gpu.py's rows take the launches they name, and together they run every instantiation full AND banded,
+    every part count of the split-KV heuristic and a banded split, a key-padding mask on every kernel, and all three arms of the GQA-family
+    kernels' workgroup decode (Hkv = 8, a larger multiple of 8, no multiple of 8) on both of them."""
+    by_name = {r["name"]: r["plan"] for r in table}
+    forms, splits, masked, decode = set(), set(), set(), set()
+    for row in cases.KEY_ROWS:
+        shape, (kernel, nw, kv_split), opts = row
+        p = cases.key_row_plan(row)
+        assert (p["kernel"], p["nw"], p["kv_split"]) == (kernel, nw, kv_split), (row, p)
+        if "krot" not in opts:
+            assert p == by_name[f"test_attention_keys: {shape}{' masked' if 'lens' in opts else ''}"], row
+        N, Sq, Skv, Hq, Hkv, window = shape
+        forms.add((kernel, nw, window >= 0))
+        splits.add((kv_split, window >= 0))
+        if "lens" in opts:
+            lens = opts["lens"]
+            assert Sq == Skv and len(lens) == N and Skv in lens and 0 in lens and any(x % 64 for x in lens), row
+            # banded: the later queries of some live sequence have no visible key
+            assert window < 0 or any(0 < x and x + window < Sq - 1 for x in lens), row
+            masked.add((kernel, nw))
+        if kernel != "attn3":
+            assert Hq == 2 * Hkv
+            decode.add((kernel, "generic" if Hkv % 8 else f"hg{Hkv // 8}"))
+            if Hkv % 8:   # surplus workgroups of the padded grid have to leave
+                assert p["grid_x"] > N * Hkv * -(-Sq // (32 * nw)), row
+    assert forms == {(k, n, b) for k, n in cases.ALL_FORMS for b in (False, True)}, forms
+    assert {s for s, _b in splits} == cases.ALL_SPLITS and any(s > 1 and b for s, b in splits), splits
+    assert {k for k, _n in masked} == {"attn3", "gqa", "rot"} and masked >= {("attn3", 4), ("gqa", 3), ("gqa", 4), ("gqa", 6), ("rot", 3)}, masked
+    assert decode == {(k, d) for k in ("gqa", "rot") for d in ("hg1", "hg2", "generic")}, decode
+
+
 # ---------------------------------------------------------------------------------------------- knobs: read once, so fresh processes
 def _spawn(env=None, krot=None):
     cmd = [sys.executable, os.path.join(cases.ROOT, "tests", "_attn_plan_cases.py"), "--plans"] + ([] if krot is None else ["--krot", str(krot)])
