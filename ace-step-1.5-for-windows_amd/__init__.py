@@ -12,6 +12,7 @@ Layout:
   lmsample.py  select_tokens / filter_logits_: top-k, top-p and the draw on the LM's logits in one native call
   lmlogits.py  shape_logits / SeenTokens / step_plan / generate_with_cfg: the LM's logits stage and its device-resident CFG loop
   audio_out.py normalize_audio, AudioSaver: GPU normalise / PCM conversion + threaded FLAC / WAV writers
+  audio_in.py  load_stereo_48k, reference_segments: WAV / FLAC payload -> clamped 48 kHz stereo on the GPU (the producer of row N3)
   backend.py   NativeDitMixin / NativeVaeMixin / NativeHandler: the reference's handler seam
   dist.py      one-process-per-GPU data-parallel runner (RCCL broadcast of conditioning)
   weightgen.py deterministic synthetic weights (no checkpoints exist on the boxes)

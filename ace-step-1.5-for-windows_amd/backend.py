@@ -37,6 +37,7 @@ MAX_BATCH_SIZE = 8  # handler/service_generate_request.py:12
 _ALIGN_POST_ENV = os.environ.get("ACE355_ALIGN_POST", "") == "1"   # read once: the default of NativeDitMixin.native_lyric_post
 _LM_SAMPLER_ENV = os.environ.get("ACE355_LM_SAMPLER", "") == "1"   # read once: the default of NativeLmMixin.use_native_lm_sampler
 _LM_LOOP_ENV = os.environ.get("ACE355_LM_LOOP", "") == "1"         # read once: the default of NativeLmMixin.use_native_lm_loop
+_AUDIO_IN_ENV = os.environ.get("ACE355_AUDIO_IN", "") == "1"       # read once: the default of NativeAudioInMixin.use_native_audio_in
 
 
 class NativeDitMixin:
@@ -610,6 +611,61 @@ class NativeLmMixin:
                                  repetition_penalty, pad_token_id, streamer, constrained_processor)
 
 
+class NativeAudioInMixin:
+    """The three loaders of ``IoAudioMixin`` (acestep/core/generation/handler/io_audio.py:39-133) on the native input stage
+    (ace355.audio_in): same signatures, same None-on-failure behaviour, but the tensor they return is already on ``self.device``, so
+    ``tiled_encode`` takes it without a copy.  Required host attribute: ``device``.  Opt-in (``use_native_audio_in``, or
+    ACE355_AUDIO_IN=1 for every host): off, each call goes to the host's own method further up the MRO, untouched."""
+
+    use_native_audio_in: bool = _AUDIO_IN_ENV
+
+    def _native_load_audio(self, audio_file):
+        """(wav fp32 [2, S] at 48 kHz on ``self.device``, max|wav|) of a WAV / FLAC file."""
+        from .audio_in import load_stereo_48k
+        return load_stereo_48k(audio_file, self.device)
+
+    def _native_audio_in(self, name: str, audio_file, reference: bool = False):
+        parent = getattr(super(), name, None)
+        if not self.use_native_audio_in:
+            if parent is None:
+                raise RuntimeError("no audio input backend available: use_native_audio_in is off and the host has no loader of its own")
+            return parent(audio_file)
+        if audio_file is None:   # (every loader of the reference: None in, None out)
+            return None
+        try:
+            wav, peak = self._native_load_audio(audio_file)
+            if not reference:
+                return wav
+            if peak < 1e-6:   # is_silence (memory_utils.py:19-21): all |x| < 1e-6
+                return None
+            from .audio_in import reference_segments
+            return reference_segments(wav)
+        except NotImplementedError as exc:   # a format, bit depth or rate the native stage does not take
+            if parent is not None:
+                logger.info("[%s] %s; the host's loader reads this file", name, exc)
+                return parent(audio_file)
+            logger.warning("[%s] %s, and the host has no loader of its own", name, exc)
+            return None
+        except (OSError, RuntimeError, ValueError) as exc:
+            if reference:
+                logger.warning("[process_reference_audio] Invalid or unsupported reference audio: %s", exc)
+            else:
+                logger.exception("[%s] Error processing audio", name)
+            return None
+
+    def process_target_audio(self, audio_file: Optional[str]) -> Optional[torch.Tensor]:
+        """io_audio.py:39-61."""
+        return self._native_audio_in("process_target_audio", audio_file)
+
+    def process_reference_audio(self, audio_file: Optional[str]) -> Optional[torch.Tensor]:
+        """io_audio.py:63-113: the 3 x 10 s cut of the clip, None for a silent one."""
+        return self._native_audio_in("process_reference_audio", audio_file, reference=True)
+
+    def process_src_audio(self, audio_file: Optional[str]) -> Optional[torch.Tensor]:
+        """io_audio.py:115-133."""
+        return self._native_audio_in("process_src_audio", audio_file)
+
+
 class _ModelShell:
     """What the mixins read from ``self.model``: decoder state dict, null embedding, config."""
 
@@ -626,7 +682,7 @@ class _ModelShell:
         self.null_condition_emb = null_condition_emb
 
 
-class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin):
+class NativeHandler(NativeDitMixin, NativeVaeMixin, NativeTextEncoderMixin, NativeAudioInMixin):
     """Self-contained counterpart of ``AceStepHandler`` for the denoise + decode path.
 
     Differences from the reference handler are confined to what is out of scope: conditioning arrives pre-embedded

@@ -285,6 +285,20 @@ class AdapterPlanInfoC(C.Structure):
         ("section_at", C.c_int64 * len(ADAPTER_SECTIONS)), ("section_bytes", C.c_int64 * len(ADAPTER_SECTIONS))]
 
 
+PCM_FORMATS = ("u8", "s16", "s24", "s32", "f32")   # ACE355_PCM_*
+PCM_BYTES = (1, 2, 3, 4, 4)
+AUDIO_IN_MAX_DENSE_TAPS = 1 << 22   # csrc/audio_in_plan.h: the largest dense tap table n x (2 width + o) the input stage takes
+
+
+class AudioInRequestC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("format", "channels", "o", "n", "K", "width")] + [("frames", C.c_int64)]
+
+
+class AudioInPlanInfoC(C.Structure):
+    _fields_ = [("out_frames", C.c_int64), ("grid", C.c_int64)] + [(n, C.c_int32) for n in (
+        "tile", "threads", "span", "table_in_lds", "lds_bytes", "passthrough")]
+
+
 # name -> (restype, argtypes); every symbol include/ace355.h declares
 SIGNATURES = {
     "ace355_last_error": (C.c_char_p, []),
@@ -402,6 +416,9 @@ SIGNATURES = {
     "ace355_wav_bound": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "ace355_wav_encode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "ace355_save_audio_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_void_p]),
+    "ace355_audio_in_plan": (C.c_int, [C.POINTER(AudioInRequestC), C.POINTER(AudioInPlanInfoC)]),
+    "ace355_audio_in_run": (C.c_int, [C.POINTER(AudioInRequestC), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     "ace355_gemm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ace355_gemm_bf16_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -544,6 +561,23 @@ def lm_pick_plan(V: int) -> dict:
     chunk, chunks = C.c_int32(), C.c_int32()
     check(lib().ace355_lm_pick_plan(int(V), C.byref(chunk), C.byref(chunks)), "lm_pick_plan")
     return {"chunk": chunk.value, "chunks": chunks.value}
+
+
+def audio_in_request(format: str, channels: int, frames: int, o: int, n: int, K: int, width: int) -> AudioInRequestC:
+    """An ace355_audio_in_request with the format by name (PCM_FORMATS)."""
+    if format not in PCM_FORMATS:
+        raise ValueError(f"unknown PCM format '{format}'")
+    return AudioInRequestC(format=PCM_FORMATS.index(format), channels=int(channels), o=int(o), n=int(n), K=int(K), width=int(width),
+                           frames=int(frames))
+
+
+def audio_in_plan(format: str, channels: int, frames: int, o: int, n: int, K: int, width: int) -> dict:
+    """`ace355_audio_in_plan` (include/ace355.h): the launch of the audio input stage for a clip of ``frames`` frames at rate
+    ``o / n x 48000`` - output frames, tile, grid, the input span a tile stages, whether the tap table sits in LDS.  A refusal raises with
+    the plan's text.  A function of the request alone; no GPU."""
+    rq, out = audio_in_request(format, channels, frames, o, n, K, width), AudioInPlanInfoC()
+    check(lib().ace355_audio_in_plan(C.byref(rq), C.byref(out)), "audio_in_plan")
+    return {k: int(getattr(out, k)) for k, _t in AudioInPlanInfoC._fields_}
 
 
 def conv_plan(B: int, M: int, N: int, Cin: int, taps: int, **bits) -> dict:

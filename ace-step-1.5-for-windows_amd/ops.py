@@ -10,6 +10,7 @@ operators (``torch.compile`` / ``torch.export`` graphs, FakeTensor shape propaga
   ace355::vae_decode    AutoencoderOobleck.decode(z).sample (handler/vae_decode_chunks.py:42,95)
   ace355::vae_encode    vae.encode(x).latent_dist.sample()  (handler/vae_encode.py:66)
   ace355::peak_normalize  post-decode peak clip             (handler/generate_music_decode.py:191-195)
+  ace355::audio_in      _normalize_audio_to_stereo_48k on a raw PCM payload (handler/io_audio.py:18-37)
 
 A native handle (``NativeDit`` / ``NativeVae``: weights packed in HBM, condition slots) is opaque state, not a tensor: it is
 registered once with ``register_handle`` and travels through the op as an integer key.  The ops have CUDA(=ROCm)
@@ -108,3 +109,19 @@ def peak_normalize(wav: Tensor) -> Tensor:
 @peak_normalize.register_fake
 def _(wav):
     return torch.empty_like(wav)
+
+
+@torch.library.custom_op("ace355::audio_in", mutates_args=(), device_types="cuda")
+def audio_in(payload: Tensor, offset: int, pcm_format: int, channels: int, frames: int, sample_rate: int) -> List[Tensor]:
+    """payload: uint8 (a multiple of 4 bytes) with ``frames`` x ``channels`` interleaved samples of ACE355_PCM_* ``pcm_format`` from byte
+    ``offset`` -> [wav fp32 [2, S] at 48 kHz clamped to [-1, 1], peak fp32 [1]]."""
+    from . import native
+    from .audio_in import resample_payload
+    wav, peak = resample_payload(payload, offset, native.PCM_FORMATS[pcm_format], channels, frames, sample_rate)
+    return [wav, peak]
+
+
+@audio_in.register_fake
+def _(payload, offset, pcm_format, channels, frames, sample_rate):
+    from .audio_in import output_frames
+    return [payload.new_empty((2, output_frames(frames, sample_rate)), dtype=torch.float32), payload.new_empty((1,), dtype=torch.float32)]

@@ -1098,6 +1098,59 @@ int ace355_save_audio_batch(const float* wav_dev, int n_items, int channels, int
                             const char* const* paths, int n_threads, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Input stage (the producer of SURVEY.md 8f row N3): what IoAudioMixin does between the file and tiled_encode,
+ * acestep/core/generation/handler/io_audio.py:18-37 (_normalize_audio_to_stereo_48k: mono duplicated :28-29, channels 0 and 1 kept
+ * :31, torchaudio.transforms.Resample(sr, 48000) :33-35, clamp to [-1, 1] :37) applied to what torchaudio.load / soundfile.read
+ * (:53, :78, :129) would have decoded - the raw interleaved PCM payload goes to the GPU instead and one kernel converts (libsndfile's
+ * PCM -> float rule), maps channels, resamples, clamps, and leaves max|x| for is_silence (memory_utils.py:19-21).  Containers are
+ * parsed and the tap table is made on the host (ace355/audio_in.py).
+ * ------------------------------------------------------------------------------------------ */
+#define ACE355_PCM_U8 0    /* (v - 128) / 128 */
+#define ACE355_PCM_S16 1   /* v / 2^15 */
+#define ACE355_PCM_S24 2   /* packed 3-byte little endian, v / 2^23 */
+#define ACE355_PCM_S32 3   /* float(v), round to nearest even, / 2^31 */
+#define ACE355_PCM_F32 4   /* IEEE float32 as is */
+
+/* With g = gcd(sr, 48000): o = sr / g, n = 48000 / g, width = ceil(6 o / (min(o, n) 0.99)) (torchaudio's sinc_interp_hann,
+ * lowpass_filter_width 6, rolloff 0.99).  K = taps kept per phase of the 2 width + o.  48 kHz: o = n = 1, K = width = 0. */
+typedef struct ace355_audio_in_request {
+    int32_t format;     /* ACE355_PCM_* */
+    int32_t channels;   /* interleaved channels in the payload, >= 1 */
+    int32_t o;
+    int32_t n;
+    int32_t K;
+    int32_t width;
+    int64_t frames;     /* input frames L */
+} ace355_audio_in_request;
+
+typedef struct ace355_audio_in_plan_info {
+    int64_t out_frames;     /* ceil(n L / o) */
+    int64_t grid;           /* workgroups: tile t owns output frames [t tile, min(out_frames, (t + 1) tile)) */
+    int32_t tile;           /* output frames per workgroup */
+    int32_t threads;
+    int32_t span;           /* input frames a workgroup stages per channel (0 at 48 kHz) */
+    int32_t table_in_lds;   /* the tap table is copied into LDS (else read from global memory) */
+    int32_t lds_bytes;
+    int32_t passthrough;    /* 48 kHz: no resampling */
+} ace355_audio_in_plan_info;
+
+/* The launch ace355_audio_in_run would make (csrc/audio_in_plan.h), a pure function of the request; no GPU.  ERR_INVALID with the
+ * reason in ace355_last_error for a request it refuses: a format outside ACE355_PCM_*, channels < 1, a rate <= 0 (o or n), o / n
+ * not sr / 48000 in lowest terms, K / width that do not fit the rate, a dense table n (2 width + o) above 2^22 taps (rates coprime
+ * to 48000 have 48000 phases; they stay with the host path), frames outside 1 .. 2^36, an output above 2^31 - 1 tiles, a rate whose
+ * smallest tile does not fit in LDS. */
+int ace355_audio_in_plan(const ace355_audio_in_request* rq, ace355_audio_in_plan_info* out);
+/* payload_dev: a device buffer of payload_bytes bytes, 4-byte aligned and allocated up to the next multiple of 4 (the kernel loads
+ * dwords and picks bytes); the samples start payload_offset bytes in, at any byte alignment: frame f, channel c at
+ * payload_offset + (f channels + c) sample_bytes.  first_dev i32 [n], taps_dev f32 [n][K]: per phase p the dense-table index of its
+ * first kept tap (0 <= first <= 2 width + o - K) and K consecutive taps k[p][first .. first + K); both may be NULL at 48 kHz.
+ * out_dev f32 [2][out_frames]: output frame j = b n + p is clamp(sum_i taps[p][i] x[b o + first[p] + i - width], -1, 1), x zero
+ * outside [0, L), accumulated in fp32 in tap order.  peak_dev f32 [1] = max|out| (a NaN in the output makes it NaN).  Enqueued on
+ * `stream`; the same call gives the same bits. */
+int ace355_audio_in_run(const ace355_audio_in_request* rq, const void* payload_dev, int64_t payload_bytes, int64_t payload_offset,
+                        const int32_t* first_dev, const float* taps_dev, float* out_dev, float* peak_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Unit kernels (test hooks; each has an oracle twin in oracle/ used by tests/)
  * ---------------------------------------------------------------------------------------- */
 /* C = A[M,K] * W[N,K]^T, bf16 in, fp32 accumulate (MFMA).  out_dtype: ACE355_DTYPE_*; bias f32 [N] or NULL. */
