@@ -37,6 +37,7 @@ MAX_BATCH_SIZE = 8  # handler/service_generate_request.py:12
 _ALIGN_POST_ENV = os.environ.get("ACE355_ALIGN_POST", "") == "1"   # read once: the default of NativeDitMixin.native_lyric_post
 _LM_SAMPLER_ENV = os.environ.get("ACE355_LM_SAMPLER", "") == "1"   # read once: the default of NativeLmMixin.use_native_lm_sampler
 _LM_LOOP_ENV = os.environ.get("ACE355_LM_LOOP", "") == "1"         # read once: the default of NativeLmMixin.use_native_lm_loop
+_LM_BATCH_ENV = os.environ.get("ACE355_LM_BATCH", "") == "1"       # read once: the default of NativeLmMixin.use_native_lm_batch
 _AUDIO_IN_ENV = os.environ.get("ACE355_AUDIO_IN", "") == "1"       # read once: the default of NativeAudioInMixin.use_native_audio_in
 
 
@@ -570,6 +571,10 @@ class NativeLmMixin:
         (``why`` is None with the flag off: nothing was asked for)."""
         if not self.use_native_lm_loop:
             return None, None
+        return self._lm_loop_accepts(batch_input_ids, batch_attention_mask, max_new_tokens)
+
+    def _lm_loop_accepts(self, batch_input_ids, batch_attention_mask, max_new_tokens):
+        """``_lm_loop_native`` whatever ``use_native_lm_loop`` says (the batched path below implies the native loop)."""
         if not isinstance(batch_input_ids, torch.Tensor) or not batch_input_ids.is_cuda or batch_input_ids.dim() != 2:
             return None, "the input ids are not a [2B, P] tensor on a CUDA device"
         from . import lm as _lm, modswap, native
@@ -609,6 +614,90 @@ class NativeLmMixin:
         from .lmlogits import generate_with_cfg
         return generate_with_cfg(self, llm, batch_input_ids, batch_attention_mask, max_new_tokens, temperature, cfg_scale, top_k, top_p,
                                  repetition_penalty, pad_token_id, streamer, constrained_processor)
+
+    # ------------------------------------------------------------------ B songs in one loop (opt-in)
+    # The reference's pt backend generates the codes of a batch one song after the other (``_run_pt``, llm_inference.py:986-1070), and
+    # its only batch caller passes the same prompt B times with B seeds (:1314-1373).  With ``use_native_lm_batch`` (ACE355_LM_BATCH=1
+    # for every host) such a call runs as ace355.lmlogits.generate_codes_batch: one prefill of the CFG pair, the cache fanned out to B
+    # + B sequences, one decode loop for all songs.  The flag implies the native loop and the native selection whatever their own
+    # flags say.  Song i comes out token for token as the sequential native loop produces it for seeds[i] - not as
+    # torch.multinomial would draw it - and the global RNG is left alone, where the reference leaves it seeded with the last item's
+    # seed.  Every other call (lmlogits.batch_request says which, and why) goes to the host's ``_run_pt`` unchanged, the reason logged
+    # once per handler (``[native-lm-batch] ...``); so does a call whose native part raises, which is safe because each sequential
+    # item resets the processor.
+    use_native_lm_batch: bool = _LM_BATCH_ENV
+    _lm_batch_reasons_logged = frozenset()
+
+    def _lm_batch_skip(self, why):
+        if why not in self._lm_batch_reasons_logged:   # once per reason and handler
+            self._lm_batch_reasons_logged = self._lm_batch_reasons_logged | {why}
+            logger.info("[native-lm-batch] %s; this request runs item by item", why)
+
+    def _run_pt_batch(self, prompt, n_items, seeds, temperature, cfg_scale, negative_prompt, top_k, top_p, repetition_penalty,
+                      use_constrained_decoding, constrained_decoding_debug, target_duration, generation_phase, caption, lyrics, cot_text):
+        """What ``_run_pt`` and ``_run_pt_single`` do around the loop, for ``n_items`` songs with one prompt: the list of their texts,
+        or None (reason logged) when the tokenised pair does not fit the native handle."""
+        from .lmlogits import batch_request, generate_codes_batch
+        tok = self.llm_tokenizer
+        texts = []
+        with self._load_model_context():
+            max_new_tokens = self._compute_max_new_tokens(target_duration=target_duration, generation_phase=generation_phase,
+                                                          fallback_max=getattr(getattr(self.llm, "config", None), "max_new_tokens", 4096))
+            uncond = self._build_unconditional_prompt(caption=caption, lyrics=lyrics, cot_text=cot_text, negative_prompt=negative_prompt,
+                                                      generation_phase=generation_phase, is_batch=False)
+            side = tok.padding_side
+            tok.padding_side = "left"
+            try:
+                pair = tok([prompt, uncond], return_tensors="pt", padding=True, truncation=True)
+            finally:
+                tok.padding_side = side
+            pair = {k: v.to(self.device) for k, v in pair.items()}
+            ids, mask = pair["input_ids"], pair.get("attention_mask", None)
+            llm, why = self._lm_loop_accepts(ids, mask, max_new_tokens)
+            ok, why = batch_request([prompt] * n_items, cfg_scale, generation_phase, use_constrained_decoding, target_duration, seeds,
+                                    loop_refusal=why if llm is None else None)
+            if not ok:
+                self._lm_batch_skip(why)
+                return None
+            group = max(llm.max_seqs // 2, 1)
+            for i0 in range(0, n_items, group):
+                proc = self._setup_constrained_processor(
+                    use_constrained_decoding=use_constrained_decoding, constrained_decoding_debug=constrained_decoding_debug,
+                    target_duration=target_duration, user_metadata=None, stop_at_reasoning=False, skip_genres=True, skip_caption=True,
+                    skip_language=True, generation_phase=generation_phase, is_batch=False)
+                out = generate_codes_batch(self, llm, ids, mask, list(seeds[i0:min(i0 + group, n_items)]), max_new_tokens, temperature,
+                                           cfg_scale, top_k, top_p, repetition_penalty, tok.pad_token_id or tok.eos_token_id, proc)
+                new = out[:, ids.shape[1]:].cpu()
+                texts += [tok.decode(row, skip_special_tokens=False) for row in new]
+        return texts
+
+    def _run_pt(self, formatted_prompts, temperature, cfg_scale, negative_prompt, top_k, top_p, repetition_penalty,
+                use_constrained_decoding=True, constrained_decoding_debug=False, target_duration=None, user_metadata=None,
+                stop_at_reasoning=False, skip_genres=True, skip_caption=False, skip_language=False, generation_phase="cot", caption="",
+                lyrics="", cot_text="", seeds=None):
+        def sequential():
+            return super(NativeLmMixin, self)._run_pt(
+                formatted_prompts, temperature, cfg_scale, negative_prompt, top_k, top_p, repetition_penalty,
+                use_constrained_decoding=use_constrained_decoding, constrained_decoding_debug=constrained_decoding_debug,
+                target_duration=target_duration, user_metadata=user_metadata, stop_at_reasoning=stop_at_reasoning,
+                skip_genres=skip_genres, skip_caption=skip_caption, skip_language=skip_language, generation_phase=generation_phase,
+                caption=caption, lyrics=lyrics, cot_text=cot_text, seeds=seeds)
+
+        if not self.use_native_lm_batch:
+            return sequential()
+        from .lmlogits import batch_request
+        ok, why = batch_request(formatted_prompts, cfg_scale, generation_phase, use_constrained_decoding, target_duration, seeds)
+        if not ok:
+            self._lm_batch_skip(why)
+            return sequential()
+        try:
+            texts = self._run_pt_batch(formatted_prompts[0], len(formatted_prompts), seeds, temperature, cfg_scale, negative_prompt, top_k,
+                                       top_p, repetition_penalty, use_constrained_decoding, constrained_decoding_debug, target_duration,
+                                       generation_phase, caption, lyrics, cot_text)
+        except Exception as exc:
+            logger.warning("[native-lm-batch] %s: %s; this request runs item by item", type(exc).__name__, exc)
+            texts = None
+        return texts if texts is not None else sequential()
 
 
 class NativeAudioInMixin:

@@ -3,7 +3,7 @@
 // head on the last column.  Prefill is the text encoder's pass with a per-sequence first visible key (textenc.hip, FIRST) plus the cache
 // store; a decode step is the same layer code at M = N rows, S = 1, with the attention below reading the cache.
 //
-// This file holds the cache store, the decode attention with its merge, the LM head, and the handle.  The cut of a cache into chunks is
+// This file holds the cache store, the cache fan-out, the decode attention with its merge, the LM head, and the handle.  The cut of a cache into chunks is
 // lm_plan.h's, a function of the length alone.  No atomics in the forward: every result has one summation order, so the same calls give
 // the same bits, and a sequence's bits do not depend on the other sequences of the batch.  (The one atomic of the file is an integer count
 // of replaced ids in lm_tokens_kernel.)
@@ -35,6 +35,41 @@ __global__ __launch_bounds__(256) void kv_store_kernel(const bf16_t* __restrict_
     const uint4 v = ldg16(qkv + (n * S + s) * ld + (is_v ? v_col0 : k_col0) + hk * 128 + ch * 8);
     bf16_t* dst = (is_v ? vc : kc) + n * seq_stride + ((long)hk * max_pos + pos0 + s) * 128 + ch * 8;
     *reinterpret_cast<uint4*>(dst) = v;
+}
+
+// ------------------------------------------------------------------------------------------------ cache fan-out
+// One wave of plan_lm_fan_out: copy c moves the K and V rows [0, len) of every layer and kv head from sequence src[c] to sequence
+// dst[c] of the same cache.  The rows below first[src] go along: decode_attn_kernel walks whole rounds of 16 keys and a masked key
+// still enters 0 x V, so every row < len of a held sequence must be a written, finite one - the source's stored pad rows are.
+// One thread = one 16-byte piece; blockIdx.y = the copy, blockIdx.x walks (layer, K | V, kv head, row, piece) with the piece fastest,
+// so a wavefront moves four whole rows.  No copy of a wave reads what another one of it writes (lm_plan.h), and a thread reads and
+// writes different sequences, so there is nothing to order inside the launch.
+struct FanOutArgs {
+    bf16_t* kv;
+    long slab, seq_stride;   // elements of one layer's K (or V) and of one sequence in it
+    int max_pos, Hkv, planes, len, count;   // planes = layers x (K, V)
+    int dst[LM_MAX_SEQS], src[LM_MAX_SEQS];
+};
+
+__global__ __launch_bounds__(256) void kv_fan_out_kernel(FanOutArgs a) {
+    const int c = blockIdx.y;
+    if (c >= a.count) return;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)a.planes * a.Hkv * a.len * 16) return;
+    const int ch = (int)(idx & 15);
+    long t = idx >> 4;
+    const int pos = (int)(t % a.len);
+    t /= a.len;
+    const int hk = (int)(t % a.Hkv);
+    const long plane = t / a.Hkv;
+    const long off = plane * a.slab + ((long)hk * a.max_pos + pos) * 128 + ch * 8;
+    *reinterpret_cast<uint4*>(a.kv + off + a.dst[c] * a.seq_stride) = ldg16(a.kv + off + a.src[c] * a.seq_stride);
+}
+
+// first[n] of the fanned-out sequences, by value: the host knows them, and a kernel argument needs no host buffer that outlives the call
+struct FirstArgs { int first[LM_MAX_SEQS]; };
+__global__ __launch_bounds__(64) void lm_set_first_kernel(FirstArgs a, int N, int* __restrict__ first) {
+    if ((int)threadIdx.x < N) first[threadIdx.x] = a.first[threadIdx.x];
 }
 
 // ------------------------------------------------------------------------------------------------ decode attention
@@ -252,6 +287,7 @@ struct ace355_lm : EncBase {
     int* first_dev = nullptr;  // [max_seqs]
     KvCache cache;             // allocated at the first prefill, kept for the handle's life
     int n_seqs = 0, length = 0;
+    int first_host[LM_MAX_SEQS] = {};   // first_dev's values for the n_seqs sequences held (ace355_lm_fan_out plans from them)
     unsigned long long* bad_dev = nullptr;   // out-of-range tokens ace355_lm_decode_tokens replaced; allocated with the cache
     hipStream_t tokens_stream = nullptr;     // the stream of the last ace355_lm_decode_tokens
 };
@@ -287,6 +323,20 @@ int lm_refuse(const std::string& msg) {
     return ACE355_ERR_INVALID;
 }
 
+int launch_rc() {
+    ACE_LAUNCH_CHECK();
+    return 0;
+}
+
+const char* fan_out_refusal(int why) {   // plan_lm_fan_out's codes
+    switch (why) {
+        case 1: return "1 .. 16 sequences, before and after";
+        case 2: return "src must be non-decreasing";
+        case 3: return "src[n] must be in [0, n]";
+        default: return "src[n] names a sequence the handle does not hold";
+    }
+}
+
 // checked host ids -> the handle's device buffer (the caller's array may be reused as soon as this returns)
 int lm_upload_ids(ace355_lm* h, const int32_t* ids, long n, hipStream_t s) {
     if (n > h->ids_cap) {
@@ -294,8 +344,9 @@ int lm_upload_ids(ace355_lm* h, const int32_t* ids, long n, hipStream_t s) {
         if (h->ids_dev) hipFree(h->ids_dev);
         h->ids_dev = nullptr;
         h->ids_cap = 0;
-        ACE_HIP(hipMalloc((void**)&h->ids_dev, sizeof(int) * n + 256));
-        h->ids_cap = n;
+        const long cap = n > LM_MAX_SEQS ? n : LM_MAX_SEQS;   // a decode step of any fan-out of this prefill fits
+        ACE_HIP(hipMalloc((void**)&h->ids_dev, sizeof(int) * cap + 256));
+        h->ids_cap = cap;
     }
     ACE_HIP(hipMemcpyAsync(h->ids_dev, ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
     ACE_HIP(hipStreamSynchronize(s));
@@ -420,8 +471,58 @@ int ace355_lm_prefill(ace355_lm* h, const int32_t* ids_host, const int32_t* firs
     ACE_HIP(hipStreamSynchronize(s));   // `first_host` is caller memory
     rc = lm_run(h, N, P, 0, logits_dev, s);
     if (rc) return rc;
+    for (int n = 0; n < N; ++n) h->first_host[n] = first_host[n];
     h->n_seqs = N;
     h->length = P;
+    return ACE355_OK;
+}
+
+int ace355_lm_fan_out(ace355_lm* h, const int32_t* src_host, int n_new, void* stream) {
+    ACE_CHECK(h && src_host, "lm_fan_out: null argument");
+    if (h->length <= 0 || h->n_seqs <= 0) return lm_refuse("lm_fan_out: no prefill to fan out");
+    if (n_new < 1 || n_new > h->cfg.max_seqs)
+        return lm_refuse("lm_fan_out: " + std::to_string(n_new) + " sequences, the handle holds max_seqs = " +
+                         std::to_string(h->cfg.max_seqs));
+    LmFanOutPlan plan;
+    const int why = plan_lm_fan_out(src_host, n_new, h->n_seqs, &plan);
+    if (why) return lm_refuse(std::string("lm_fan_out: ") + fan_out_refusal(why) + " (" + std::to_string(h->n_seqs) + " sequences held)");
+    ACE_CHECK(h->cache.kv && h->first_dev && h->ids_cap >= n_new, "lm_fan_out: the handle's cache");
+    // nothing was refused
+    hipStream_t s = (hipStream_t)stream;
+    const KvCache& c = h->cache;
+    FirstArgs fa{};
+    for (int n = 0; n < n_new; ++n) fa.first[n] = h->first_host[src_host[n]];
+    int rc = 0;
+    for (int w = 0; w < plan.n_waves && !rc; ++w) {
+        FanOutArgs a{c.kv, c.slab(h->KVH), (long)h->KVH * c.max_pos * 128, c.max_pos, h->KVH, 2 * h->cfg.num_layers, h->length, 0, {}, {}};
+        for (int n = 0; n < n_new; ++n) {
+            if (plan.wave_of[n] != w) continue;
+            a.dst[a.count] = n;
+            a.src[a.count] = src_host[n];
+            ++a.count;
+        }
+        const long total = (long)a.planes * a.Hkv * a.len * 16;
+        if (a.count == 0 || total <= 0) continue;   // (a cache without layers)
+        hipLaunchKernelGGL(kv_fan_out_kernel, dim3((unsigned)((total + 255) / 256), a.count), dim3(256), 0, s, a);
+        rc = launch_rc();
+    }
+    if (!rc) {
+        hipLaunchKernelGGL(lm_set_first_kernel, dim3(1), dim3(64), 0, s, fa, n_new, h->first_dev);
+        rc = launch_rc();
+    }
+    if (rc) { h->length = 0; h->n_seqs = 0; return rc; }   // a failed launch: the cache is not trustworthy
+    for (int n = 0; n < n_new; ++n) h->first_host[n] = fa.first[n];
+    h->n_seqs = n_new;
+    return ACE355_OK;
+}
+
+int ace355_lm_fan_out_plan(const int32_t* src, int n_new, int n_old, int32_t* wave_out, int32_t* n_waves_out) {
+    ACE_CHECK(src && wave_out && n_waves_out, "lm_fan_out_plan: null argument");
+    LmFanOutPlan plan;
+    const int why = plan_lm_fan_out(src, n_new, n_old, &plan);
+    if (why) return lm_refuse(std::string("lm_fan_out_plan: ") + fan_out_refusal(why));
+    for (int n = 0; n < n_new; ++n) wave_out[n] = plan.wave_of[n];
+    *n_waves_out = plan.n_waves;
     return ACE355_OK;
 }
 

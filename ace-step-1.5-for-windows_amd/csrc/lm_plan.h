@@ -1,5 +1,5 @@
-// lm_plan.h - the launch decision of the LM's decode attention (lm.hip) as data, in the shape of attn_plan.h / gemm_plan.h: how the keys
-// [0, len) of one sequence are cut into chunks, one workgroup per (sequence, kv head, chunk), merged afterwards in chunk order.
+// lm_plan.h - the launch decisions of the LM (lm.hip: decode attention, cache fan-out; lm_sample.hip: token selection) as data, in the
+// shape of attn_plan.h / gemm_plan.h.  The decode attention: how the keys [0, len) of one sequence are cut into chunks, one workgroup per (sequence, kv head, chunk), merged afterwards in chunk order.
 // plan_lm_decode is a pure function of the current length ALONE: it reads no global, no environment, makes no HIP call, and does not see
 // the number of sequences - so the bits of a sequence's logits do not depend on how many others decode beside it.
 #pragma once
@@ -23,6 +23,39 @@ inline LmDecodePlan plan_lm_decode(int len) {
     p.chunk = len <= 256 ? 64 : len <= 1024 ? 128 : 256;
     p.splits = len > 0 ? (len + p.chunk - 1) / p.chunk : 0;
     return p;
+}
+
+// ------------------------------------------------------------------------------------------------ cache fan-out (lm.hip)
+// The cache's n_old sequences become n_new: new sequence n holds old sequence src[n].  The copy is in place, so the order matters:
+// with src = [0, 0, 1, 1] destination 1 overwrites old sequence 1 while destinations 2 and 3 still read it.  plan_lm_fan_out puts the
+// copies into waves, one launch each, such that no wave reads a sequence that the same or an earlier wave writes: a copy's wave is
+// one more than the last wave that reads its destination.  src is non-decreasing with src[n] <= n, so every reader of old sequence n
+// is a destination m > n and one walk from the last destination down settles all of them.  A destination with src[n] == n stays
+// where it is and is in no wave.  Pure: no global, no environment, no HIP call.
+struct LmFanOutPlan {
+    int n_waves;                // launches; 0 when every sequence stays
+    int wave_of[LM_MAX_SEQS];   // of destination n: its wave, or -1 for src[n] == n
+};
+
+// 0, or which rule the request breaks: 1 n_new / n_old outside 1 .. LM_MAX_SEQS, 2 a decreasing src, 3 src[n] > n (or < 0),
+// 4 src[n] >= n_old.  A refused request leaves *p untouched.
+inline int plan_lm_fan_out(const int* src, int n_new, int n_old, LmFanOutPlan* p) {
+    if (n_new < 1 || n_new > LM_MAX_SEQS || n_old < 1 || n_old > LM_MAX_SEQS) return 1;
+    for (int n = 0; n < n_new; ++n) {
+        if (n > 0 && src[n] < src[n - 1]) return 2;
+        if (src[n] < 0 || src[n] > n) return 3;
+        if (src[n] >= n_old) return 4;
+    }
+    LmFanOutPlan q{};
+    int after[LM_MAX_SEQS] = {};   // of old sequence n: the first wave in which it may be overwritten
+    for (int n = n_new - 1; n >= 0; --n) {
+        if (src[n] == n) { q.wave_of[n] = -1; continue; }
+        q.wave_of[n] = after[n];
+        if (after[n] + 1 > q.n_waves) q.n_waves = after[n] + 1;
+        if (after[n] + 1 > after[src[n]]) after[src[n]] = after[n] + 1;
+    }
+    *p = q;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ token selection (lm_sample.hip)

@@ -178,6 +178,24 @@ class NativeCausalLM(native.Owner):
                          "lm_decode_tokens")
         return out
 
+    def fan_out(self, src) -> None:
+        """``ace355_lm_fan_out``: the cache's sequences become ``len(src)`` sequences of the same length, sequence ``n`` a copy of
+        old sequence ``src[n]`` (``src`` non-decreasing, ``src[n] <= n``).  B songs with one prompt: prefill the ``[2, P]`` pair, then
+        ``fan_out([0] * B + [1] * B)``.  In place, on the current stream, nothing is read back; tokens of earlier calls go stale."""
+        if self._first is None:
+            raise ValueError("ace355: LM fan-out without a prefill")
+        src = [int(v) for v in src]
+        n_old = len(self._first)
+        if not 1 <= len(src) <= self.max_seqs:
+            raise ValueError(f"ace355: a fan-out to {len(src)} sequences, the handle holds 1 .. {self.max_seqs}")
+        if any(s > n or s >= n_old or s < 0 or (n and s < src[n - 1]) for n, s in enumerate(src)):
+            raise ValueError(f"ace355: fan-out src {src} must be non-decreasing with src[n] <= n and src[n] < {n_old}")
+        arr = (C.c_int32 * len(src))(*src)
+        self._generation += 1
+        with torch.cuda.device(self.device):
+            native.check(self._lib.ace355_lm_fan_out(self._h, arr, len(src), native.current_stream_ptr()), "lm_fan_out")
+        self._first = [self._first[s] for s in src]
+
     def bad_tokens(self) -> int:
         """Out-of-vocabulary ids ``decode_tokens`` has replaced since the last call of this method (one synchronisation; clears)."""
         with torch.cuda.device(self.device):

@@ -8,7 +8,9 @@ transformers' ``RepetitionPenaltyLogitsProcessor``; then ``_update_constrained_p
 * ``shape_logits`` is the stage as one native launch (``ace355_lm_shape``; semantics, exactly: include/ace355.h above that call);
 * ``SeenTokens`` is the bitmap of ids the repetition penalty reads (``ace355_lm_seen_mark``);
 * ``step_plan`` decides, from the processor's attributes alone, what one step of the loop is;
-* ``generate_with_cfg`` is the loop (``NativeLmMixin._generate_with_cfg_custom`` calls it when ``use_native_lm_loop`` is set).
+* ``generate_with_cfg`` is the loop (``NativeLmMixin._generate_with_cfg_custom`` calls it when ``use_native_lm_loop`` is set);
+* ``generate_codes_batch`` is that loop for B songs that share one prompt, each with the tokens the loop gives it alone, and
+  ``batch_request`` decides which ``_run_pt`` calls are such batches (``NativeLmMixin._run_pt``, ``use_native_lm_batch``).
 
 The native stage covers the processor's branches that are a fixed mask plus one EOS rule: no processor, a disabled one, ``COMPLETED``
 and ``CODES_GENERATION``.  Every other FSM state runs the reference's own torch code on the native forward's logits, as before.
@@ -249,3 +251,148 @@ def generate_with_cfg(handler, lm, batch_input_ids: torch.Tensor, batch_attentio
         raise RuntimeError(f"ace355: the native LM loop drew no valid token at some step (a logits row with a NaN, a +inf or no finite "
                            f"entry; {replaced} ids replaced in the forward); the constrained processor has advanced {steps} steps")
     return torch.cat([ids, tokens[:steps].t().repeat(2, 1).to(ids.dtype)], dim=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- B songs, one loop
+def batch_request(formatted_prompts, cfg_scale, generation_phase, use_constrained_decoding, target_duration, seeds,
+                  loop_refusal: Optional[str] = None):
+    """``(ok, why)``: may a ``_run_pt`` call run as one batched loop (``generate_codes_batch``)?  Pure.  The reference's only batch
+    caller passes the same prompt B times with B seeds (llm_inference.py:1314-1373); everything else stays sequential.
+    ``loop_refusal``: why ``NativeLmMixin._lm_loop_accepts`` turned the tokenised pair down, once that is known."""
+    if not isinstance(formatted_prompts, list) or len(formatted_prompts) < 2:
+        return False, "the prompts are not a list of two or more"
+    if any(not isinstance(p, str) or p != formatted_prompts[0] for p in formatted_prompts):
+        return False, "the prompts of the batch differ"
+    if not cfg_scale > 1.0:
+        return False, f"cfg_scale {cfg_scale} runs no CFG pair"
+    if generation_phase != "codes":
+        return False, f"generation phase '{generation_phase}' is not 'codes'"
+    if not use_constrained_decoding:
+        return False, "constrained decoding is off, so nothing ends every song at the same step"
+    if target_duration is None or not target_duration > 0:
+        return False, "no target duration, so nothing ends every song at the same step"
+    if (not isinstance(seeds, (list, tuple)) or len(seeds) < len(formatted_prompts)
+            or any(isinstance(s, bool) or not isinstance(s, int) for s in seeds[:len(formatted_prompts)])):
+        return False, "seeds does not hold an int for every item"
+    if loop_refusal is not None:
+        return False, loop_refusal
+    return True, None
+
+
+def generate_codes_batch(handler, lm, pair_ids: torch.Tensor, pair_mask: Optional[torch.Tensor], seeds, max_new_tokens: int,
+                         temperature: float, cfg_scale: float, top_k: Optional[int], top_p: Optional[float], repetition_penalty: float,
+                         pad_token_id: int, constrained_processor) -> torch.Tensor:
+    """The audio codes of ``B = len(seeds)`` songs that share one prompt, in one CFG loop: int64 ``[B, P + steps]``, the B conditional
+    rows.  Row i equals the conditional row of ``generate_with_cfg(handler, lm, pair_ids, pair_mask, ...)`` called right after
+    ``torch.manual_seed(seeds[i]); torch.cuda.manual_seed_all(seeds[i])`` with a freshly reset processor - what the reference's
+    ``_run_pt`` does per item (llm_inference.py:1021-1059).
+
+    ``pair_ids`` ``[2, P]``: the conditional and the unconditional prompt, left-padded.  The pair is prefilled once; its staged row
+    is expanded to B rows, B tokens are selected, the cache is fanned out to B conditional + B unconditional sequences
+    (``lm.fan_out``) and every later step decodes all 2B.  Row i draws its uniforms from a generator of its own, seeded ``seeds[i]``:
+    the t-th is the t-th ``torch.rand(1)`` after that seeding, and the global generators are not touched.  The processor counts once
+    per step (codes per song) and is left as the last sequential item would leave it.  Needs an enabled processor with
+    ``target_codes`` and ``eos_token_id``: EOS is blocked until the count is reached and then forced, so every row stops at the same
+    step; a step that finds only some rows stopped raises.  Leaves ``handler._lm_loop_stats`` (plus ``batch``, ``prefill_rows``)."""
+    from . import lmsample
+    proc = constrained_processor
+    if proc is None or not proc.enabled or proc.target_codes is None or proc.eos_token_id is None:
+        raise RuntimeError("ace355: the batched LM loop needs an enabled constrained processor with target_codes and eos_token_id "
+                           "(nothing else ends every song at the same step)")
+    seeds = [int(s) for s in seeds]
+    B = len(seeds)
+    if pair_ids.dim() != 2 or pair_ids.shape[0] != 2:
+        raise ValueError("ace355: the batched LM loop takes the [2, P] pair of conditional and unconditional ids")
+    if not 1 <= B or 2 * B > lm.max_seqs:
+        raise ValueError(f"ace355: {B} songs need {2 * B} sequences, the native LM holds {lm.max_seqs}")
+    ids = pair_ids
+    dev = ids.device
+    P = ids.shape[1]
+    V = lm.cfg.vocab_size
+    eos = handler.llm_tokenizer.eos_token_id
+    if eos is None:
+        eos = pad_token_id
+    penalty = float(repetition_penalty)
+    sample = temperature > 0
+    stats = {"steps": 0, "native_steps": 0, "sync_free_steps": 0, "token_reads": 0, "batch": B, "prefill_rows": 2}
+    handler._lm_loop_stats = stats
+    tokens = torch.empty(max(int(max_new_tokens), 1), B, dtype=torch.int64, device=dev)   # row t: the tokens of step t
+    prompt = ids[:1].to(torch.int64).expand(B, P)                                         # every song's conditional row
+    seen = SeenTokens(B, V, dev).mark(prompt) if penalty != 1.0 else None
+    gens = [torch.Generator(device=dev).manual_seed(s) for s in seeds] if sample else []
+    u = torch.empty(B, dtype=torch.float32, device=dev) if sample else None
+    stop_ids = {eos} | ({pad_token_id} if pad_token_id is not None else set())
+    blocked, blocked_for = None, None
+    steps, bad_draw = 0, False
+    lm.bad_tokens()   # whatever an earlier user of the handle left uncounted is not this call's
+
+    with torch.inference_mode():
+        for step in range(int(max_new_tokens)):
+            logits = lm.prefill(ids, pair_mask) if step == 0 else lm.decode_tokens(tokens[step - 1])
+            if lm.out_dtype != torch.float32:
+                logits = logits.to(lm.out_dtype).float()   # the model's own output dtype, upcast as llm_inference.py:2482 does
+            n = 1 if step == 0 else B
+            cond, uncond = logits[:n], logits[n:]
+            if _state_name(proc.state) == "CODES_GENERATION" and proc.non_audio_code_mask is not None:
+                m = _codes_mask(proc, "non_audio_code_mask", dev)
+                if blocked_for is not proc.non_audio_code_mask:   # once per call: which of the loop's stop ids the mask rules out
+                    known = [t for t in stop_ids if 0 <= t < m.shape[0]]
+                    vals = m[torch.tensor(known, dtype=torch.int64, device=dev)].tolist() if known else []
+                    blocked = frozenset(t for t, v in zip(known, vals) if v == NEG_INF)
+                    blocked_for = proc.non_audio_code_mask
+            plan = step_plan(StepView(proc, eos, pad_token_id, False, blocked))
+            if plan.native:
+                if step == 0:   # one staged row per song: the penalty's bitmap and the selection have B rows
+                    cond, uncond = cond.repeat(B, 1), uncond.repeat(B, 1)
+                mask = None
+                if plan.mask is not None:
+                    mask = _codes_mask(proc, "audio_code_mask" if _state_name(proc.state) == "COMPLETED" else "non_audio_code_mask", dev)
+                x = shape_logits(cond, uncond, cfg_scale, mask, proc.eos_token_id if plan.eos_mode else None, plan.eos_mode,
+                                 plan.temperature, penalty, seen, out=cond)
+                stats["native_steps"] += 1
+            else:   # the reference's processor on the pair's row (THINK_TAG -> CODES_GENERATION is made in its __call__)
+                if step != 0:
+                    raise RuntimeError(f"ace355: the constrained processor left the codes phase at step {step} of a batched loop "
+                                       f"(state {_state_name(proc.state)})")
+                cur = ids[:1]
+                x = uncond + cfg_scale * (cond - uncond)
+                x = proc(cur, x)
+                for lp in handler._build_logits_processor(repetition_penalty):
+                    x = lp(cur, x)
+                x = x.repeat(B, 1)
+            for i, g in enumerate(gens):   # row i's own stream of uniforms: one torch.rand(1) per step, as the B = 1 loop draws
+                torch.rand(1, generator=g, out=u[i:i + 1])
+            toks = lmsample.pick(x, top_k, top_p, temperature, u)[0]
+            tokens[step] = toks
+            steps = step + 1
+            if seen is not None:
+                seen.mark(tokens[step])
+            if step == 0:
+                lm.fan_out([0] * B + [1] * B)
+            if plan.native and plan.sync_free:
+                proc.update_state(0)   # CODES_GENERATION only counts (update_state :2153-2158), once per step: codes per song
+                stats["sync_free_steps"] += 1
+                continue
+            host = toks.tolist()
+            stats["token_reads"] += 1
+            if min(host) < 0:
+                bad_draw = True
+                break
+            proc.update_state(host[0])
+            if _state_name(proc.state) != "CODES_GENERATION":
+                raise RuntimeError(f"ace355: the constrained processor is in state {_state_name(proc.state)} after step {step} of a "
+                                   f"batched loop; only the codes phase runs batched")
+            stopped = [t in stop_ids for t in host]
+            if any(stopped) and not all(stopped):
+                raise RuntimeError(f"ace355: songs {[i for i, s in enumerate(stopped) if s]} of {B} stopped at step {step} and the "
+                                   f"others did not; the batched LM loop returns no ragged rows")
+            if all(stopped):
+                break
+    stats["steps"] = steps
+    replaced = lm.bad_tokens() if steps > 1 else 0
+    if not bad_draw and steps:
+        bad_draw = bool((tokens[:steps] < 0).any())
+    if bad_draw or replaced:
+        raise RuntimeError(f"ace355: the native LM loop drew no valid token at some step (a logits row with a NaN, a +inf or no finite "
+                           f"entry; {replaced} ids replaced in the forward); the constrained processor has advanced {steps} steps")
+    return torch.cat([prompt, tokens[:steps].t()], dim=1)

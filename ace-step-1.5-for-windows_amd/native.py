@@ -405,6 +405,8 @@ SIGNATURES = {
     "ace355_lm_seen_mark": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ace355_lm_decode_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ace355_lm_bad_tokens": (C.c_int64, [C.c_void_p]),
+    "ace355_lm_fan_out": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
+    "ace355_lm_fan_out_plan": (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ace355_peak_normalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "ace355_latent_check": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_void_p]),
     "ace355_normalize_audio": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
@@ -524,6 +526,17 @@ def lm_decode_plan(length: int) -> dict:
     chunk, splits = C.c_int32(), C.c_int32()
     check(lib().ace355_lm_decode_plan(int(length), C.byref(chunk), C.byref(splits)), "lm_decode_plan")
     return {"chunk": chunk.value, "splits": splits.value}
+
+
+def lm_fan_out_plan(src, n_old: int) -> list:
+    """`ace355_lm_fan_out_plan` (include/ace355.h): the launches of ``ace355_lm_fan_out`` for ``src`` on a handle that holds ``n_old``
+    sequences, as a list of waves, each a list of ``(dst, src)`` copies in ascending ``dst``.  No wave reads a sequence that the same or
+    an earlier wave writes; a sequence that stays (``src[n] == n``) is in no wave.  A refusal raises.  No GPU, no handle."""
+    src = [int(v) for v in src]
+    n = len(src)
+    arr, waves, n_waves = (C.c_int32 * max(n, 1))(*src), (C.c_int32 * max(n, 1))(), C.c_int32()
+    check(lib().ace355_lm_fan_out_plan(arr, n, int(n_old), waves, C.byref(n_waves)), "lm_fan_out_plan")
+    return [[(d, src[d]) for d in range(n) if waves[d] == w] for w in range(n_waves.value)]
 
 
 def encoder_pass_plan(hidden_size: int, intermediate_size: int, num_heads: int, num_kv_heads: int, num_layers: int, N: int, S: int, **fields) -> dict:

@@ -991,6 +991,21 @@ int ace355_lm_decode_tokens(ace355_lm* h, const int64_t* tokens_dev, int B, floa
  * stream of the last ace355_lm_decode_tokens call, with one synchronisation of that stream.  0 when that call was never made;
  * < 0 for a null handle or a HIP error. */
 int64_t ace355_lm_bad_tokens(ace355_lm* h);
+/* Cache fan-out: after a prefill (and any decode steps that followed it) the handle holds n_old sequences of length L; afterwards it
+ * holds n_new sequences of length L, and sequence n has the K and V rows [0, L) of every layer and kv head of old sequence src[n]
+ * (its stored pad rows below first[src[n]] included: the decode attention reads them, masked) and that sequence's first - as if every
+ * read happened before any write.  B songs that share one prompt are prefilled once,
+ * as the [2, P] CFG pair, and fanned out with src = [0] * B + [1] * B.  The copy is in place (no scratch): one launch per wave of
+ * ace355_lm_fan_out_plan, in wave order, plus one tiny launch for first; stream-ordered on `stream`, which must be the stream of the
+ * calls around it, and without a host synchronisation.  src host int32 [n_new] is read before the call returns.
+ * ACE355_ERR_INVALID before any launch, with the handle unchanged: without a prefill, n_new outside 1 .. max_seqs, src decreasing,
+ * src[n] outside [0, n], src[n] >= n_old. */
+int ace355_lm_fan_out(ace355_lm* h, const int32_t* src_host, int n_new, void* stream);
+/* The launch order of ace355_lm_fan_out as data (plan_lm_fan_out, csrc/lm_plan.h): wave_out[n] = the wave in which destination n is
+ * written, -1 for a sequence that stays (src[n] == n); *n_waves_out = launches.  No wave reads a sequence that the same or an earlier
+ * wave writes.  A pure function of src and n_old - no GPU, no handle; refuses what ace355_lm_fan_out refuses of src, with
+ * 1 .. ACE355_LM_MAX_SEQS in place of max_seqs. */
+int ace355_lm_fan_out_plan(const int32_t* src, int n_new, int n_old, int32_t* wave_out, int32_t* n_waves_out);
 
 /* ------------------------------------------------------------------------------------------
  * Audio-token detokenizer of the LM-hint path: AudioTokenDetokenizer.forward,
