@@ -11,6 +11,7 @@ Layout:
   lm.py        NativeCausalLM: the 5 Hz LM's forward (Qwen3ForCausalLM): prefill, KV-cached decode steps, last-position logits
   lmsample.py  select_tokens / filter_logits_: top-k, top-p and the draw on the LM's logits in one native call
   lmlogits.py  shape_logits / SeenTokens / step_plan / generate_with_cfg: the LM's logits stage and its device-resident CFG loop
+  lmscore.py   calculate_pmi_score_per_condition and its helpers: the reference's LM quality score on NativeCausalLM.score
   audio_out.py normalize_audio, AudioSaver: GPU normalise / PCM conversion + threaded FLAC / WAV writers
   audio_in.py  load_stereo_48k, reference_segments: WAV / FLAC payload -> clamped 48 kHz stereo on the GPU (the producer of row N3)
   backend.py   NativeDitMixin / NativeVaeMixin / NativeHandler: the reference's handler seam

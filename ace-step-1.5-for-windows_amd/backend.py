@@ -38,6 +38,7 @@ _ALIGN_POST_ENV = os.environ.get("ACE355_ALIGN_POST", "") == "1"   # read once: 
 _LM_SAMPLER_ENV = os.environ.get("ACE355_LM_SAMPLER", "") == "1"   # read once: the default of NativeLmMixin.use_native_lm_sampler
 _LM_LOOP_ENV = os.environ.get("ACE355_LM_LOOP", "") == "1"         # read once: the default of NativeLmMixin.use_native_lm_loop
 _LM_BATCH_ENV = os.environ.get("ACE355_LM_BATCH", "") == "1"       # read once: the default of NativeLmMixin.use_native_lm_batch
+_LM_SCORE_ENV = os.environ.get("ACE355_LM_SCORE", "") == "1"       # read once: the default of NativeLmMixin.use_native_lm_score
 _AUDIO_IN_ENV = os.environ.get("ACE355_AUDIO_IN", "") == "1"       # read once: the default of NativeAudioInMixin.use_native_audio_in
 
 
@@ -504,6 +505,23 @@ class NativeLmMixin:
             logger.warning("[native-lm] init failed (%s: %s); PyTorch path stays active", type(exc).__name__, exc)
             self.use_native_lm = False
             return False
+
+    # ------------------------------------------------------------------ the quality score (opt-in)
+    # ``ace355.lmscore`` carries the reference's scoring entry points (acestep/core/scoring/lm_score.py) on ``NativeCausalLM.score``:
+    # per target token one log-probability and one rank from the GPU instead of [T, V] logits on the host.  It takes the native path
+    # only with this flag set (ACE355_LM_SCORE=1 turns it on for every host); ranks among EQUAL logits are by ascending id there,
+    # where torch.topk's order is unspecified, which is why it is opt-in.
+    use_native_lm_score: bool = _LM_SCORE_ENV
+
+    def get_hf_model_for_scoring(self):
+        """The reference's scoring reads the logits of EVERY position of ``model(input_ids, attention_mask)``; the native swap answers
+        that call with the last column only ([1, 1, V]).  On the ``pt`` backend with the swap installed this therefore hands out the
+        kept ``Qwen3ForCausalLM`` instead of ``self.llm``; everything else is the host's own answer."""
+        from . import modswap
+        llm = getattr(self, "llm", None)
+        if getattr(self, "llm_backend", "pt") == "pt" and isinstance(llm, modswap.NativeCausalLMSwap):
+            return llm._reference
+        return super().get_hf_model_for_scoring()
 
     # ------------------------------------------------------------------ token selection (opt-in)
     # The reference's loops call _apply_top_k_filter, _apply_top_p_filter and _sample_tokens in that order on one tensor

@@ -3,7 +3,8 @@
 // head on the last column.  Prefill is the text encoder's pass with a per-sequence first visible key (textenc.hip, FIRST) plus the cache
 // store; a decode step is the same layer code at M = N rows, S = 1, with the attention below reading the cache.
 //
-// This file holds the cache store, the cache fan-out, the decode attention with its merge, the LM head, and the handle.  The cut of a cache into chunks is
+// This file holds the cache store, the cache fan-out, the decode attention with its merge, the LM head, and the handle (ace355_lm_score runs
+// the prefill's pass and hands the final norm of the target rows to lm_score.hip).  The cut of a cache into chunks is
 // lm_plan.h's, a function of the length alone.  No atomics in the forward: every result has one summation order, so the same calls give
 // the same bits, and a sequence's bits do not depend on the other sequences of the batch.  (The one atomic of the file is an integer count
 // of replaced ids in lm_tokens_kernel.)
@@ -290,6 +291,8 @@ struct ace355_lm : EncBase {
     int first_host[LM_MAX_SEQS] = {};   // first_dev's values for the n_seqs sequences held (ace355_lm_fan_out plans from them)
     unsigned long long* bad_dev = nullptr;   // out-of-range tokens ace355_lm_decode_tokens replaced; allocated with the cache
     hipStream_t tokens_stream = nullptr;     // the stream of the last ace355_lm_decode_tokens
+    char* score_ws = nullptr;                // ace355_lm_score: row list, targets and the rows entry's workspace; grows on demand
+    size_t score_cap = 0;
 };
 
 namespace {
@@ -380,14 +383,39 @@ __global__ __launch_bounds__(64) void lm_tokens_kernel(const int64_t* __restrict
     if (!ok) atomicAdd(bad, 1ull);
 }
 
-// the stack over N x S rows at position pos0 (h->h embedded from ids_dev), and the head on every sequence's last row
-int lm_run(ace355_lm* h, int N, int S, int pos0, float* logits_dev, hipStream_t s) {
+// the stack over N x S rows at position pos0 (h->h embedded from ids_dev): the final norm of every row -> xn (bf16 [N * S, D])
+int lm_forward(ace355_lm* h, int N, int S, int pos0, hipStream_t s) {
     const EncPassRequest rq = enc_request(*h, h->enc, N, S, false, &h->cache, pos0);
     int rc = ensure_workspace(h, plan_encoder_workspace(&rq, 1, 0, 0), s);
     if (!rc) rc = launch_embed_rows(h->embed, h->ids_dev, h->h, nullptr, (long)N * S, h->D, s);
-    if (!rc) rc = run_encoder_pass(h, h->enc, rq, nullptr, h->xn, s, &h->cache);   // final norm of every row -> xn (bf16 [M, D])
+    if (!rc) rc = run_encoder_pass(h, h->enc, rq, nullptr, h->xn, s, &h->cache);
+    return rc;
+}
+
+// ... and the head on every sequence's last row
+int lm_run(ace355_lm* h, int N, int S, int pos0, float* logits_dev, hipStream_t s) {
+    const int rc = lm_forward(h, N, S, pos0, s);
     if (rc) return rc;
     return launch_lm_head(h->xn + (long)(S - 1) * h->D, (long)S * h->D, h->head, logits_dev, N, h->cfg.vocab_size, h->D, s);
+}
+
+// the refusals ace355_lm_prefill and ace355_lm_score share, made before anything is launched
+int lm_check_prompt(ace355_lm* h, const int32_t* ids_host, const int32_t* first_host, int N, int P, const std::string& who) {
+    if (!h->finalized) { set_error(who + ": call ace355_lm_finalize first"); return ACE355_ERR_STATE; }
+    ACE_CHECK(N > 0 && P > 0, who + ": sizes");
+    if (N > h->cfg.max_seqs)
+        return lm_refuse(who + ": " + std::to_string(N) + " sequences, the handle holds max_seqs = " + std::to_string(h->cfg.max_seqs));
+    if (P > h->cfg.max_positions)
+        return lm_refuse(who + ": " + std::to_string(P) + " positions, the handle holds max_positions = " +
+                         std::to_string(h->cfg.max_positions));
+    if ((long)N * P > ACE355_LM_MAX_TOKENS)
+        return lm_refuse(who + ": N * P = " + std::to_string((long)N * P) + " tokens in one prefill, at most " +
+                         std::to_string(ACE355_LM_MAX_TOKENS));
+    for (int n = 0; n < N; ++n)
+        if (first_host[n] < 0 || first_host[n] >= P)
+            return lm_refuse(who + ": first[" + std::to_string(n) + "] = " + std::to_string(first_host[n]) + " outside [0, " +
+                             std::to_string(P) + ")");
+    return lm_check_ids(h, ids_host, (long)N * P, who.c_str());
 }
 
 }  // namespace
@@ -426,6 +454,7 @@ void ace355_lm_destroy(ace355_lm* h) {
     hipDeviceSynchronize();
     free_encoder(h);
     if (h->ids_dev) hipFree(h->ids_dev);
+    if (h->score_ws) hipFree(h->score_ws);
     delete h;
 }
 
@@ -444,21 +473,7 @@ int ace355_lm_finalize(ace355_lm* h) {
 
 int ace355_lm_prefill(ace355_lm* h, const int32_t* ids_host, const int32_t* first_host, int N, int P, float* logits_dev, void* stream) {
     ACE_CHECK(h && ids_host && first_host && logits_dev, "lm_prefill: null argument");
-    if (!h->finalized) { set_error("lm_prefill: call ace355_lm_finalize first"); return ACE355_ERR_STATE; }
-    ACE_CHECK(N > 0 && P > 0, "lm_prefill: sizes");
-    if (N > h->cfg.max_seqs)
-        return lm_refuse("lm_prefill: " + std::to_string(N) + " sequences, the handle holds max_seqs = " + std::to_string(h->cfg.max_seqs));
-    if (P > h->cfg.max_positions)
-        return lm_refuse("lm_prefill: " + std::to_string(P) + " positions, the handle holds max_positions = " +
-                         std::to_string(h->cfg.max_positions));
-    if ((long)N * P > ACE355_LM_MAX_TOKENS)
-        return lm_refuse("lm_prefill: N * P = " + std::to_string((long)N * P) + " tokens in one prefill, at most " +
-                         std::to_string(ACE355_LM_MAX_TOKENS));
-    for (int n = 0; n < N; ++n)
-        if (first_host[n] < 0 || first_host[n] >= P)
-            return lm_refuse("lm_prefill: first[" + std::to_string(n) + "] = " + std::to_string(first_host[n]) + " outside [0, " +
-                             std::to_string(P) + ")");
-    int rc = lm_check_ids(h, ids_host, (long)N * P, "lm_prefill");
+    int rc = lm_check_prompt(h, ids_host, first_host, N, P, "lm_prefill");
     if (rc) return rc;
     // nothing was refused: from here on the previous generation is gone
     hipStream_t s = (hipStream_t)stream;
@@ -475,6 +490,55 @@ int ace355_lm_prefill(ace355_lm* h, const int32_t* ids_host, const int32_t* firs
     h->n_seqs = N;
     h->length = P;
     return ACE355_OK;
+}
+
+int ace355_lm_score(ace355_lm* h, const int32_t* ids_host, const int32_t* first_host, const int32_t* start_host, int N, int P,
+                    float* logprob_dev, int32_t* rank_dev, void* stream) {
+    ACE_CHECK(h && ids_host && first_host && start_host && logprob_dev && rank_dev, "lm_score: null argument");
+    int rc = lm_check_prompt(h, ids_host, first_host, N, P, "lm_score");
+    if (rc) return rc;
+    long R = 0;
+    for (int n = 0; n < N; ++n) {
+        if (start_host[n] <= first_host[n] || start_host[n] >= P)
+            return lm_refuse("lm_score: start[" + std::to_string(n) + "] = " + std::to_string(start_host[n]) + " outside (first = " +
+                             std::to_string(first_host[n]) + ", " + std::to_string(P) + ")");
+        R += P - start_host[n];
+    }
+    // nothing was refused: from here on the previous generation is gone, and none follows
+    hipStream_t s = (hipStream_t)stream;
+    h->length = 0;
+    h->n_seqs = 0;
+    const int V = h->cfg.vocab_size, D = (int)h->D;
+    // column c of sequence n is predicted by row n * P + c - 1
+    std::vector<int32_t> list((size_t)2 * R);
+    long r = 0;
+    for (int n = 0; n < N; ++n)
+        for (int c = start_host[n]; c < P; ++c, ++r) {
+            list[r] = n * P + c - 1;
+            list[R + r] = ids_host[(long)n * P + c];
+        }
+    const size_t list_bytes = ((size_t)2 * R * sizeof(int32_t) + 255) & ~(size_t)255;
+    const size_t rows_bytes = ace355_lm_score_workspace_bytes((int)R, V);
+    ACE_CHECK(rows_bytes > 0, "lm_score: no scoring plan for this handle's vocabulary / hidden size");
+    if (list_bytes + rows_bytes > h->score_cap) {
+        ACE_HIP(hipStreamSynchronize(s));
+        if (h->score_ws) hipFree(h->score_ws);
+        h->score_ws = nullptr;
+        h->score_cap = 0;
+        ACE_HIP(hipMalloc((void**)&h->score_ws, list_bytes + rows_bytes));
+        h->score_cap = list_bytes + rows_bytes;
+    }
+    rc = lm_ensure_cache(h, s);
+    if (!rc) rc = lm_upload_ids(h, ids_host, (long)N * P, s);
+    if (rc) return rc;
+    ACE_HIP(hipMemcpyAsync(h->first_dev, first_host, sizeof(int) * N, hipMemcpyHostToDevice, s));
+    ACE_HIP(hipMemcpyAsync(h->score_ws, list.data(), (size_t)2 * R * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    ACE_HIP(hipStreamSynchronize(s));   // `first_host` is caller memory, `list` this call's
+    rc = lm_forward(h, N, P, 0, s);
+    if (rc) return rc;
+    const int32_t* rows_dev = (const int32_t*)h->score_ws;
+    return ace355_lm_score_rows(h->xn, D, rows_dev, h->head, rows_dev + R, (int)R, V, D, logprob_dev, rank_dev, h->score_ws + list_bytes,
+                                rows_bytes, stream);
 }
 
 int ace355_lm_fan_out(ace355_lm* h, const int32_t* src_host, int n_new, void* stream) {

@@ -78,4 +78,49 @@ inline LmPickPlan plan_lm_pick(int V) {
     return p;
 }
 
+// ------------------------------------------------------------------------------------------------ teacher-forced scoring (lm_score.hip)
+// R rows of final-norm activations against the head W [V, D]: a workgroup takes LM_SCORE_TILE_ROWS rows and one chunk of ids, walks the
+// chunk in steps of LM_SCORE_STEP_IDS ids with a K loop over D in slices of LM_SCORE_K_SLICE, and leaves one partial per (row, chunk);
+// the merge combines a row's partials in chunk order.  Chunk c holds ids [c * chunk, min(V, (c + 1) * chunk)).  The cut of the
+// vocabulary is a function of V ALONE, and a row's arithmetic does not depend on where in a tile it sits, so a row's bits do not
+// depend on R or on the rows beside it.  One regime: 1024 ids per workgroup - the real vocabulary (217 205) is 213 chunks, which fill
+// the chip from one row tile on.  Row tiles are the fast grid dimension: the workgroups that share a chunk of W run side by side.
+constexpr int LM_SCORE_TILE_ROWS = 64;
+constexpr int LM_SCORE_STEP_IDS = 256;
+constexpr int LM_SCORE_K_SLICE = 64;
+constexpr int LM_SCORE_CHUNK = 1024;
+constexpr int LM_SCORE_MAX_ROWS = 65536;   // ACE355_LM_MAX_TOKENS
+constexpr int LM_SCORE_MAX_V = LM_PICK_MAX_V;
+constexpr int LM_SCORE_MAX_D = 16384;
+constexpr int LM_SCORE_PART_BYTES = 32;    // one (row, chunk) partial: max, sum, two counts, the target's logit, a flag, padding
+static_assert(LM_SCORE_CHUNK % LM_SCORE_STEP_IDS == 0, "a chunk is a whole number of column steps");
+
+struct LmScorePlan {
+    int tile_rows;   // rows per workgroup
+    int chunk;       // ids per workgroup
+    int chunks;      // ceil(V / chunk); 0 for a request outside the limits
+    int grid_x;      // row tiles = ceil(R / tile_rows)
+    int grid_y;      // = chunks
+};
+
+// 0 chunks for R outside 1 .. LM_SCORE_MAX_ROWS, V outside 1 .. LM_SCORE_MAX_V, or D no multiple of LM_SCORE_K_SLICE in (0, LM_SCORE_MAX_D]
+inline LmScorePlan plan_lm_score(int R, int V, int D) {
+    LmScorePlan p{};
+    p.tile_rows = LM_SCORE_TILE_ROWS;
+    p.chunk = LM_SCORE_CHUNK;
+    if (R < 1 || R > LM_SCORE_MAX_ROWS || V < 1 || V > LM_SCORE_MAX_V || D < 1 || D > LM_SCORE_MAX_D || D % LM_SCORE_K_SLICE != 0) return p;
+    p.chunks = (V + p.chunk - 1) / p.chunk;
+    p.grid_x = (R + p.tile_rows - 1) / p.tile_rows;
+    p.grid_y = p.chunks;
+    return p;
+}
+
+// the rows entry's workspace: z fp32 [R] (the counting thresholds), then the partials [R][chunks]; 0 for a request outside the limits
+inline unsigned long long lm_score_align256(unsigned long long n) { return (n + 255) & ~255ull; }
+inline unsigned long long lm_score_workspace_bytes(int R, int V) {
+    const LmScorePlan p = plan_lm_score(R, V, LM_SCORE_K_SLICE);
+    if (p.chunks == 0) return 0;
+    return lm_score_align256((unsigned long long)R * 4) + lm_score_align256((unsigned long long)R * p.chunks * LM_SCORE_PART_BYTES);
+}
+
 }  // namespace ace355

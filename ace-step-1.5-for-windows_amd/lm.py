@@ -13,7 +13,9 @@ positions are the padded column indices and the first visible key of a row is it
 Only the forward is native here.  By default the CFG combine, repetition penalty and the constrained logits processor stay the
 reference's torch code, run on the logits returned here; top-k / top-p and the draw have a native counterpart in ``ace355.lmsample``
 (opt-in at the seam: ``NativeLmMixin.use_native_lm_sampler``), and the rest of the loop body in ``ace355.lmlogits`` (opt-in:
-``NativeLmMixin.use_native_lm_loop``), which drives ``decode_tokens`` below.  It is not an ``nn.Module``: ``modswap.NativeCausalLMSwap`` wraps it and keeps
+``NativeLmMixin.use_native_lm_loop``), which drives ``decode_tokens`` below.  ``score`` is the teacher-forced counterpart for the
+reference's quality score (``ace355.lmscore``; opt-in: ``NativeLmMixin.use_native_lm_score``): the prefill's pass, then per target token one
+log-probability and one rank instead of logits.  It is not an ``nn.Module``: ``modswap.NativeCausalLMSwap`` wraps it and keeps
 the reference module as the fallback.
 """
 from __future__ import annotations
@@ -138,6 +140,45 @@ class NativeCausalLM(native.Owner):
         self._prefill(host, torch.tensor(first, dtype=torch.int32), out)
         self._first = first
         return out
+
+    def score(self, ids, attention_mask=None, start=None):
+        """Teacher-forced scoring (``ace355_lm_score``): for every sequence ``n`` and column ``c`` in ``[start[n], P)`` the log-probability
+        of ``ids[n][c]`` given the columns before it, and its 0-based rank among that position's logits (0: it is the argmax; equal
+        logits are ordered by ascending id).  ``start``: an int or one per sequence, ``first[n] < start[n] < P``.  Returns
+        ``(logprob fp32 [R], rank int32 [R])`` on the device, compact in ``(n, c)`` order.  Refuses what ``prefill`` refuses; it is not a
+        prefill: afterwards the handle holds no generation, a ``decode`` raises and an older ``KvToken`` is stale."""
+        if not isinstance(ids, torch.Tensor):
+            ids = torch.as_tensor(ids)
+        if ids.dim() != 2 or ids.shape[1] == 0 or ids.shape[0] == 0:
+            raise ValueError("ace355: input_ids must be a non-empty [batch, positions]")
+        N, P = ids.shape
+        if attention_mask is None:
+            first = [0] * N
+        else:
+            if tuple(attention_mask.shape) != (N, P):
+                raise NotImplementedError(f"ace355: attention_mask {tuple(attention_mask.shape)} for input_ids {(N, P)}")
+            first = left_pad_first(attention_mask)
+        if N > self.max_seqs or P > self.max_positions or N * P > native.LM_MAX_TOKENS:
+            raise ValueError(f"ace355: an LM prefill of {N} x {P} exceeds the handle ({self.max_seqs} sequences, {self.max_positions} "
+                             f"positions, {native.LM_MAX_TOKENS} tokens)")
+        if start is None:
+            raise ValueError("ace355: LM score needs start (the first scored column of every sequence)")
+        start = [int(start)] * N if isinstance(start, int) else [int(v) for v in start]
+        if len(start) != N or any(not f < s < P for f, s in zip(first, start)):
+            raise ValueError(f"ace355: LM score start {start} must lie in (first, P) = ({first}, {P}) for each of the {N} sequences")
+        host = _host_ids(ids, self.cfg.vocab_size, "input_ids")
+        R = sum(P - s for s in start)
+        logprob = torch.empty(R, device=self.device, dtype=torch.float32)
+        rank = torch.empty(R, device=self.device, dtype=torch.int32)
+        self._generation += 1
+        self._first = None
+        p32 = C.POINTER(C.c_int32)
+        first_t, start_t = torch.tensor(first, dtype=torch.int32), torch.tensor(start, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            native.check(self._lib.ace355_lm_score(self._h, C.cast(host.data_ptr(), p32), C.cast(first_t.data_ptr(), p32),
+                                                   C.cast(start_t.data_ptr(), p32), N, P, native.ptr(logprob), native.ptr(rank),
+                                                   native.current_stream_ptr()), "lm_score")
+        return logprob, rank
 
     def decode(self, next_ids) -> torch.Tensor:
         if not isinstance(next_ids, torch.Tensor):

@@ -394,6 +394,12 @@ SIGNATURES = {
     "ace355_lm_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "ace355_lm_length": (C.c_int, [C.c_void_p]),
     "ace355_lm_decode_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ace355_lm_score_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ace355_lm_score_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ace355_lm_score_plan": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int32)] * 5),
+    "ace355_lm_score": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "ace355_encoder_pass_plan": (C.c_int, [C.POINTER(EncoderPassRequestC), C.POINTER(EncoderStepInfoC), C.c_int, C.POINTER(C.c_int32),
                                            C.POINTER(EncoderPassInfoC)]),
     "ace355_lm_pick_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
@@ -574,6 +580,19 @@ def lm_pick_plan(V: int) -> dict:
     chunk, chunks = C.c_int32(), C.c_int32()
     check(lib().ace355_lm_pick_plan(int(V), C.byref(chunk), C.byref(chunks)), "lm_pick_plan")
     return {"chunk": chunk.value, "chunks": chunks.value}
+
+
+def lm_score_plan(R: int, V: int, D: int) -> dict:
+    """`ace355_lm_score_plan` (include/ace355.h): what the scoring head launches for ``R`` rows against a ``[V, D]`` head - rows per
+    workgroup (``tile_rows``), ids per workgroup (``chunk``, a function of V alone), ``chunks`` and the grid.  No GPU."""
+    o = [C.c_int32() for _ in range(5)]
+    check(lib().ace355_lm_score_plan(int(R), int(V), int(D), *[C.byref(v) for v in o]), "lm_score_plan")
+    return dict(zip(("tile_rows", "chunk", "chunks", "grid_x", "grid_y"), (v.value for v in o)))
+
+
+def lm_score_workspace_bytes(R: int, V: int) -> int:
+    """`ace355_lm_score_workspace_bytes`: bytes `ace355_lm_score_rows` needs for ``R`` rows of ``V`` ids (0: outside the limits)."""
+    return int(lib().ace355_lm_score_workspace_bytes(int(R), int(V)))
 
 
 def audio_in_request(format: str, channels: int, frames: int, o: int, n: int, K: int, width: int) -> AudioInRequestC:

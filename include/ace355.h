@@ -842,6 +842,42 @@ int ace355_lm_length(ace355_lm* h);
  * function of the length alone - no GPU, no handle. */
 int ace355_lm_decode_plan(int length, int32_t* chunk_out, int32_t* splits_out);
 
+/* Teacher-forced scoring (csrc/lm_score.hip; the reference's acestep/core/scoring/lm_score.py needs, per target token, one
+ * log-probability and one rank - not the [T, V] logits it copies to the host).
+ *
+ * ace355_lm_score_rows is handle-free: R rows of bf16 activations against a bf16 head W [V, D] (row stride D), one target id per row.
+ *   row r          = x[row_index[r] * x_row_stride ..] (x[r * x_row_stride ..] when row_index_dev is NULL)
+ *   logit[r][v]    = sum_k row_r[k] * W[v][k], fp32 accumulation on the matrix cores
+ *   logprob_out[r] = logit[r][t_r] - logsumexp_v logit[r][v], clamped to <= 0               (fp32 [R])
+ *   rank_out[r]    = #{v != t_r : logit[r][v] > z_r, or logit[r][v] == z_r and v < t_r}     (int32 [R], 0 = the target is the argmax)
+ * with z_r the target's own logit: equal values are ordered by ascending id, as ace355_lm_pick orders them.  Three launches on
+ * `stream`, no atomics: the same call gives the same bits, and a row's bits do not depend on R or on the other rows.  No logits are
+ * stored; ids >= V are masked and no row of W at or beyond V is read, so V needs no padding.  row_index and targets are device
+ * memory and are NOT checked: row_index must name rows of x; a target outside [0, V) yields log-prob NaN and rank -1.
+ * ACE355_ERR_INVALID before any HIP call for R outside 1 .. ACE355_LM_MAX_TOKENS, V outside 1 .. 1 << 20, D no multiple of 64 or
+ * above 16384, x_row_stride < D or no multiple of 8, a null pointer other than row_index_dev, x / W / workspace not 16-byte
+ * aligned, or a workspace smaller than ace355_lm_score_workspace_bytes(R, V). */
+int ace355_lm_score_rows(const void* x_dev, int64_t x_row_stride, const int32_t* row_index_dev, const void* W_dev,
+                         const int32_t* targets_dev, int R, int V, int D, float* logprob_out, int32_t* rank_out, void* workspace_dev,
+                         size_t workspace_bytes, void* stream);
+/* Bytes of workspace ace355_lm_score_rows needs: the thresholds and one 32-byte partial per (row, chunk).  Pure; 0 for R or V outside
+ * the limits above. */
+size_t ace355_lm_score_workspace_bytes(int R, int V);
+/* What ace355_lm_score_rows launches (csrc/lm_plan.h: plan_lm_score): rows per workgroup, ids per workgroup (a function of V alone),
+ * chunks = ceil(V / chunk), and the fused head's grid (x = row tiles, y = chunks).  Chunk c holds ids [c * chunk, min(V, (c + 1) *
+ * chunk)).  Pure: no GPU, no handle.  ACE355_ERR_INVALID for a request ace355_lm_score_rows would refuse for its sizes. */
+int ace355_lm_score_plan(int R, int V, int D, int32_t* tile_rows_out, int32_t* chunk_out, int32_t* chunks_out, int32_t* grid_x_out,
+                         int32_t* grid_y_out);
+/* Scores the columns [start[n], P) of every sequence of a left-padded batch (ids, first, N, P as for ace355_lm_prefill; start host
+ * int32 [N], first[n] < start[n] < P): the same upload, embedding and stack as a prefill, then ace355_lm_score_rows on the final
+ * norm of the rows that predict those columns (row n * P + c - 1 predicts ids[n][c]) and the handle's head.  Outputs are compact, in
+ * (n, c) order: logprob dev f32 [R], rank dev int32 [R], R = sum_n (P - start[n]).  Refused like ace355_lm_prefill, and for a start
+ * outside (first, P), before anything is launched and with the handle unchanged.  Afterwards the handle holds NO generation
+ * (ace355_lm_length is 0; a decode is refused): scoring is not a prefill.  The scoring workspace belongs to the handle and grows on
+ * demand.  ids, first and start are copied before the call returns. */
+int ace355_lm_score(ace355_lm* h, const int32_t* ids_host, const int32_t* first_host, const int32_t* start_host, int N, int P,
+                    float* logprob_dev, int32_t* rank_dev, void* stream);
+
 /* One pass of the encoder stack behind ace355_cond (two stacks), ace355_detok, ace355_tok, ace355_textenc and ace355_lm as data, in
  * launch order: plan_encoder_pass of csrc/encoder_plan.h, which those handles execute step by step.  One step is one call of a launcher
  * with everything it takes except pointers; buffers appear as roles.  No GPU, no handle. */
