@@ -464,10 +464,10 @@ class NativeTextEncoderMixin:
                 return False
             if getattr(self, "text_encoder", None) is None:
                 raise RuntimeError("no text encoder loaded")
-            from .modswap import swap_in_text_encoder
+            from .modswap import native_of, swap_in_text_encoder
             wrapper = swap_in_text_encoder(self, self.device)
             self.use_native_text_encoder = True
-            cfg = object.__getattribute__(wrapper, "_native").cfg
+            cfg = native_of(wrapper).cfg
             logger.info("[native-text-encoder] packed for gfx950 (%d layers, hidden %d)", cfg.num_hidden_layers, cfg.hidden_size)
             return True
         except Exception as exc:
@@ -497,7 +497,7 @@ class NativeLmMixin:
             from . import modswap
             wrapper = modswap.swap_in_lm(self, self.device, max_positions=int(getattr(self, "native_lm_max_positions", 8192)))
             self.use_native_lm = True
-            cfg = object.__getattribute__(wrapper, "_native").cfg
+            cfg = modswap.native_of(wrapper).cfg
             logger.info("[native-lm] packed for gfx950 (%d layers, hidden %d, vocabulary %d)", cfg.num_hidden_layers, cfg.hidden_size,
                         cfg.vocab_size)
             return True
@@ -596,9 +596,7 @@ class NativeLmMixin:
         if not isinstance(batch_input_ids, torch.Tensor) or not batch_input_ids.is_cuda or batch_input_ids.dim() != 2:
             return None, "the input ids are not a [2B, P] tensor on a CUDA device"
         from . import lm as _lm, modswap, native
-        llm = getattr(self, "llm", None)
-        if isinstance(llm, modswap.NativeCausalLMSwap):
-            llm = object.__getattribute__(llm, "_native")
+        llm = modswap.native_of(getattr(self, "llm", None))
         if not isinstance(llm, _lm.NativeCausalLM):
             return None, "self.llm is not the native LM (see _init_native_lm)"
         if batch_input_ids.device != llm.device:

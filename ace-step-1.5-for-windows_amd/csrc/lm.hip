@@ -418,6 +418,37 @@ int lm_check_prompt(ace355_lm* h, const int32_t* ids_host, const int32_t* first_
     return lm_check_ids(h, ids_host, (long)N * P, who.c_str());
 }
 
+// ... and what both do once nothing was refused: the previous generation is gone, the cache exists, the ids, `first` and, if any,
+// `extra_bytes` of the call's own are on the device, and the stream is synchronised (`first_host` is caller memory)
+int lm_begin_prompt(ace355_lm* h, const int32_t* ids_host, const int32_t* first_host, int N, int P, void* extra_dev,
+                    const void* extra_host, size_t extra_bytes, hipStream_t s) {
+    h->length = 0;
+    h->n_seqs = 0;
+    int rc = lm_ensure_cache(h, s);
+    if (!rc) rc = lm_upload_ids(h, ids_host, (long)N * P, s);
+    if (rc) return rc;
+    ACE_HIP(hipMemcpyAsync(h->first_dev, first_host, sizeof(int) * N, hipMemcpyHostToDevice, s));
+    if (extra_bytes) ACE_HIP(hipMemcpyAsync(extra_dev, extra_host, extra_bytes, hipMemcpyHostToDevice, s));
+    ACE_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// the refusals ace355_lm_decode and ace355_lm_decode_tokens share
+int lm_check_step(const ace355_lm* h, const std::string& who) {
+    if (h->length <= 0 || h->n_seqs <= 0) return lm_refuse(who + ": no prefill to continue from");
+    if (h->length >= h->cfg.max_positions)
+        return lm_refuse(who + ": the cache is full (length " + std::to_string(h->length) + " = max_positions)");
+    return 0;
+}
+
+// ... and their step, once ids_dev holds the step's ids (`rc`: how getting them there went)
+int lm_step(ace355_lm* h, int rc, float* logits_dev, hipStream_t s) {
+    if (!rc) rc = lm_run(h, h->n_seqs, 1, h->length, logits_dev, s);
+    if (rc) { h->length = 0; h->n_seqs = 0; return rc; }   // a failed launch: the cache is not trustworthy
+    h->length += 1;
+    return ACE355_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -477,14 +508,8 @@ int ace355_lm_prefill(ace355_lm* h, const int32_t* ids_host, const int32_t* firs
     if (rc) return rc;
     // nothing was refused: from here on the previous generation is gone
     hipStream_t s = (hipStream_t)stream;
-    h->length = 0;
-    h->n_seqs = 0;
-    rc = lm_ensure_cache(h, s);
-    if (!rc) rc = lm_upload_ids(h, ids_host, (long)N * P, s);
-    if (rc) return rc;
-    ACE_HIP(hipMemcpyAsync(h->first_dev, first_host, sizeof(int) * N, hipMemcpyHostToDevice, s));
-    ACE_HIP(hipStreamSynchronize(s));   // `first_host` is caller memory
-    rc = lm_run(h, N, P, 0, logits_dev, s);
+    rc = lm_begin_prompt(h, ids_host, first_host, N, P, nullptr, nullptr, 0, s);
+    if (!rc) rc = lm_run(h, N, P, 0, logits_dev, s);
     if (rc) return rc;
     for (int n = 0; n < N; ++n) h->first_host[n] = first_host[n];
     h->n_seqs = N;
@@ -504,10 +529,7 @@ int ace355_lm_score(ace355_lm* h, const int32_t* ids_host, const int32_t* first_
                              std::to_string(first_host[n]) + ", " + std::to_string(P) + ")");
         R += P - start_host[n];
     }
-    // nothing was refused: from here on the previous generation is gone, and none follows
     hipStream_t s = (hipStream_t)stream;
-    h->length = 0;
-    h->n_seqs = 0;
     const int V = h->cfg.vocab_size, D = (int)h->D;
     // column c of sequence n is predicted by row n * P + c - 1
     std::vector<int32_t> list((size_t)2 * R);
@@ -528,13 +550,9 @@ int ace355_lm_score(ace355_lm* h, const int32_t* ids_host, const int32_t* first_
         ACE_HIP(hipMalloc((void**)&h->score_ws, list_bytes + rows_bytes));
         h->score_cap = list_bytes + rows_bytes;
     }
-    rc = lm_ensure_cache(h, s);
-    if (!rc) rc = lm_upload_ids(h, ids_host, (long)N * P, s);
-    if (rc) return rc;
-    ACE_HIP(hipMemcpyAsync(h->first_dev, first_host, sizeof(int) * N, hipMemcpyHostToDevice, s));
-    ACE_HIP(hipMemcpyAsync(h->score_ws, list.data(), (size_t)2 * R * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    ACE_HIP(hipStreamSynchronize(s));   // `first_host` is caller memory, `list` this call's
-    rc = lm_forward(h, N, P, 0, s);
+    // nothing was refused: from here on the previous generation is gone, and none follows (`list` is on the device when this returns)
+    rc = lm_begin_prompt(h, ids_host, first_host, N, P, h->score_ws, list.data(), (size_t)2 * R * sizeof(int32_t), s);
+    if (!rc) rc = lm_forward(h, N, P, 0, s);
     if (rc) return rc;
     const int32_t* rows_dev = (const int32_t*)h->score_ws;
     return ace355_lm_score_rows(h->xn, D, rows_dev, h->head, rows_dev + R, (int)R, V, D, logprob_dev, rank_dev, h->score_ws + list_bytes,
@@ -592,24 +610,17 @@ int ace355_lm_fan_out_plan(const int32_t* src, int n_new, int n_old, int32_t* wa
 
 int ace355_lm_decode(ace355_lm* h, const int32_t* ids_host, float* logits_dev, void* stream) {
     ACE_CHECK(h && ids_host && logits_dev, "lm_decode: null argument");
-    if (h->length <= 0 || h->n_seqs <= 0) return lm_refuse("lm_decode: no prefill to continue from");
-    if (h->length >= h->cfg.max_positions)
-        return lm_refuse("lm_decode: the cache is full (length " + std::to_string(h->length) + " = max_positions)");
-    int rc = lm_check_ids(h, ids_host, h->n_seqs, "lm_decode");
+    int rc = lm_check_step(h, "lm_decode");
+    if (!rc) rc = lm_check_ids(h, ids_host, h->n_seqs, "lm_decode");
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    rc = lm_upload_ids(h, ids_host, h->n_seqs, s);
-    if (!rc) rc = lm_run(h, h->n_seqs, 1, h->length, logits_dev, s);
-    if (rc) { h->length = 0; h->n_seqs = 0; return rc; }   // a failed launch: the cache is not trustworthy
-    h->length += 1;
-    return ACE355_OK;
+    return lm_step(h, lm_upload_ids(h, ids_host, h->n_seqs, s), logits_dev, s);
 }
 
 int ace355_lm_decode_tokens(ace355_lm* h, const int64_t* tokens_dev, int B, float* logits_dev, void* stream) {
     ACE_CHECK(h && tokens_dev && logits_dev, "lm_decode_tokens: null argument");
-    if (h->length <= 0 || h->n_seqs <= 0) return lm_refuse("lm_decode_tokens: no prefill to continue from");
-    if (h->length >= h->cfg.max_positions)
-        return lm_refuse("lm_decode_tokens: the cache is full (length " + std::to_string(h->length) + " = max_positions)");
+    const int refused = lm_check_step(h, "lm_decode_tokens");
+    if (refused) return refused;
     if (B < 1 || h->n_seqs % B != 0)
         return lm_refuse("lm_decode_tokens: B = " + std::to_string(B) + " tokens for " + std::to_string(h->n_seqs) +
                          " sequences (n_seqs must be a multiple of B)");
@@ -619,10 +630,7 @@ int ace355_lm_decode_tokens(ace355_lm* h, const int64_t* tokens_dev, int B, floa
     h->tokens_stream = s;
     hipLaunchKernelGGL(lm_tokens_kernel, dim3(1), dim3(64), 0, s, tokens_dev, B, h->n_seqs, h->cfg.vocab_size, h->ids_dev, h->bad_dev);
     ACE_LAUNCH_CHECK();   // (nothing of the cache has been touched yet: the handle stays as it was)
-    int rc = lm_run(h, h->n_seqs, 1, h->length, logits_dev, s);
-    if (rc) { h->length = 0; h->n_seqs = 0; return rc; }   // a failed launch: the cache is not trustworthy
-    h->length += 1;
-    return ACE355_OK;
+    return lm_step(h, 0, logits_dev, s);
 }
 
 int64_t ace355_lm_bad_tokens(ace355_lm* h) {

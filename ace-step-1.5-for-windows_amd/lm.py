@@ -118,7 +118,8 @@ class NativeCausalLM(native.Owner):
         return self._length()
 
     # ------------------------------------------------------------------ the two steps: fp32 [N, V] logits of the last column
-    def prefill(self, ids, attention_mask=None) -> torch.Tensor:
+    def _prompt(self, ids, attention_mask):
+        """What ``prefill`` and ``score`` check alike: ``(ids as a [N, P] tensor, first)`` for a prompt the handle can take."""
         if not isinstance(ids, torch.Tensor):
             ids = torch.as_tensor(ids)
         if ids.dim() != 2 or ids.shape[1] == 0 or ids.shape[0] == 0:
@@ -133,6 +134,19 @@ class NativeCausalLM(native.Owner):
         if N > self.max_seqs or P > self.max_positions or N * P > native.LM_MAX_TOKENS:
             raise ValueError(f"ace355: an LM prefill of {N} x {P} exceeds the handle ({self.max_seqs} sequences, {self.max_positions} "
                              f"positions, {native.LM_MAX_TOKENS} tokens)")
+        return ids, first
+
+    def _decode_seqs(self) -> int:
+        """The state ``decode`` and ``decode_tokens`` need: a prefill to continue from and room for one more position.  Returns N."""
+        if self._first is None:
+            raise ValueError("ace355: LM decode without a prefill")
+        if self.length >= self.max_positions:
+            raise ValueError(f"ace355: the LM cache is full ({self.max_positions} positions)")
+        return len(self._first)
+
+    def prefill(self, ids, attention_mask=None) -> torch.Tensor:
+        ids, first = self._prompt(ids, attention_mask)
+        N = ids.shape[0]
         host = _host_ids(ids, self.cfg.vocab_size, "input_ids")
         out = torch.empty(N, self.cfg.vocab_size, device=self.device, dtype=torch.float32)
         self._generation += 1
@@ -147,20 +161,8 @@ class NativeCausalLM(native.Owner):
         logits are ordered by ascending id).  ``start``: an int or one per sequence, ``first[n] < start[n] < P``.  Returns
         ``(logprob fp32 [R], rank int32 [R])`` on the device, compact in ``(n, c)`` order.  Refuses what ``prefill`` refuses; it is not a
         prefill: afterwards the handle holds no generation, a ``decode`` raises and an older ``KvToken`` is stale."""
-        if not isinstance(ids, torch.Tensor):
-            ids = torch.as_tensor(ids)
-        if ids.dim() != 2 or ids.shape[1] == 0 or ids.shape[0] == 0:
-            raise ValueError("ace355: input_ids must be a non-empty [batch, positions]")
+        ids, first = self._prompt(ids, attention_mask)
         N, P = ids.shape
-        if attention_mask is None:
-            first = [0] * N
-        else:
-            if tuple(attention_mask.shape) != (N, P):
-                raise NotImplementedError(f"ace355: attention_mask {tuple(attention_mask.shape)} for input_ids {(N, P)}")
-            first = left_pad_first(attention_mask)
-        if N > self.max_seqs or P > self.max_positions or N * P > native.LM_MAX_TOKENS:
-            raise ValueError(f"ace355: an LM prefill of {N} x {P} exceeds the handle ({self.max_seqs} sequences, {self.max_positions} "
-                             f"positions, {native.LM_MAX_TOKENS} tokens)")
         if start is None:
             raise ValueError("ace355: LM score needs start (the first scored column of every sequence)")
         start = [int(start)] * N if isinstance(start, int) else [int(v) for v in start]
@@ -183,13 +185,9 @@ class NativeCausalLM(native.Owner):
     def decode(self, next_ids) -> torch.Tensor:
         if not isinstance(next_ids, torch.Tensor):
             next_ids = torch.as_tensor(next_ids)
-        if self._first is None:
-            raise ValueError("ace355: LM decode without a prefill")
-        N = len(self._first)
+        N = self._decode_seqs()
         if next_ids.numel() != N or next_ids.dim() > 2 or (next_ids.dim() == 2 and next_ids.shape[1] != 1):
             raise ValueError(f"ace355: LM decode takes one token for each of the {N} sequences")
-        if self.length >= self.max_positions:
-            raise ValueError(f"ace355: the LM cache is full ({self.max_positions} positions)")
         host = _host_ids(next_ids.reshape(-1), self.cfg.vocab_size, "input_ids")
         out = torch.empty(N, self.cfg.vocab_size, device=self.device, dtype=torch.float32)
         self._generation += 1
@@ -200,16 +198,12 @@ class NativeCausalLM(native.Owner):
         """``decode`` for ids that stay on the GPU: ``tokens`` int64 ``[B]`` on this device, ``N % B == 0``, sequence ``n`` takes
         ``tokens[n % B]`` (the CFG loop's ``next_tokens.repeat(2, 1)``).  Nothing is read back and the stream is not synchronised; an id
         outside the vocabulary is embedded as id 0 and counted (``bad_tokens``)."""
-        if self._first is None:
-            raise ValueError("ace355: LM decode without a prefill")
-        N = len(self._first)
+        N = self._decode_seqs()
         if not isinstance(tokens, torch.Tensor) or tokens.dtype != torch.int64 or tokens.device != self.device or tokens.dim() != 1:
             raise ValueError(f"ace355: decode_tokens takes an int64 [B] tensor on {self.device}")
         B = tokens.shape[0]
         if B < 1 or N % B != 0:
             raise ValueError(f"ace355: {B} tokens for {N} sequences (N must be a multiple of B)")
-        if self.length >= self.max_positions:
-            raise ValueError(f"ace355: the LM cache is full ({self.max_positions} positions)")
         if not tokens.is_contiguous():
             tokens = tokens.contiguous()
         out = torch.empty(N, self.cfg.vocab_size, device=self.device, dtype=torch.float32)

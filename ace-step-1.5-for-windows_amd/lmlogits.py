@@ -10,7 +10,8 @@ transformers' ``RepetitionPenaltyLogitsProcessor``; then ``_update_constrained_p
 * ``step_plan`` decides, from the processor's attributes alone, what one step of the loop is;
 * ``generate_with_cfg`` is the loop (``NativeLmMixin._generate_with_cfg_custom`` calls it when ``use_native_lm_loop`` is set);
 * ``generate_codes_batch`` is that loop for B songs that share one prompt, each with the tokens the loop gives it alone, and
-  ``batch_request`` decides which ``_run_pt`` calls are such batches (``NativeLmMixin._run_pt``, ``use_native_lm_batch``).
+  ``batch_request`` decides which ``_run_pt`` calls are such batches (``NativeLmMixin._run_pt``, ``use_native_lm_batch``);
+* ``_cfg_loop`` is the one loop behind both: each of the two builds a ``_LoopMode`` and formats what the loop returns.
 
 The native stage covers the processor's branches that are a fixed mask plus one EOS rule: no processor, a disabled one, ``COMPLETED``
 and ``CODES_GENERATION``.  Every other FSM state runs the reference's own torch code on the native forward's logits, as before.
@@ -164,68 +165,96 @@ def _codes_mask(processor, name: str, device) -> Optional[torch.Tensor]:
     return m if m.dim() == 1 and m.is_contiguous() else m.reshape(-1).contiguous()
 
 
-def generate_with_cfg(handler, lm, batch_input_ids: torch.Tensor, batch_attention_mask: Optional[torch.Tensor], max_new_tokens: int,
-                      temperature: float, cfg_scale: float, top_k: Optional[int], top_p: Optional[float], repetition_penalty: float,
-                      pad_token_id: int, streamer, constrained_processor=None) -> torch.Tensor:
-    """``LLMHandler._generate_with_cfg_custom`` on ``lm`` (a ``NativeCausalLM``): same arguments, same return (``[2B, P + steps]``,
-    conditional rows first), same streamer calls, the processor left as the reference's loop leaves it.  The draw is the native
-    selection's (``lmsample``: one ``torch.rand(B)`` per step), not ``torch.multinomial``'s.  ``handler`` supplies ``llm_tokenizer`` and
-    ``_build_logits_processor`` (the latter only on a reference step).  Leaves ``handler._lm_loop_stats``."""
+class _LoopMode(NamedTuple):
+    """Which loop ``_cfg_loop`` runs.  ``seeds`` None: ``generate_with_cfg``, the rows of the ids are B conditional + B unconditional
+    prompts and the global generator draws.  ``seeds`` a list: ``generate_codes_batch``, the ids are one ``[2, P]`` pair for
+    ``B = len(seeds)`` songs, row i draws from a generator of its own seeded ``seeds[i]``, and there is no streamer."""
+    B: int                  # token rows
+    seeds: Optional[list]
+    streamer: Any
+
+
+def _cfg_loop(handler, lm, ids: torch.Tensor, attention_mask: Optional[torch.Tensor], mode: _LoopMode, max_new_tokens: int,
+              temperature: float, cfg_scale: float, top_k: Optional[int], top_p: Optional[float], repetition_penalty: float,
+              pad_token_id: int, proc) -> torch.Tensor:
+    """The CFG loop behind ``generate_with_cfg`` and ``generate_codes_batch``: int64 ``[steps, B]``, row t the tokens of step t.
+    Leaves ``handler._lm_loop_stats``; raises when some step could draw no token."""
     from . import lmsample
-    ids = batch_input_ids
+    B, streamer, batched = mode.B, mode.streamer, mode.seeds is not None
     dev = ids.device
-    B = ids.shape[0] // 2
+    n0 = 1 if batched else B   # conditional rows of the prompt, and of step 0's logits
     V = lm.cfg.vocab_size
     eos = handler.llm_tokenizer.eos_token_id
     if eos is None:
         eos = pad_token_id
-    proc = constrained_processor
     penalty = float(repetition_penalty)
     sample = temperature > 0
     stats = {"steps": 0, "native_steps": 0, "sync_free_steps": 0, "token_reads": 0}
+    if batched:
+        stats.update(batch=B, prefill_rows=2)
     handler._lm_loop_stats = stats
     tokens = torch.empty(max(int(max_new_tokens), 1), B, dtype=torch.int64, device=dev)   # row t: the tokens of step t
-    seen = SeenTokens(B, V, dev).mark(ids[:B].to(torch.int64)) if penalty != 1.0 else None   # the conditional rows, pads included
+    # the conditional rows, pads included; batched: every song's is the pair's
+    seen = SeenTokens(B, V, dev).mark(ids[:n0].to(torch.int64).expand(B, ids.shape[1])) if penalty != 1.0 else None
+    gens = [torch.Generator(device=dev).manual_seed(s) for s in mode.seeds] if batched and sample else []
+    u = torch.empty(B, dtype=torch.float32, device=dev) if gens else None
+    stop_ids = {eos} | ({pad_token_id} if pad_token_id is not None else set())
     blocked, blocked_for = None, None
     steps, bad_draw = 0, False
     lm.bad_tokens()   # whatever an earlier user of the handle left uncounted is not this call's
 
     with torch.inference_mode():
         for step in range(int(max_new_tokens)):
-            logits = lm.prefill(ids, batch_attention_mask) if step == 0 else lm.decode_tokens(tokens[step - 1])
+            logits = lm.prefill(ids, attention_mask) if step == 0 else lm.decode_tokens(tokens[step - 1])
             if lm.out_dtype != torch.float32:
                 logits = logits.to(lm.out_dtype).float()   # the model's own output dtype, upcast as llm_inference.py:2482 does
-            cond, uncond = logits[:B], logits[B:]
+            n = n0 if step == 0 else B
+            cond, uncond = logits[:n], logits[n:]
             if proc is not None and proc.enabled and _state_name(proc.state) == "CODES_GENERATION" and proc.non_audio_code_mask is not None:
                 m = _codes_mask(proc, "non_audio_code_mask", dev)
                 if blocked_for is not proc.non_audio_code_mask:   # once per call: which of the loop's stop ids the mask rules out
-                    stop_ids = [t for t in {eos, pad_token_id} if t is not None and 0 <= t < m.shape[0]]
-                    vals = m[torch.tensor(stop_ids, dtype=torch.int64, device=dev)].tolist() if stop_ids else []
-                    blocked = frozenset(t for t, v in zip(stop_ids, vals) if v == NEG_INF)
+                    known = [t for t in stop_ids if 0 <= t < m.shape[0]]
+                    vals = m[torch.tensor(known, dtype=torch.int64, device=dev)].tolist() if known else []
+                    blocked = frozenset(t for t, v in zip(known, vals) if v == NEG_INF)
                     blocked_for = proc.non_audio_code_mask
             plan = step_plan(StepView(proc, eos, pad_token_id, streamer is not None, blocked))
             if plan.native:
+                if n != B:   # one staged row per song: the penalty's bitmap and the selection have B rows
+                    cond, uncond = cond.repeat(B, 1), uncond.repeat(B, 1)
                 mask = None
                 if plan.mask is not None:
                     mask = _codes_mask(proc, "audio_code_mask" if _state_name(proc.state) == "COMPLETED" else "non_audio_code_mask", dev)
                 x = shape_logits(cond, uncond, cfg_scale, mask, proc.eos_token_id if plan.eos_mode else None, plan.eos_mode,
                                  plan.temperature, penalty, seen, out=cond)
-                u = torch.rand(B, device=dev) if sample else None
-                toks = lmsample.pick(x, top_k, top_p, temperature, u)[0]
                 stats["native_steps"] += 1
-            else:
-                cur = torch.cat([ids[:B], tokens[:step].t().to(ids.dtype)], dim=1)
+            else:   # the reference's processor (THINK_TAG -> CODES_GENERATION is made in its __call__)
+                if batched and step != 0:
+                    raise RuntimeError(f"ace355: the constrained processor left the codes phase at step {step} of a batched loop "
+                                       f"(state {_state_name(proc.state)})")
+                cur = ids[:1] if batched else torch.cat([ids[:B], tokens[:step].t().to(ids.dtype)], dim=1)
                 x = uncond + cfg_scale * (cond - uncond)
                 x = proc(cur, x)
                 for lp in handler._build_logits_processor(repetition_penalty):
                     x = lp(cur, x)
+                if batched:
+                    x = x.repeat(B, 1)
+            if batched:   # row i's own stream of uniforms: one torch.rand(1) per step, as the B = 1 loop draws
+                for i, g in enumerate(gens):
+                    torch.rand(1, generator=g, out=u[i:i + 1])
+            elif plan.native and sample:
+                u = torch.rand(B, device=dev)
+            if plan.native or batched:
+                toks = lmsample.pick(x, top_k, top_p, temperature, u)[0]
+            else:
                 toks = lmsample.select_tokens(x, top_k, top_p, temperature, check=False)
             tokens[step] = toks
             steps = step + 1
             if seen is not None:
                 seen.mark(tokens[step])
+            if batched and step == 0:
+                lm.fan_out([0] * B + [1] * B)
             if plan.native and plan.sync_free:
-                for _ in range(B):
+                for _ in range(1 if batched else B):   # batched: once per step, codes per song
                     proc.update_state(0)   # CODES_GENERATION only counts (update_state :2153-2158): the value is not looked at
                 stats["sync_free_steps"] += 1
                 continue
@@ -234,12 +263,21 @@ def generate_with_cfg(handler, lm, batch_input_ids: torch.Tensor, batch_attentio
             if min(host) < 0:
                 bad_draw = True
                 break
-            if proc is not None:
+            if batched:
+                proc.update_state(host[0])
+                if _state_name(proc.state) != "CODES_GENERATION":
+                    raise RuntimeError(f"ace355: the constrained processor is in state {_state_name(proc.state)} after step {step} of a "
+                                       f"batched loop; only the codes phase runs batched")
+            elif proc is not None:
                 for t in host:
                     proc.update_state(t)
             if streamer is not None:
                 streamer.put(toks.unsqueeze(1))
-            if eos in host or (pad_token_id is not None and pad_token_id != eos and pad_token_id in host):
+            stopped = [t in stop_ids for t in host]
+            if batched and any(stopped) and not all(stopped):
+                raise RuntimeError(f"ace355: songs {[i for i, s in enumerate(stopped) if s]} of {B} stopped at step {step} and the "
+                                   f"others did not; the batched LM loop returns no ragged rows")
+            if any(stopped):
                 break
     stats["steps"] = steps
     if streamer is not None:
@@ -250,7 +288,20 @@ def generate_with_cfg(handler, lm, batch_input_ids: torch.Tensor, batch_attentio
     if bad_draw or replaced:
         raise RuntimeError(f"ace355: the native LM loop drew no valid token at some step (a logits row with a NaN, a +inf or no finite "
                            f"entry; {replaced} ids replaced in the forward); the constrained processor has advanced {steps} steps")
-    return torch.cat([ids, tokens[:steps].t().repeat(2, 1).to(ids.dtype)], dim=1)
+    return tokens[:steps]
+
+
+def generate_with_cfg(handler, lm, batch_input_ids: torch.Tensor, batch_attention_mask: Optional[torch.Tensor], max_new_tokens: int,
+                      temperature: float, cfg_scale: float, top_k: Optional[int], top_p: Optional[float], repetition_penalty: float,
+                      pad_token_id: int, streamer, constrained_processor=None) -> torch.Tensor:
+    """``LLMHandler._generate_with_cfg_custom`` on ``lm`` (a ``NativeCausalLM``): same arguments, same return (``[2B, P + steps]``,
+    conditional rows first), same streamer calls, the processor left as the reference's loop leaves it.  The draw is the native
+    selection's (``lmsample``: one ``torch.rand(B)`` per step), not ``torch.multinomial``'s.  ``handler`` supplies ``llm_tokenizer`` and
+    ``_build_logits_processor`` (the latter only on a reference step).  Leaves ``handler._lm_loop_stats``."""
+    ids = batch_input_ids
+    tokens = _cfg_loop(handler, lm, ids, batch_attention_mask, _LoopMode(ids.shape[0] // 2, None, streamer), max_new_tokens, temperature,
+                       cfg_scale, top_k, top_p, repetition_penalty, pad_token_id, constrained_processor)
+    return torch.cat([ids, tokens.t().repeat(2, 1).to(ids.dtype)], dim=1)
 
 
 # ---------------------------------------------------------------------------------------------------------------- B songs, one loop
@@ -294,7 +345,6 @@ def generate_codes_batch(handler, lm, pair_ids: torch.Tensor, pair_mask: Optiona
     per step (codes per song) and is left as the last sequential item would leave it.  Needs an enabled processor with
     ``target_codes`` and ``eos_token_id``: EOS is blocked until the count is reached and then forced, so every row stops at the same
     step; a step that finds only some rows stopped raises.  Leaves ``handler._lm_loop_stats`` (plus ``batch``, ``prefill_rows``)."""
-    from . import lmsample
     proc = constrained_processor
     if proc is None or not proc.enabled or proc.target_codes is None or proc.eos_token_id is None:
         raise RuntimeError("ace355: the batched LM loop needs an enabled constrained processor with target_codes and eos_token_id "
@@ -305,94 +355,6 @@ def generate_codes_batch(handler, lm, pair_ids: torch.Tensor, pair_mask: Optiona
         raise ValueError("ace355: the batched LM loop takes the [2, P] pair of conditional and unconditional ids")
     if not 1 <= B or 2 * B > lm.max_seqs:
         raise ValueError(f"ace355: {B} songs need {2 * B} sequences, the native LM holds {lm.max_seqs}")
-    ids = pair_ids
-    dev = ids.device
-    P = ids.shape[1]
-    V = lm.cfg.vocab_size
-    eos = handler.llm_tokenizer.eos_token_id
-    if eos is None:
-        eos = pad_token_id
-    penalty = float(repetition_penalty)
-    sample = temperature > 0
-    stats = {"steps": 0, "native_steps": 0, "sync_free_steps": 0, "token_reads": 0, "batch": B, "prefill_rows": 2}
-    handler._lm_loop_stats = stats
-    tokens = torch.empty(max(int(max_new_tokens), 1), B, dtype=torch.int64, device=dev)   # row t: the tokens of step t
-    prompt = ids[:1].to(torch.int64).expand(B, P)                                         # every song's conditional row
-    seen = SeenTokens(B, V, dev).mark(prompt) if penalty != 1.0 else None
-    gens = [torch.Generator(device=dev).manual_seed(s) for s in seeds] if sample else []
-    u = torch.empty(B, dtype=torch.float32, device=dev) if sample else None
-    stop_ids = {eos} | ({pad_token_id} if pad_token_id is not None else set())
-    blocked, blocked_for = None, None
-    steps, bad_draw = 0, False
-    lm.bad_tokens()   # whatever an earlier user of the handle left uncounted is not this call's
-
-    with torch.inference_mode():
-        for step in range(int(max_new_tokens)):
-            logits = lm.prefill(ids, pair_mask) if step == 0 else lm.decode_tokens(tokens[step - 1])
-            if lm.out_dtype != torch.float32:
-                logits = logits.to(lm.out_dtype).float()   # the model's own output dtype, upcast as llm_inference.py:2482 does
-            n = 1 if step == 0 else B
-            cond, uncond = logits[:n], logits[n:]
-            if _state_name(proc.state) == "CODES_GENERATION" and proc.non_audio_code_mask is not None:
-                m = _codes_mask(proc, "non_audio_code_mask", dev)
-                if blocked_for is not proc.non_audio_code_mask:   # once per call: which of the loop's stop ids the mask rules out
-                    known = [t for t in stop_ids if 0 <= t < m.shape[0]]
-                    vals = m[torch.tensor(known, dtype=torch.int64, device=dev)].tolist() if known else []
-                    blocked = frozenset(t for t, v in zip(known, vals) if v == NEG_INF)
-                    blocked_for = proc.non_audio_code_mask
-            plan = step_plan(StepView(proc, eos, pad_token_id, False, blocked))
-            if plan.native:
-                if step == 0:   # one staged row per song: the penalty's bitmap and the selection have B rows
-                    cond, uncond = cond.repeat(B, 1), uncond.repeat(B, 1)
-                mask = None
-                if plan.mask is not None:
-                    mask = _codes_mask(proc, "audio_code_mask" if _state_name(proc.state) == "COMPLETED" else "non_audio_code_mask", dev)
-                x = shape_logits(cond, uncond, cfg_scale, mask, proc.eos_token_id if plan.eos_mode else None, plan.eos_mode,
-                                 plan.temperature, penalty, seen, out=cond)
-                stats["native_steps"] += 1
-            else:   # the reference's processor on the pair's row (THINK_TAG -> CODES_GENERATION is made in its __call__)
-                if step != 0:
-                    raise RuntimeError(f"ace355: the constrained processor left the codes phase at step {step} of a batched loop "
-                                       f"(state {_state_name(proc.state)})")
-                cur = ids[:1]
-                x = uncond + cfg_scale * (cond - uncond)
-                x = proc(cur, x)
-                for lp in handler._build_logits_processor(repetition_penalty):
-                    x = lp(cur, x)
-                x = x.repeat(B, 1)
-            for i, g in enumerate(gens):   # row i's own stream of uniforms: one torch.rand(1) per step, as the B = 1 loop draws
-                torch.rand(1, generator=g, out=u[i:i + 1])
-            toks = lmsample.pick(x, top_k, top_p, temperature, u)[0]
-            tokens[step] = toks
-            steps = step + 1
-            if seen is not None:
-                seen.mark(tokens[step])
-            if step == 0:
-                lm.fan_out([0] * B + [1] * B)
-            if plan.native and plan.sync_free:
-                proc.update_state(0)   # CODES_GENERATION only counts (update_state :2153-2158), once per step: codes per song
-                stats["sync_free_steps"] += 1
-                continue
-            host = toks.tolist()
-            stats["token_reads"] += 1
-            if min(host) < 0:
-                bad_draw = True
-                break
-            proc.update_state(host[0])
-            if _state_name(proc.state) != "CODES_GENERATION":
-                raise RuntimeError(f"ace355: the constrained processor is in state {_state_name(proc.state)} after step {step} of a "
-                                   f"batched loop; only the codes phase runs batched")
-            stopped = [t in stop_ids for t in host]
-            if any(stopped) and not all(stopped):
-                raise RuntimeError(f"ace355: songs {[i for i, s in enumerate(stopped) if s]} of {B} stopped at step {step} and the "
-                                   f"others did not; the batched LM loop returns no ragged rows")
-            if all(stopped):
-                break
-    stats["steps"] = steps
-    replaced = lm.bad_tokens() if steps > 1 else 0
-    if not bad_draw and steps:
-        bad_draw = bool((tokens[:steps] < 0).any())
-    if bad_draw or replaced:
-        raise RuntimeError(f"ace355: the native LM loop drew no valid token at some step (a logits row with a NaN, a +inf or no finite "
-                           f"entry; {replaced} ids replaced in the forward); the constrained processor has advanced {steps} steps")
-    return torch.cat([prompt, tokens[:steps].t()], dim=1)
+    tokens = _cfg_loop(handler, lm, pair_ids, pair_mask, _LoopMode(B, seeds, None), max_new_tokens, temperature, cfg_scale, top_k, top_p,
+                       repetition_penalty, pad_token_id, proc)
+    return torch.cat([pair_ids[:1].to(torch.int64).expand(B, pair_ids.shape[1]), tokens.t()], dim=1)

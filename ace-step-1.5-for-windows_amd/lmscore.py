@@ -50,10 +50,8 @@ def native_lm(llm_handler):
     if getattr(llm_handler, "llm_backend", "pt") != "pt":
         return None
     from .lm import NativeCausalLM
-    from .modswap import NativeCausalLMSwap
-    llm = getattr(llm_handler, "llm", None)
-    if isinstance(llm, NativeCausalLMSwap):
-        llm = object.__getattribute__(llm, "_native")
+    from .modswap import native_of
+    llm = native_of(getattr(llm_handler, "llm", None))
     return llm if isinstance(llm, NativeCausalLM) else None
 
 

@@ -50,7 +50,7 @@ class NativeModuleSwap(torch.nn.Module):
     @staticmethod
     def _reload_native(module, incompatible_keys):
         # weights changed under the wrapper (parent.load_state_dict): the native copy is re-packed from the kept module
-        native = object.__getattribute__(module, "_native")
+        native = native_of(module)
         if hasattr(native, "load_state_dict"):
             try:
                 native.load_state_dict(module._reference.state_dict())
@@ -78,6 +78,11 @@ class NativeModuleSwap(torch.nn.Module):
             return getattr(super().__getattr__("_reference"), item)
 
 
+def native_of(module):
+    """The native implementation behind a ``NativeModuleSwap``; any other object is returned as it is."""
+    return object.__getattribute__(module, "_native") if isinstance(module, NativeModuleSwap) else module
+
+
 class _NativeEmbedTokens:
     """``wrapper.embed_tokens``: callable like the reference's ``nn.Embedding``; the native gather first, the kept module's own
     ``embed_tokens`` on ValueError / RuntimeError / NotImplementedError.  Other attributes (``weight``, ``num_embeddings`` ...) are the
@@ -89,7 +94,7 @@ class _NativeEmbedTokens:
     def __call__(self, ids):
         swap = self._swap
         try:
-            out = object.__getattribute__(swap, "_native").embed_tokens(ids)
+            out = native_of(swap).embed_tokens(ids)
             swap.native_calls += 1
             return out
         except (ValueError, RuntimeError, NotImplementedError) as exc:
