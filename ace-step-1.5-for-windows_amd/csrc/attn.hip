@@ -33,6 +33,9 @@ __device__ unsigned long long g_attn_probe[8];
 //   (key = 8*half + 16*(r>>3) + (r&7)): the P^T operand of O^T += V^T P^T then pairs with ONE 16-byte V^T read, and both
 //   tiles use the GEMM's 16-byte XOR swizzles (applied on the DMA source address).  The same permutation on the V^T rows
 //   makes a lane's output octet eight contiguous d: the epilogue is 8 x 16-byte stores per lane.
+// Shared with attn_gqa_kernel and attn_rot_kernel through the building blocks below: attn_keys (tile range, K / V^T bases), attn_k_voff /
+// attn_v_voff (DMA piece offsets), attn_q_to_lds (NW == 4), attn_softmax_step, attn_pack8, attn_store_uniform / attn_store_row,
+// attn_probe_loop.  Its own: the (q-block, q head) grid, split-KV, Q fragments in registers, the one-batch K loop.
 __device__ __forceinline__ void attn_glds16(unsigned voff, const void* sbase, unsigned lds_addr) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
@@ -41,6 +44,185 @@ __device__ __forceinline__ void attn_glds16(unsigned voff, const void* sbase, un
                  : "memory");
 }
 __device__ __forceinline__ int pi23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }
+
+// ------------------------------------------------------------------------------------------------ building blocks of the three kernels
+// Straight-line arithmetic and address set-up only: no wait, barrier, scheduling barrier or opaque asm lives here (the DMA helpers call
+// attn_glds16); where those stand in the instruction stream is each kernel's own business.
+
+// Workgroup -> (q-block, KV head, sequence) of the GQA-shared kernels.  Block b runs on XCD b % 8 (observed; speed only): the KV head picks
+// the XCD, so that every workgroup reading one head's K / V^T - the q-blocks of a sequence, and for cross-attention every sequence
+// that attends the same condition slot - shares ONE private L2 (self-attention at the metric: 98 -> 74 MB per launch
+// leave the L2s; cross-attention: the 0.4 MB of a head's keys are fetched once per launch instead of once per workgroup).
+struct AttnUnit { int qb, hkv, n; };   // (n >= N: a surplus id, the grid is padded to a multiple of 8 by the launcher)
+__device__ __forceinline__ AttnUnit attn_unit(const AttnArgs& a, int QB) {
+    AttnUnit u;
+    const int nqb = (a.Sq + QB - 1) / QB;
+    const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
+    if ((a.Hkv & 7) == 0) {
+        const int hg = a.Hkv >> 3;
+        u.hkv = xcd + 8 * (j % hg);
+        const int rest = j / hg;
+        u.qb = rest % nqb;
+        u.n = rest / nqb;
+    } else {  // generic order
+        u.hkv = id % a.Hkv;
+        const int rest = id / a.Hkv;
+        u.qb = rest % nqb;
+        u.n = rest / nqb;
+    }
+    return u;
+}
+
+// The key tiles [kt_lo, kt_hi) a q-block of QB rows from q0 walks (band, skv valid keys) and its KV head's K / V^T base pointers.
+struct AttnKeys { int kt_lo, kt_hi; const bf16_t* kbase; const bf16_t* vbase; };
+__device__ __forceinline__ AttnKeys attn_keys(const AttnArgs& a, int n, int hkv, int q0, int QB, int skv) {
+    AttnKeys t;
+    t.kt_lo = 0, t.kt_hi = (skv + KB - 1) / KB;
+    if (a.window >= 0) {
+        t.kt_lo = max(0, q0 - a.window) / KB;
+        t.kt_hi = min(t.kt_hi, (min(skv - 1, q0 + QB - 1 + a.window)) / KB + 1);
+    }
+    t.kbase = (a.use_tab ? reinterpret_cast<const bf16_t*>(a.k_tab[n]) : a.k + (long)n * a.k_seq_stride) + (long)hkv * a.k_head_stride;
+    t.vbase = (a.use_tab ? reinterpret_cast<const bf16_t*>(a.vt_tab[n]) : a.vt + (long)n * a.vt_seq_stride) + (long)hkv * a.vt_head_stride;
+    return t;
+}
+
+// A tile goes to LDS as 32 DMA pieces of 1 KB: K piece p (< 16) = K rows 4p..4p+3 (256 B each), lane = (row<<4 | slot'); V^T piece p
+// (< 16) = V^T rows 8p..8p+7 (128 B each), lane = (row<<3 | slot').  LDS image lane-linear; the XOR swizzle is on the source chunk.
+// Addressing = uniform 64-bit base in SGPRs (advances per tile) + a loop-invariant 32-bit per-lane byte offset: the
+// asm's VGPR operands are never recycled (hipcc waits vmcnt before it lets anything overwrite a register an inline-asm
+// VMEM instruction used, which would drain the prefetch in the middle of the QK MFMAs).  `tail`: the offset for the last (possibly
+// ragged) tile, rows past Skv - 1 clamped to it.
+__device__ __forceinline__ unsigned attn_k_voff(const AttnArgs& a, int p, int lane, bool tail) {
+    const int tail_key0 = ((a.Skv - 1) / KB) * KB;  // first key of the last tile
+    const int key = 4 * p + (lane >> 4);
+    const int j = (lane & 15) ^ (key & 15);
+    const int row = tail ? min(tail_key0 + key, a.Skv - 1) - tail_key0 : key;
+    return (unsigned)(row * a.k_row_stride + j * 8) * 2u;
+}
+__device__ __forceinline__ unsigned attn_v_voff(const AttnArgs& a, int p, int lane) {
+    const int d = 8 * p + (lane >> 3);
+    const int jv = (lane & 7) ^ ((d >> 1) & 7);
+    return (unsigned)(d * a.vt_ld + jv * 8) * 2u;
+}
+// ... of piece p of the 32, K pieces first, then V^T pieces (whose tail offset is the ordinary one; p >= 32: no piece).  Returned by
+// value: handed the kernels' offset arrays by reference, hipcc leaves them in scratch memory.
+struct AttnPieceOff { unsigned voff, voff_tail; };
+__device__ __forceinline__ AttnPieceOff attn_piece_voff(const AttnArgs& a, int p, int lane) {
+    if (p < 16) return {attn_k_voff(a, p, lane, false), attn_k_voff(a, p, lane, true)};
+    const unsigned v = attn_v_voff(a, p - 16, lane);
+    return {v, v};
+}
+
+// Q rows qw0 .. qw0 + 31 of one head (qsrc: uniform) -> an 8 KB LDS slice at qbuf, as pieces i0 .. i0 + NP - 1 of its eight (four rows of
+// 256 B each: full lines - a row-per-lane 16-byte load pattern fetches every line eight times - XOR-swizzled chunks); rows past Sq - 1 clamped.
+template <int NP>
+__device__ __forceinline__ void attn_q_to_lds(const AttnArgs& a, const bf16_t* qsrc, int qw0, int lane, unsigned qbuf, int i0) {
+#pragma unroll
+    for (int i2 = 0; i2 < NP; ++i2) {
+        const int i = i0 + i2;
+        const int row_l = 4 * i + (lane >> 4);
+        const int j = (lane & 15) ^ (row_l & 15);
+        const unsigned voff = (unsigned)(min(qw0 + row_l, a.Sq - 1) * a.q_row_stride + j * 8) * 2u;
+        attn_glds16(voff, qsrc, (unsigned)__builtin_amdgcn_readfirstlane((int)(qbuf + (unsigned)i * 1024u)));
+    }
+}
+
+// eight consecutive values v[i0 .. i0 + 7] -> bf16x8 (P^T as an MFMA B operand; 16 bytes of an output row)
+template <typename V>
+__device__ __forceinline__ uint4 attn_pack8(const V& v, int i0) {
+    uint4 pk;
+    pk.x = pack_bf2(v[i0 + 0], v[i0 + 1]);
+    pk.y = pack_bf2(v[i0 + 2], v[i0 + 3]);
+    pk.z = pack_bf2(v[i0 + 4], v[i0 + 5]);
+    pk.w = pack_bf2(v[i0 + 6], v[i0 + 7]);
+    return pk;
+}
+
+// One online-softmax step of attn3_kernel and attn_gqa_kernel on a tile's two blocks of 32 keys x 32 query rows of S^T (s -> P, unnormalised),
+// the running (m, l) and O.  Lane owns query qrow; register r of s[t2] is key kb0 + t2*32 + 16*(r>>3) + (r&7) (kb0 = the tile's first key +
+// 8*half); !interior: keys past skv or outside the band |qrow - key| <= win are masked.
+// Deferred rescale: the running max only moves when some row's tile max exceeds it by more than 2^8 (wave-uniform
+// decision); otherwise p = 2^(s - m_run) may reach 256, harmless in fp32 / bf16, and the 64-multiply rescale of O
+// plus the alpha bookkeeping are skipped.  (m_run = -inf on a row's first live tile always takes the move branch.)
+// attn_rot_kernel's seg_sm is a COPY of this on one score block with packed-pair exponentials, kept on purpose: see the comment there.
+__device__ __forceinline__ void attn_softmax_step(f32x16 (&s)[2], f32x16 (&o)[4], float& m_run, float& l_run, bool interior, int kb0, int skv,
+                                                  int qrow, int win, float scale_log2, float defer_thr) {
+    if (!interior) {
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = kb0 + t2 * 32 + 16 * (r >> 3) + (r & 7);
+                const bool ok = (key < skv) & ((unsigned)(qrow - key + win) <= (unsigned)(2 * win));
+                s[t2][r] = ok ? s[t2][r] : -INFINITY;
+            }
+    }
+    float mx = s[0][0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[0][r]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[1][r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_tile = mx * scale_log2;
+    const bool move = __any(m_tile - m_run > defer_thr);
+    const float m_new = move ? fmaxf(m_run, m_tile) : m_run;
+    const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+    const float alpha = move ? __builtin_amdgcn_exp2f(m_run - m_use) : 1.0f;
+    m_run = m_new;
+    float psum = 0.f;
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t2][r], scale_log2, -m_use));
+            s[t2][r] = p;
+            psum += p;
+        }
+    l_run = l_run * alpha + psum;
+    if (move && __any(alpha != 1.0f)) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+    }
+}
+
+// Output row qrow of head h, from head dim d0 (d0 % 8 == 0)
+__device__ __forceinline__ bf16_t* attn_out_row(const AttnArgs& a, int n, int qrow, int h, int d0) {
+    return a.out + (long)n * a.o_seq_stride + (long)qrow * a.o_row_stride + h * 128 + d0;
+}
+// A row with no valid key at all (only possible with kv_len): the reference's finfo.min mask makes it uniform over ALL keys = vmean.
+// A lane copies NC 16-byte chunks, 16 head dims apart, from head dim d0 (the octets its O accumulators hold).
+template <int NC>
+__device__ __forceinline__ void attn_store_uniform(const AttnArgs& a, int n, int hkv, int d0, bf16_t* op) {
+    const bf16_t* vm = a.vmean + ((long)n * a.Hkv + hkv) * 128 + d0;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) *reinterpret_cast<uint4*>(op + c * 16) = *reinterpret_cast<const uint4*>(vm + c * 16);
+}
+// O[q][d] = O^T[d][q] * inv; register r of o[dt] is d = dt*32 + 16*(r>>3) + 8*half + (r&7): 8 x 16-byte stores per lane (op: attn_out_row at 8*half)
+__device__ __forceinline__ void attn_store_row(const f32x16 (&o)[4], float inv, bf16_t* op) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = o[dt][8 * g + e] * inv;
+            *reinterpret_cast<uint4*>(op + dt * 32 + 16 * g) = attn_pack8(v, 0);
+        }
+}
+
+// ACE355_ATTN_CLK, the probed wave after its K loop: loop clocks, wall clock, wait + barrier clocks, tiles walked, prologue clocks.  (The
+// record at exit, g_attn_probe[5], stays in each kernel: one statement behind an s_waitcnt of its own.)
+__device__ __forceinline__ void attn_probe_loop(unsigned long long pc0, unsigned long long pw0, unsigned long long pbar, int tiles,
+                                                unsigned long long t_entry) {
+    g_attn_probe[0] = clock64() - pc0;
+    g_attn_probe[1] = wall_clock64() - pw0;
+    g_attn_probe[2] = pbar;
+    g_attn_probe[3] = (unsigned long long)tiles;
+    g_attn_probe[4] = pc0 - t_entry;
+}
 
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs a, float scale_log2, float defer_thr) {
@@ -64,39 +246,27 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs a, float sca
     const bool wave_live = qw0 < a.Sq;         // waves past the end of the sequence only help with the DMA
     const int skv = a.kv_len ? a.kv_len[n] : a.Skv;  // valid (un-padded) keys of this sequence
 
-    int kt_lo = 0, kt_hi = (skv + KB - 1) / KB;
-    if (a.window >= 0) {
-        kt_lo = max(0, q0 - a.window) / KB;
-        kt_hi = min(kt_hi, (min(skv - 1, q0 + QB - 1 + a.window)) / KB + 1);
-    }
+    const AttnKeys keys = attn_keys(a, n, hkv, q0, QB, skv);
+    int kt_lo = keys.kt_lo, kt_hi = keys.kt_hi;
+    const bf16_t* kbase = keys.kbase;
+    const bf16_t* vbase = keys.vbase;
     if (ksp > 1) {  // split-KV: this workgroup's share of the key tiles (possibly empty: it then leaves a neutral partial)
         const int chunk = __builtin_amdgcn_readfirstlane((max(kt_hi - kt_lo, 0) + ksp - 1) / ksp);
         kt_lo = kt_lo + sp * chunk;
         kt_hi = min(kt_hi, kt_lo + chunk);
     }
-    const bf16_t* kbase = (a.use_tab ? reinterpret_cast<const bf16_t*>(a.k_tab[n]) : a.k + (long)n * a.k_seq_stride) + (long)hkv * a.k_head_stride;
-    const bf16_t* vbase = (a.use_tab ? reinterpret_cast<const bf16_t*>(a.vt_tab[n]) : a.vt + (long)n * a.vt_seq_stride) + (long)hkv * a.vt_head_stride;
 
-    // DMA piece p = wave + NW*i:  p < 16: K rows 4p..4p+3 (256 B each), lane = (row<<4 | slot');  p >= 16: V^T rows
-    // 8(p-16)..+7 (128 B each), lane = (row<<3 | slot').  LDS image lane-linear; the XOR swizzle is on the source chunk.
-    // Addressing = uniform 64-bit base in SGPRs (advances per tile) + a loop-invariant 32-bit per-lane byte offset: the
-    // asm's VGPR operands are never recycled (hipcc waits vmcnt before it lets anything overwrite a register an inline-asm
-    // VMEM instruction used, which would drain the prefetch in the middle of the QK MFMAs).
+    // This wave's DMA pieces (attn_k_voff): K pieces and V^T pieces wave + NW*i, i < NPK, each kind in an array of its own
     static_assert(16 % NW == 0, "K and V^T pieces must not mix inside one i");
-    constexpr int NPK = 16 / NW;  // K pieces per wave (i < NPK), V^T pieces per wave (i >= NPK)
+    constexpr int NPK = 16 / NW;  // K pieces per wave, V^T pieces per wave
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
     unsigned k_voff[NPK], k_voff_tail[NPK], v_voff[NPK];
-    const int tail_key0 = ((a.Skv - 1) / KB) * KB;  // first key of the last (possibly ragged) tile
 #pragma unroll
     for (int i = 0; i < NPK; ++i) {
         const int p = wave + NW * i;
-        const int key = 4 * p + (lane >> 4);
-        const int j = (lane & 15) ^ (key & 15);
-        k_voff[i] = (unsigned)(key * a.k_row_stride + j * 8) * 2u;
-        k_voff_tail[i] = (unsigned)((min(tail_key0 + key, a.Skv - 1) - tail_key0) * a.k_row_stride + j * 8) * 2u;
-        const int d = 8 * p + (lane >> 3);
-        const int jv = (lane & 7) ^ ((d >> 1) & 7);
-        v_voff[i] = (unsigned)(d * a.vt_ld + jv * 8) * 2u;
+        k_voff[i] = attn_k_voff(a, p, lane, false);
+        k_voff_tail[i] = attn_k_voff(a, p, lane, true);
+        v_voff[i] = attn_v_voff(a, p, lane);
     }
     auto issue = [&](int kt) {
         const int key0 = kt * KB;
@@ -122,19 +292,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs a, float sca
     // Q fragments (B operand of S^T = K Q^T): lane holds q = lq, d = ks*16 + half*8 .. +8
     bf16x8 qf[8];
     if constexpr (NW == 4) {
-        // Each wave DMAs its own 32 Q rows (256 B each, full lines: a row-per-lane 16-byte load pattern fetches every line
-        // eight times) into its 8 KB slice of the K/V buffer that is idle until tile kt_lo+1 is issued, then reads the
-        // fragments back.  Own data: this wave's vmcnt is the only ordering needed; the loop's first barrier keeps every
-        // other wave's next-tile DMA out of the slice until the fragments are in registers.
+        // Each wave DMAs its own 32 Q rows (attn_q_to_lds) into its 8 KB slice of the K/V buffer that is idle until tile kt_lo+1 is
+        // issued, then reads the fragments back.  Own data: this wave's vmcnt is the only ordering needed; the loop's first barrier keeps
+        // every other wave's next-tile DMA out of the slice until the fragments are in registers.
         const unsigned qbuf = lds0 + (unsigned)((kt_lo + 1) & 1) * BUF + (unsigned)wave * 8192u;
-        const bf16_t* qb = a.q + (long)n * a.q_seq_stride + h * 128;  // uniform
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int row_l = 4 * i + (lane >> 4);
-            const int j = (lane & 15) ^ (row_l & 15);
-            const unsigned voff = (unsigned)(min(qw0 + row_l, a.Sq - 1) * a.q_row_stride + j * 8) * 2u;
-            attn_glds16(voff, qb, (unsigned)__builtin_amdgcn_readfirstlane((int)(qbuf + (unsigned)i * 1024u)));
-        }
+        attn_q_to_lds<8>(a, a.q + (long)n * a.q_seq_stride + h * 128, qw0, lane, qbuf, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         const char* qs = smem + ((kt_lo + 1) & 1) * BUF + wave * 8192 + lq * 256;
@@ -211,70 +373,18 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs a, float sca
                         as_bf16x8(*reinterpret_cast<const uint4*>(Vs + dt * 4096 + v_row_off + (((t2 * 4 + 2 * t + half) ^ v_swz) << 4)));
         // lane owns query qrow; register r of s[t2] is key key0 + t2*32 + 16*(r>>3) + 8*half + (r&7)
         const bool interior = (key0 + KB <= skv) && (qw0 + 31 - key0 <= win) && (key0 + KB - 1 - qw0 <= win);
-        if (!interior) {
-            const int kb = key0 + 8 * half;
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kb + t2 * 32 + 16 * (r >> 3) + (r & 7);
-                    const bool ok = (key < skv) & ((unsigned)(qrow - key + win) <= (unsigned)(2 * win));
-                    s[t2][r] = ok ? s[t2][r] : -INFINITY;
-                }
-        }
-        float mx = s[0][0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[0][r]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[1][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        // Deferred rescale: the running max only moves when some row's tile max exceeds it by more than 2^8 (wave-uniform
-        // decision); otherwise p = 2^(s - m_run) may reach 256, harmless in fp32 / bf16, and the 64-multiply rescale of O
-        // plus the alpha bookkeeping are skipped.  (m_run = -inf on a row's first live tile always takes the move branch.)
-        const float m_tile = mx * scale_log2;
-        const bool move = __any(m_tile - m_run > defer_thr);
-        const float m_new = move ? fmaxf(m_run, m_tile) : m_run;
-        const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = move ? __builtin_amdgcn_exp2f(m_run - m_use) : 1.0f;
-        m_run = m_new;
-        float psum = 0.f;
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t2][r], scale_log2, -m_use));
-                s[t2][r] = p;
-                psum += p;
-            }
-        l_run = l_run * alpha + psum;
-        if (move && __any(alpha != 1.0f)) {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-        }
+        attn_softmax_step(s, o, m_run, l_run, interior, key0 + 8 * half, skv, qrow, win, scale_log2, defer_thr);
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                uint4 pb;
-                pb.x = pack_bf2(s[t2][8 * t + 0], s[t2][8 * t + 1]);
-                pb.y = pack_bf2(s[t2][8 * t + 2], s[t2][8 * t + 3]);
-                pb.z = pack_bf2(s[t2][8 * t + 4], s[t2][8 * t + 5]);
-                pb.w = pack_bf2(s[t2][8 * t + 6], s[t2][8 * t + 7]);
-                const bf16x8 pf = as_bf16x8(pb);
+                const bf16x8 pf = as_bf16x8(attn_pack8(s[t2], 8 * t));
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) o[dt] = mfma32(fr[(t2 * 2 + t) * 4 + dt], pf, o[dt]);
             }
     }
 
-    if (probe) {
-        g_attn_probe[0] = clock64() - pc0;
-        g_attn_probe[1] = wall_clock64() - pw0;
-        g_attn_probe[2] = pbar;
-        g_attn_probe[3] = (unsigned long long)(kt_hi - kt_lo);
-        g_attn_probe[4] = pc0 - t_entry;
-    }
+    if (probe) attn_probe_loop(pc0, pw0, pbar, kt_hi - kt_lo, t_entry);
     // O[q][d] = O^T[d][q] / l; register r of o[dt] is d = dt*32 + 16*(r>>3) + 8*half + (r&7)
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     if (ksp > 1) {
@@ -294,26 +404,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn3_kernel(AttnArgs a, float sca
         return;
     }
     const float inv = 1.f / l_tot;
-    if (qrow < a.Sq && l_tot == 0.f) {
-        // no valid key at all (only possible with kv_len): the reference's finfo.min mask makes this row uniform over ALL keys
-        bf16_t* op = a.out + (long)n * a.o_seq_stride + (long)qrow * a.o_row_stride + h * 128 + 8 * half;
-        const bf16_t* vm = a.vmean + ((long)n * a.Hkv + hkv) * 128 + 8 * half;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) *reinterpret_cast<uint4*>(op + c * 16) = *reinterpret_cast<const uint4*>(vm + c * 16);
-    } else if (qrow < a.Sq) {
-        bf16_t* op = a.out + (long)n * a.o_seq_stride + (long)qrow * a.o_row_stride + h * 128 + 8 * half;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                uint4 pk;
-                pk.x = pack_bf2(o[dt][8 * g + 0] * inv, o[dt][8 * g + 1] * inv);
-                pk.y = pack_bf2(o[dt][8 * g + 2] * inv, o[dt][8 * g + 3] * inv);
-                pk.z = pack_bf2(o[dt][8 * g + 4] * inv, o[dt][8 * g + 5] * inv);
-                pk.w = pack_bf2(o[dt][8 * g + 6] * inv, o[dt][8 * g + 7] * inv);
-                *reinterpret_cast<uint4*>(op + dt * 32 + 16 * g) = pk;
-            }
-    }
+    if (qrow < a.Sq && l_tot == 0.f) attn_store_uniform<8>(a, n, hkv, 8 * half, attn_out_row(a, n, qrow, h, 8 * half));
+    else if (qrow < a.Sq) attn_store_row(o, inv, attn_out_row(a, n, qrow, h, 8 * half));
     if (probe) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); g_attn_probe[5] = clock64() - t_entry; }
 }
 
@@ -358,7 +450,10 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(const float* __restrict
 // S (32) and a useful batch of K fragments: Q lives in LDS instead (each wave DMAs its own 32 rows into a private 8 KB
 // slice once) and its fragments are re-read per tile in the same batches as the K fragments; K / V^T fragments are read in
 // batches of 8 (half of a tile's contraction) instead of 16.  LDS: 2 x 32 KB K / V^T stages + 2*NWH x 8 KB of Q = 160 KB
-// at NWH = 6.  Tile images, swizzles, the row permutation, softmax and epilogue are attn3_kernel's.
+// at NWH = 6.  Tile images, swizzles, the row permutation, softmax and epilogue are attn3_kernel's, by the same building blocks: attn_unit
+// (workgroup order, with attn_rot_kernel), attn_keys, attn_piece_voff, attn_q_to_lds<8>, attn_softmax_step, attn_pack8,
+// attn_store_uniform<8> / attn_store_row, attn_probe_loop.  Its own: the batched K loop with the DMA pieces between its batches, the
+// per-tile re-materialised fragment addresses, the MXFP8 output store.
 template <int NWH>
 __global__ __launch_bounds__(NWH * 128, (2 * NWH + 3) / 4) void attn_gqa_kernel(AttnArgs a, float scale_log2, float defer_thr) {
     constexpr int NW = 2 * NWH;
@@ -369,28 +464,9 @@ __global__ __launch_bounds__(NWH * 128, (2 * NWH + 3) / 4) void attn_gqa_kernel(
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // Workgroup -> (q-block, KV head, sequence).  Block b runs on XCD b % 8 (observed; speed only): the KV head picks the XCD, so
-    // that every workgroup reading one head's K / V^T - the q-blocks of a sequence, and for cross-attention every sequence
-    // that attends the same condition slot - shares ONE private L2 (self-attention at the metric: 98 -> 74 MB per launch
-    // leave the L2s; cross-attention: the 0.4 MB of a head's keys are fetched once per launch instead of once per workgroup).
-    int qb, hkv, n;
-    {
-        const int nqb = (a.Sq + QB - 1) / QB;
-        const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
-        if ((a.Hkv & 7) == 0) {
-            const int hg = a.Hkv >> 3;
-            hkv = xcd + 8 * (j % hg);
-            const int rest = j / hg;
-            qb = rest % nqb;
-            n = rest / nqb;
-        } else {  // generic order (grid is padded to a multiple of 8 by the launcher: surplus ids leave)
-            hkv = id % a.Hkv;
-            const int rest = id / a.Hkv;
-            qb = rest % nqb;
-            n = rest / nqb;
-        }
-        if (n >= a.N) return;
-    }
+    const AttnUnit unit = attn_unit(a, QB);   // XCD-aware
+    const int qb = unit.qb, hkv = unit.hkv, n = unit.n;
+    if (n >= a.N) return;
     const unsigned long long t_entry = a.clk_probe ? clock64() : 0ull;
     const int hw = wave / NWH, wr = wave - hw * NWH;   // q head inside the group, 32-row tile inside the block
     const int h = hkv * 2 + hw;
@@ -402,31 +478,18 @@ __global__ __launch_bounds__(NWH * 128, (2 * NWH + 3) / 4) void attn_gqa_kernel(
     const bool wave_live = qw0 < a.Sq;
     const int skv = a.kv_len ? a.kv_len[n] : a.Skv;
 
-    int kt_lo = 0, kt_hi = (skv + KB - 1) / KB;
-    if (a.window >= 0) {
-        kt_lo = max(0, q0 - a.window) / KB;
-        kt_hi = min(kt_hi, (min(skv - 1, q0 + QB - 1 + a.window)) / KB + 1);
-    }
-    const bf16_t* kbase = (a.use_tab ? reinterpret_cast<const bf16_t*>(a.k_tab[n]) : a.k + (long)n * a.k_seq_stride) + (long)hkv * a.k_head_stride;
-    const bf16_t* vbase = (a.use_tab ? reinterpret_cast<const bf16_t*>(a.vt_tab[n]) : a.vt + (long)n * a.vt_seq_stride) + (long)hkv * a.vt_head_stride;
+    const AttnKeys keys = attn_keys(a, n, hkv, q0, QB, skv);
+    const int kt_lo = keys.kt_lo, kt_hi = keys.kt_hi;
+    const bf16_t* kbase = keys.kbase;
+    const bf16_t* vbase = keys.vbase;
 
-    // DMA piece p = wave + NW*i (p < 32): p < 16 = K rows 4p..4p+3, else V^T rows 8(p-16)..+7 (see attn3_kernel)
+    // DMA piece p = wave + NW*i (p < 32): p < 16 = K piece p, else V^T piece p - 16 (attn_piece_voff)
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
     unsigned p_voff[NPI], p_voff_tail[NPI];
-    const int tail_key0 = ((a.Skv - 1) / KB) * KB;
 #pragma unroll
     for (int i = 0; i < NPI; ++i) {
-        const int p = wave + NW * i;
-        if (p < 16) {
-            const int key = 4 * p + (lane >> 4);
-            const int j = (lane & 15) ^ (key & 15);
-            p_voff[i] = (unsigned)(key * a.k_row_stride + j * 8) * 2u;
-            p_voff_tail[i] = (unsigned)((min(tail_key0 + key, a.Skv - 1) - tail_key0) * a.k_row_stride + j * 8) * 2u;
-        } else {
-            const int d = 8 * (p - 16) + (lane >> 3);
-            const int jv = (lane & 7) ^ ((d >> 1) & 7);
-            p_voff[i] = p_voff_tail[i] = (unsigned)(d * a.vt_ld + jv * 8) * 2u;
-        }
+        const AttnPieceOff po = attn_piece_voff(a, wave + NW * i, lane);
+        p_voff[i] = po.voff, p_voff_tail[i] = po.voff_tail;
     }
     auto issue_piece = [&](int kt, int i) {  // this wave's i-th DMA instruction of tile kt
         const int key0 = kt * KB;
@@ -444,17 +507,7 @@ __global__ __launch_bounds__(NWH * 128, (2 * NWH + 3) / 4) void attn_gqa_kernel(
     };
 
     // this wave's 32 Q rows -> its private slice (full 256-byte lines, XOR-swizzled chunks), once
-    const unsigned qbuf = lds0 + 2u * BUF + (unsigned)wave * 8192u;
-    {
-        const bf16_t* qsrc = a.q + (long)n * a.q_seq_stride + h * 128;  // uniform
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int row_l = 4 * i + (lane >> 4);
-            const int j = (lane & 15) ^ (row_l & 15);
-            const unsigned voff = (unsigned)(min(qw0 + row_l, a.Sq - 1) * a.q_row_stride + j * 8) * 2u;
-            attn_glds16(voff, qsrc, (unsigned)__builtin_amdgcn_readfirstlane((int)(qbuf + (unsigned)i * 1024u)));
-        }
-    }
+    attn_q_to_lds<8>(a, a.q + (long)n * a.q_seq_stride + h * 128, qw0, lane, lds0 + 2u * BUF + (unsigned)wave * 8192u, 0);
     if (kt_lo < kt_hi) issue(kt_lo);
 
     f32x16 o[4];
@@ -546,58 +599,13 @@ __global__ __launch_bounds__(NWH * 128, (2 * NWH + 3) / 4) void attn_gqa_kernel(
             for (int dt = 0; dt < 4; ++dt)
                 fv[t * 4 + dt] = as_bf16x8(*reinterpret_cast<const uint4*>(Vs + dt * 4096 + v_row_off + ((t * 32) ^ vx)));
         const bool interior = (key0 + KB <= skv) && (qw0 + 31 - key0 <= win) && (key0 + KB - 1 - qw0 <= win);
-        if (!interior) {
-            const int kb0 = key0 + 8 * half;
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kb0 + t2 * 32 + 16 * (r >> 3) + (r & 7);
-                    const bool ok = (key < skv) & ((unsigned)(qrow - key + win) <= (unsigned)(2 * win));
-                    s[t2][r] = ok ? s[t2][r] : -INFINITY;
-                }
-        }
-        float mx = s[0][0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[0][r]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[1][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_tile = mx * scale_log2;
-        const bool move = __any(m_tile - m_run > defer_thr);
-        const float m_new = move ? fmaxf(m_run, m_tile) : m_run;
-        const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = move ? __builtin_amdgcn_exp2f(m_run - m_use) : 1.0f;
-        m_run = m_new;
-        float psum = 0.f;
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t2][r], scale_log2, -m_use));
-                s[t2][r] = p;
-                psum += p;
-            }
-        l_run = l_run * alpha + psum;
-        if (move && __any(alpha != 1.0f)) {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-        }
+        attn_softmax_step(s, o, m_run, l_run, interior, key0 + 8 * half, skv, qrow, win, scale_log2, defer_thr);
         // ---- O^T += V^T P^T: keys 0..31 with the fragments already here, the second half's reads issued under those MFMAs
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2) {
             bf16x8 pf[2];
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                uint4 pb;
-                pb.x = pack_bf2(s[t2][8 * t + 0], s[t2][8 * t + 1]);
-                pb.y = pack_bf2(s[t2][8 * t + 2], s[t2][8 * t + 3]);
-                pb.z = pack_bf2(s[t2][8 * t + 4], s[t2][8 * t + 5]);
-                pb.w = pack_bf2(s[t2][8 * t + 6], s[t2][8 * t + 7]);
-                pf[t] = as_bf16x8(pb);
-            }
+            for (int t = 0; t < 2; ++t) pf[t] = as_bf16x8(attn_pack8(s[t2], 8 * t));
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -612,20 +620,11 @@ __global__ __launch_bounds__(NWH * 128, (2 * NWH + 3) / 4) void attn_gqa_kernel(
         }
     }
 
-    if (probe) {
-        g_attn_probe[0] = clock64() - pc0;
-        g_attn_probe[1] = wall_clock64() - pw0;
-        g_attn_probe[2] = pbar;
-        g_attn_probe[3] = (unsigned long long)(kt_hi - kt_lo);
-        g_attn_probe[4] = pc0 - t_entry;
-    }
+    if (probe) attn_probe_loop(pc0, pw0, pbar, kt_hi - kt_lo, t_entry);
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.f / l_tot;
     if (qrow < a.Sq && l_tot == 0.f) {
-        bf16_t* op = a.out + (long)n * a.o_seq_stride + (long)qrow * a.o_row_stride + h * 128 + 8 * half;
-        const bf16_t* vm = a.vmean + ((long)n * a.Hkv + hkv) * 128 + 8 * half;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) *reinterpret_cast<uint4*>(op + c * 16) = *reinterpret_cast<const uint4*>(vm + c * 16);
+        attn_store_uniform<8>(a, n, hkv, 8 * half, attn_out_row(a, n, qrow, h, 8 * half));
     } else if (a.out_q) {
         // MXFP8 output: block dt of this head = columns 32 dt .. +31 = this lane's 16 values (g = 0, 1) + its partner's (lane ^ 32);
         // the values quantised are the bf16-rounded outputs, so this equals attention -> mx_quant_kernel bit for bit.  Every lane
@@ -663,18 +662,7 @@ __global__ __launch_bounds__(NWH * 128, (2 * NWH + 3) / 4) void attn_gqa_kernel(
         }
         if (qrow < a.Sq && half == 0) a.out_scales[(long)h * a.out_pad + grow] = word;
     } else if (qrow < a.Sq) {
-        bf16_t* op = a.out + (long)n * a.o_seq_stride + (long)qrow * a.o_row_stride + h * 128 + 8 * half;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                uint4 pk;
-                pk.x = pack_bf2(o[dt][8 * g + 0] * inv, o[dt][8 * g + 1] * inv);
-                pk.y = pack_bf2(o[dt][8 * g + 2] * inv, o[dt][8 * g + 3] * inv);
-                pk.z = pack_bf2(o[dt][8 * g + 4] * inv, o[dt][8 * g + 5] * inv);
-                pk.w = pack_bf2(o[dt][8 * g + 6] * inv, o[dt][8 * g + 7] * inv);
-                *reinterpret_cast<uint4*>(op + dt * 32 + 16 * g) = pk;
-            }
+        attn_store_row(o, inv, attn_out_row(a, n, qrow, h, 8 * half));
     }
     if (probe) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); g_attn_probe[5] = clock64() - t_entry; }
 }
@@ -708,7 +696,9 @@ __global__ __launch_bounds__(NWH * 128, (2 * NWH + 3) / 4) void attn_gqa_kernel(
 // waves that split every 64-key tile into its two 32-key halves (S is 16 registers instead of 32) and keep separate (m, l, O)
 // states, merged through LDS after the loop (each wave finishes half of the head dim).  Per wave and tile: 8 + 8 MFMAs and 16
 // exponentials; per SIMD and tile 1536 cycles of MFMA issue against ~1500 of VALU, running side by side instead of in turn.
-// Tile images, swizzles, the row permutation and the deferred rescale are attn3_kernel's.
+// Tile images, swizzles, the row permutation and the deferred rescale are attn3_kernel's, by the same building blocks: attn_unit, attn_keys,
+// attn_piece_voff, attn_q_to_lds<4> (each wave of a pair brings half of the slice), attn_pack8, attn_store_uniform<4>, attn_probe_loop.
+// Its own: the rings, the three rotated loops, seg_sm (a copy of attn_softmax_step, see there), the merge of the two key halves through LDS.
 template <int NRT>   // 32-row tiles per q head; waves = 2 heads x NRT x 2 key halves
 __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, float scale_log2, float defer_thr) {
     constexpr int NW = 4 * NRT;
@@ -725,24 +715,9 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int qb, hkv, n;
-    {
-        const int nqb = (a.Sq + QB - 1) / QB;
-        const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
-        if ((a.Hkv & 7) == 0) {
-            const int hg = a.Hkv >> 3;
-            hkv = xcd + 8 * (j % hg);
-            const int rest = j / hg;
-            qb = rest % nqb;
-            n = rest / nqb;
-        } else {
-            hkv = id % a.Hkv;
-            const int rest = id / a.Hkv;
-            qb = rest % nqb;
-            n = rest / nqb;
-        }
-        if (n >= a.N) return;
-    }
+    const AttnUnit unit = attn_unit(a, QB);
+    const int qb = unit.qb, hkv = unit.hkv, n = unit.n;
+    if (n >= a.N) return;
     const unsigned long long t_entry = a.clk_probe ? clock64() : 0ull;
     const int grp = wave >> 2;                                   // rotation group (waves w, w + 4, w + 8 share SIMD w & 3)
     const int hw = wave / (2 * NRT), rr = wave - hw * 2 * NRT;   // q head inside the group
@@ -757,33 +732,18 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
     const bool wave_live = qw0 < a.Sq;
     const int skv = __builtin_amdgcn_readfirstlane(a.kv_len ? a.kv_len[n] : a.Skv);   // (uniform: every per-tile predicate below stays on the scalar unit)
 
-    int kt_lo = 0, kt_hi = (skv + KB - 1) / KB;
-    if (a.window >= 0) {
-        kt_lo = max(0, q0 - a.window) / KB;
-        kt_hi = min(kt_hi, (min(skv - 1, q0 + QB - 1 + a.window)) / KB + 1);
-    }
-    kt_lo = __builtin_amdgcn_readfirstlane(kt_lo);
-    kt_hi = __builtin_amdgcn_readfirstlane(kt_hi);
-    const bf16_t* kbase = (a.use_tab ? reinterpret_cast<const bf16_t*>(a.k_tab[n]) : a.k + (long)n * a.k_seq_stride) + (long)hkv * a.k_head_stride;
-    const bf16_t* vbase = (a.use_tab ? reinterpret_cast<const bf16_t*>(a.vt_tab[n]) : a.vt + (long)n * a.vt_seq_stride) + (long)hkv * a.vt_head_stride;
+    const AttnKeys keys = attn_keys(a, n, hkv, q0, QB, skv);
+    const int kt_lo = __builtin_amdgcn_readfirstlane(keys.kt_lo), kt_hi = __builtin_amdgcn_readfirstlane(keys.kt_hi);
+    const bf16_t* kbase = keys.kbase;
+    const bf16_t* vbase = keys.vbase;
 
-    // DMA piece p = wave + NW*i (p < 32): p < 16 = K rows 4p..4p+3, else V^T rows 8(p-16)..+7 (see attn3_kernel)
+    // DMA piece p = wave + NW*i (p < 32): p < 16 = K piece p, else V^T piece p - 16 (attn_piece_voff)
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
     unsigned p_voff[NPI], p_voff_tail[NPI];
-    const int tail_key0 = ((a.Skv - 1) / KB) * KB;
 #pragma unroll
     for (int i = 0; i < NPI; ++i) {
-        const int p = wave + NW * i;
-        if (p < 16) {
-            const int key = 4 * p + (lane >> 4);
-            const int j = (lane & 15) ^ (key & 15);
-            p_voff[i] = (unsigned)(key * a.k_row_stride + j * 8) * 2u;
-            p_voff_tail[i] = (unsigned)((min(tail_key0 + key, a.Skv - 1) - tail_key0) * a.k_row_stride + j * 8) * 2u;
-        } else {
-            const int d = 8 * (p - 16) + (lane >> 3);
-            const int jv = (lane & 7) ^ ((d >> 1) & 7);
-            p_voff[i] = p_voff_tail[i] = (unsigned)(d * a.vt_ld + jv * 8) * 2u;
-        }
+        const AttnPieceOff po = attn_piece_voff(a, wave + NW * i, lane);
+        p_voff[i] = po.voff, p_voff_tail[i] = po.voff_tail;
     }
     auto vstage = [&](int kt) {  // V^T ring slot of tile kt (wave-uniform)
         const int r = kt - kt_lo;
@@ -804,18 +764,7 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
     };
 
     // the pair's 32 Q rows -> its 8 KB slice (full 256-byte lines, XOR-swizzled chunks): each of the two waves brings four of the rows' eight KB
-    {
-        const bf16_t* qsrc = a.q + (long)n * a.q_seq_stride + h * 128;  // uniform
-        const unsigned qbuf = lds0 + QOFF + (unsigned)pair * 8192u;
-#pragma unroll
-        for (int i2 = 0; i2 < 4; ++i2) {
-            const int i = kh * 4 + i2;
-            const int row_l = 4 * i + (lane >> 4);
-            const int j = (lane & 15) ^ (row_l & 15);
-            const unsigned voff = (unsigned)(min(qw0 + row_l, a.Sq - 1) * a.q_row_stride + j * 8) * 2u;
-            attn_glds16(voff, qsrc, (unsigned)__builtin_amdgcn_readfirstlane((int)(qbuf + (unsigned)i * 1024u)));
-        }
-    }
+    attn_q_to_lds<4>(a, a.q + (long)n * a.q_seq_stride + h * 128, qw0, lane, lds0 + QOFF + (unsigned)pair * 8192u, kh * 4);
 #pragma unroll
     for (int t = 0; t < PD; ++t)
         if (kt_lo + t < kt_hi) {
@@ -829,10 +778,10 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
-    f32x16 sreg;          // S^T of this wave's 32 keys x 32 query rows (group 2 carries it across the barrier)
+    f32x16 sreg[1];       // S^T of this wave's 32 keys x 32 query rows: one score block (group 2 carries it across the barrier)
     bf16x8 pf[2];         // P^T as the B operand of the two 16-key MFMA steps (group 1 carries it across the barrier)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) sreg[r] = 0.f;
+    for (int r = 0; r < 16; ++r) sreg[0][r] = 0.f;
     pf[0] = pf[1] = as_bf16x8(make_uint4(0, 0, 0, 0));
 
     const int prow = pi23(lq);
@@ -865,10 +814,10 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
     auto mma_qk = [&](const bf16x8 (&f)[4], bool first) {
         if (first) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sreg[r] = 0.f;
+            for (int r = 0; r < 16; ++r) sreg[0][r] = 0.f;
         }
-        sreg = mfma32(f[0], f[2], sreg);
-        sreg = mfma32(f[1], f[3], sreg);
+        sreg[0] = mfma32(f[0], f[2], sreg[0]);
+        sreg[0] = mfma32(f[1], f[3], sreg[0]);
     };
     auto ld_pv = [&](bf16x8 (&f)[4], int kt, int t) {    // V^T fragments of 16-key step t of this wave's 32 keys: f[dt]
         int vx = (half ^ v_swz) << 4;
@@ -890,6 +839,9 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
     };
     auto seg_sm = [&](int kt) {   // online softmax step on sreg -> pf, (m_run, l_run), O rescaled when the running max moved
         const int k0 = kt * KB + 32 * kh;
+        // A copy of attn_softmax_step on this wave's ONE score block, kept inline on purpose: through the shared function this kernel's tile
+        // predicates compiled to other scalar code (80 instead of 78 SGPRs) and its launches measured above the parent's bound
+        // (profiles/attn_blocks_refactor.txt section 4).  (pairs: v_pk_fma_f32 / v_pk_add_f32 halve the plain VALU work around the 16 exponentials)
         const bool interior = (k0 + 32 <= skv) && (qw0 + 31 - k0 <= win) && (k0 + 31 - qw0 <= win);
         if (!interior) {
             const int kb0 = k0 + 8 * half;
@@ -897,12 +849,12 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
             for (int r = 0; r < 16; ++r) {
                 const int key = kb0 + 16 * (r >> 3) + (r & 7);
                 const bool ok = (key < skv) & ((unsigned)(qrow - key + win) <= (unsigned)(2 * win));
-                sreg[r] = ok ? sreg[r] : -INFINITY;
+                sreg[0][r] = ok ? sreg[0][r] : -INFINITY;
             }
         }
-        float mx = sreg[0];
+        float mx = sreg[0][0];
 #pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sreg[r]);
+        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sreg[0][r]);
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         const float m_tile = mx * scale_log2;
         const bool move = __any(m_tile - m_run > defer_thr);
@@ -910,16 +862,15 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
         const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
         const float alpha = move ? __builtin_amdgcn_exp2f(m_run - m_use) : 1.0f;
         m_run = m_new;
-        // (pairs: v_pk_fma_f32 / v_pk_add_f32 halve the plain VALU work around the 16 exponentials)
         f32x2_t psum2 = {0.f, 0.f};
         const f32x2_t sc2 = {scale_log2, scale_log2}, mu2 = {-m_use, -m_use};
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
-            const f32x2_t x = {sreg[r], sreg[r + 1]};
+            const f32x2_t x = {sreg[0][r], sreg[0][r + 1]};
             const f32x2_t y = __builtin_elementwise_fma(x, sc2, mu2);
             const f32x2_t p = {__builtin_amdgcn_exp2f(y[0]), __builtin_amdgcn_exp2f(y[1])};
-            sreg[r] = p[0];
-            sreg[r + 1] = p[1];
+            sreg[0][r] = p[0];
+            sreg[0][r + 1] = p[1];
             psum2 += p;
         }
         l_run = l_run * alpha + (psum2[0] + psum2[1]);
@@ -930,14 +881,7 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
                 for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
         }
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            uint4 pb;
-            pb.x = pack_bf2(sreg[8 * t + 0], sreg[8 * t + 1]);
-            pb.y = pack_bf2(sreg[8 * t + 2], sreg[8 * t + 3]);
-            pb.z = pack_bf2(sreg[8 * t + 4], sreg[8 * t + 5]);
-            pb.w = pack_bf2(sreg[8 * t + 6], sreg[8 * t + 7]);
-            pf[t] = as_bf16x8(pb);
-        }
+        for (int t = 0; t < 2; ++t) pf[t] = as_bf16x8(attn_pack8(sreg[0], 8 * t));
     };
     // Loads retire in order: before the barrier of tile kt this wave's pieces of tiles <= kt must have landed (first time: its Q rows
     // too), the PD - 1 tiles requested after it may stay in flight (waves 0-7 own three pieces of a tile, waves 8-11 two).
@@ -1029,13 +973,7 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
 #undef ROT_QK_TAIL
 #undef ROT_SB
 
-    if (probe) {
-        g_attn_probe[0] = clock64() - pc0;
-        g_attn_probe[1] = wall_clock64() - pw0;
-        g_attn_probe[2] = 0;
-        g_attn_probe[3] = (unsigned long long)(kt_hi - kt_lo);
-        g_attn_probe[4] = pc0 - t_entry;
-    }
+    if (probe) attn_probe_loop(pc0, pw0, 0, kt_hi - kt_lo, t_entry);
 
     // ---- merge of the two key halves: wave kh finishes head dims [64 kh, 64 kh + 64) and hands the other half of its O to its partner
     float l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -1065,12 +1003,9 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
     const float c_me = w_me * inv, c_pa = w_pa * inv;
     const char* theirs = smem + pw * 8192 + lane * 16;
     if (qrow < a.Sq && l_tot == 0.f) {
-        bf16_t* op = a.out + (long)n * a.o_seq_stride + (long)qrow * a.o_row_stride + h * 128 + 64 * kh + 8 * half;
-        const bf16_t* vm = a.vmean + ((long)n * a.Hkv + hkv) * 128 + 64 * kh + 8 * half;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) *reinterpret_cast<uint4*>(op + c * 16) = *reinterpret_cast<const uint4*>(vm + c * 16);
+        attn_store_uniform<4>(a, n, hkv, 64 * kh + 8 * half, attn_out_row(a, n, qrow, h, 64 * kh + 8 * half));
     } else {
-        bf16_t* op = a.out + (long)n * a.o_seq_stride + (long)qrow * a.o_row_stride + h * 128 + 64 * kh + 8 * half;
+        bf16_t* op = attn_out_row(a, n, qrow, h, 64 * kh + 8 * half);
         auto finish = [&](const f32x16& x, int d2) {   // head dims 64 kh + 32 d2 .. + 31 of this lane's row
             float v[16];
 #pragma unroll
@@ -1083,14 +1018,7 @@ __global__ __launch_bounds__(NRT * 256, NRT) void attn_rot_kernel(AttnArgs a, fl
             }
             if (qrow < a.Sq) {
 #pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    uint4 pk;
-                    pk.x = pack_bf2(v[8 * g + 0], v[8 * g + 1]);
-                    pk.y = pack_bf2(v[8 * g + 2], v[8 * g + 3]);
-                    pk.z = pack_bf2(v[8 * g + 4], v[8 * g + 5]);
-                    pk.w = pack_bf2(v[8 * g + 6], v[8 * g + 7]);
-                    *reinterpret_cast<uint4*>(op + d2 * 32 + 16 * g) = pk;
-                }
+                for (int g = 0; g < 2; ++g) *reinterpret_cast<uint4*>(op + d2 * 32 + 16 * g) = attn_pack8(v, 8 * g);
             }
         };
         if (kh == 0) { finish(o[0], 0); finish(o[1], 1); }
