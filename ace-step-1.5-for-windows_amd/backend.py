@@ -39,6 +39,7 @@ _LM_SAMPLER_ENV = os.environ.get("ACE355_LM_SAMPLER", "") == "1"   # read once: 
 _LM_LOOP_ENV = os.environ.get("ACE355_LM_LOOP", "") == "1"         # read once: the default of NativeLmMixin.use_native_lm_loop
 _LM_BATCH_ENV = os.environ.get("ACE355_LM_BATCH", "") == "1"       # read once: the default of NativeLmMixin.use_native_lm_batch
 _LM_SCORE_ENV = os.environ.get("ACE355_LM_SCORE", "") == "1"       # read once: the default of NativeLmMixin.use_native_lm_score
+_LM_GQA4_ENV = os.environ.get("ACE355_LM_GQA4", "") == "1"         # read once: the default of NativeLmMixin.use_native_lm_gqa4
 _AUDIO_IN_ENV = os.environ.get("ACE355_AUDIO_IN", "") == "1"       # read once: the default of NativeAudioInMixin.use_native_audio_in
 
 
@@ -481,6 +482,11 @@ class NativeLmMixin:
     ``offload_to_cpu``, ``native_lm_max_positions`` (cache positions: prompt + generated tokens, default 8192)."""
 
     use_native_lm: bool = False
+    # Four q heads per kv head (``acestep-5Hz-lm-4B``: Qwen3-4B, 32 / 8 heads) are served only to a host that asks: with this flag
+    # set (ACE355_LM_GQA4=1 turns it on for every host) the swap below passes ``allow_gqa4=True`` down to ``ace355_lm_create_ex``.
+    # Without it a 4B host logs the refusal and keeps PyTorch, as before.  Opt-in because the layout is unpinned on trained weights
+    # and its native copy costs 8 GB beside the module.
+    use_native_lm_gqa4: bool = _LM_GQA4_ENV
 
     def _init_native_lm(self) -> bool:
         """Swap ``self.llm`` for ``modswap.NativeCausalLMSwap`` after the model is loaded: ``_forward_pass``'s prefill and decode steps
@@ -495,11 +501,12 @@ class NativeLmMixin:
             if getattr(self, "llm", None) is None:
                 raise RuntimeError("no LM loaded")
             from . import modswap
-            wrapper = modswap.swap_in_lm(self, self.device, max_positions=int(getattr(self, "native_lm_max_positions", 8192)))
+            opt_in = {"allow_gqa4": True} if self.use_native_lm_gqa4 else {}
+            wrapper = modswap.swap_in_lm(self, self.device, max_positions=int(getattr(self, "native_lm_max_positions", 8192)), **opt_in)
             self.use_native_lm = True
             cfg = modswap.native_of(wrapper).cfg
-            logger.info("[native-lm] packed for gfx950 (%d layers, hidden %d, vocabulary %d)", cfg.num_hidden_layers, cfg.hidden_size,
-                        cfg.vocab_size)
+            logger.info("[native-lm] packed for gfx950 (%d layers, hidden %d, %d / %d heads, vocabulary %d)", cfg.num_hidden_layers,
+                        cfg.hidden_size, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.vocab_size)
             return True
         except Exception as exc:
             logger.warning("[native-lm] init failed (%s: %s); PyTorch path stays active", type(exc).__name__, exc)

@@ -222,19 +222,22 @@ class TextEncoderConfig:
 
 @dataclass
 class LmConfig(TextEncoderConfig):
-    """Fields of transformers' ``Qwen3Config`` that ``Qwen3ForCausalLM`` (the reference's 5 Hz LM, 0.6B / 1.7B) uses: the text encoder's
+    """Fields of transformers' ``Qwen3Config`` that ``Qwen3ForCausalLM`` (the reference's 5 Hz LM, 0.6B / 1.7B / 4B) uses: the text encoder's
     stack plus the head.  ``vocab_size`` is whatever the checkpoint says (Qwen3's vocabulary plus the audio-code tokens)."""
 
     tie_word_embeddings: bool = True
 
     @classmethod
-    def from_reference(cls, cfg) -> "LmConfig":
+    def from_reference(cls, cfg, allow_gqa4: bool = False) -> "LmConfig":
         """From a ``Qwen3Config``.  Refuses what ``TextEncoderConfig.from_reference`` refuses (sliding-window layers, ``attention_bias``,
-        non-default RoPE) and the head layouts the kernels do not serve (Qwen3-4B's 32 / 8 heads): ``NotImplementedError``."""
+        non-default RoPE) and the head layouts the kernels do not serve: ``NotImplementedError``.  Two q heads per kv head of 128 are
+        always served; four (Qwen3-4B's 32 / 8 heads) only to a caller that asks with ``allow_gqa4=True``."""
         base = TextEncoderConfig.from_reference(cfg)
-        if base.head_dim != 128 or base.num_attention_heads != 2 * base.num_key_value_heads:
+        ratios = (2, 4) if allow_gqa4 else (2,)
+        if base.head_dim != 128 or all(base.num_attention_heads != g * base.num_key_value_heads for g in ratios):
+            served = "2 or 4 q heads" if allow_gqa4 else "2 q heads"
             raise NotImplementedError(f"ace355: LM head layout {base.num_attention_heads} / {base.num_key_value_heads} heads of "
-                                      f"{base.head_dim} (only 2 q heads per kv head, head_dim 128)")
+                                      f"{base.head_dim} (only {served} per kv head, head_dim 128)")
         return cls(**base.__dict__, tie_word_embeddings=bool(getattr(cfg, "tie_word_embeddings", False)))
 
     def weight_shapes(self) -> Dict[str, Tuple[int, ...]]:

@@ -125,15 +125,17 @@ int run_encoder_pass(EncBase* h, const EncoderW& E, const EncPassRequest& rq, co
 void free_encoder(EncBase* h);   // free_base + the workspace
 
 // textenc.hip.  k_first_dev (null: none): per-sequence first visible key; query rows below it store zeros.
-int launch_causal_attention(const bf16_t* qkv, int ld, int k_col0, int v_col0, bf16_t* out, int o_ld, int N, int S, int Hkv, float scale,
-                            hipStream_t s, const int* k_first_dev = nullptr);
+// Hq = 2 Hkv or 4 Hkv: q head hq reads kv head hq / (Hq / Hkv).
+int launch_causal_attention(const bf16_t* qkv, int ld, int k_col0, int v_col0, bf16_t* out, int o_ld, int N, int S, int Hq, int Hkv,
+                            float scale, hipStream_t s, const int* k_first_dev = nullptr);
 int launch_embed_rows(const bf16_t* table, const int* ids_dev, float* out_f32, bf16_t* out_bf, long rows, int D, hipStream_t s);
 
 // lm.hip.  Rows n * S + s of the QKV workspace -> layer `layer` of the cache at position pos0 + s.
 int launch_kv_store(const bf16_t* qkv, int ld, int k_col0, int v_col0, const KvCache& c, int layer, int N, int S, int Hkv, int pos0,
                     hipStream_t s);
-// One query row per (sequence, q head) (row n of the QKV workspace) over keys [first[n], len) of the cache; out [N, 2 Hkv * 128] bf16.
-int launch_decode_attention(const bf16_t* qkv, int ld, const KvCache& c, int layer, int len, bf16_t* out, int N, int Hkv, float scale,
-                            hipStream_t s);
+// One query row per (sequence, q head) (row n of the QKV workspace) over keys [first[n], len) of the cache; out [N, Hq * 128] bf16,
+// Hq = 2 Hkv or 4 Hkv.
+int launch_decode_attention(const bf16_t* qkv, int ld, const KvCache& c, int layer, int len, bf16_t* out, int N, int Hq, int Hkv,
+                            float scale, hipStream_t s);
 
 }  // namespace ace355

@@ -225,9 +225,9 @@ int run_encoder_pass(EncBase* h, const EncoderW& E, const EncPassRequest& rq, co
             break;
         }
         case ACE355_ENC_STEP_KV_STORE: rc = launch_kv_store(qkv, st.ld, st.k_col0, st.v_col0, *cache, st.layer, st.seqs, st.Sq, st.Hkv, st.pos0, s); break;
-        case ACE355_ENC_STEP_DECODE_ATTN: rc = launch_decode_attention(qkv, st.ld, *cache, st.layer, st.len, h->ao, st.seqs, st.Hkv, scale, s); break;
+        case ACE355_ENC_STEP_DECODE_ATTN: rc = launch_decode_attention(qkv, st.ld, *cache, st.layer, st.len, h->ao, st.seqs, st.Hq, st.Hkv, scale, s); break;
         case ACE355_ENC_STEP_CAUSAL_ATTN:
-            rc = launch_causal_attention(qkv, st.ld, st.k_col0, st.v_col0, h->ao, st.o_ld, st.seqs, st.Sq, st.Hkv, scale, s, st.first ? cache->first_dev : nullptr);
+            rc = launch_causal_attention(qkv, st.ld, st.k_col0, st.v_col0, h->ao, st.o_ld, st.seqs, st.Sq, st.Hq, st.Hkv, scale, s, st.first ? cache->first_dev : nullptr);
             break;
         case ACE355_ENC_STEP_TRANSPOSE_V: rc = launch_transpose_v(qkv, st.ld, st.v_col0, st.seqs, st.Sq, st.Hkv, h->vt, st.Sp, s); break;
         case ACE355_ENC_STEP_VMEAN: rc = launch_vmean(qkv, st.ld, st.v_col0, st.seqs, st.Sq, st.Hkv, h->vmean, s); break;

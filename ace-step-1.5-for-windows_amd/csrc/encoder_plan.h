@@ -57,6 +57,8 @@ inline void plan_encoder_pass(const EncPassRequest& r, EncPassPlan& p) {
             if (decode && !r.has_first) return refuse("decode attention: cache bounds");
             if (decode && plan_lm_decode(r.pos0 + 1).splits > LM_MAX_SPLITS) return refuse("decode attention: plan");
             if (!decode && (N > 65535 || KVH > 65535)) return refuse("causal attention: sizes");
+            // the two causal kernels share a K / V read among 2 or 4 q heads (textenc.hip, lm.hip); no other layout is built
+            if (HQ != 2 * KVH && HQ != 4 * KVH) return refuse("causal attention: 2 or 4 q heads per kv head");
         } else {
             if (HQ % KVH != 0) return refuse("attention: Hq % Hkv");
         }

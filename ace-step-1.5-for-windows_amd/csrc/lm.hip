@@ -74,12 +74,12 @@ __global__ __launch_bounds__(64) void lm_set_first_kernel(FirstArgs a, int N, in
 }
 
 // ------------------------------------------------------------------------------------------------ decode attention
-// One query row per (sequence, q head): out[n][hq] = softmax_{first[n] <= j < len}(scale q[n][hq] . K[n][hq/2][j]) V[n][hq/2][j].
+// One query row per (sequence, q head): out[n][hq] = softmax_{first[n] <= j < len}(scale q[n][hq] . K[n][hq/G][j]) V[n][hq/G][j].
 //
-// Bound by the K / V bytes, so VALU dot products: a workgroup takes one (chunk of keys, kv head, sequence) and BOTH q heads of that kv
-// head, and reads every K / V row of its chunk once.  256 threads = 16 key groups x 16 lanes; a lane holds 8 of the 128 head dims
+// Bound by the K / V bytes, so VALU dot products: a workgroup takes one (chunk of keys, kv head, sequence) and ALL G q heads of that kv
+// head (G = 2, or 4 for Qwen3-4B's 32 / 8 layout), and reads every K / V row of its chunk once.  256 threads = 16 key groups x 16 lanes; a lane holds 8 of the 128 head dims
 // (one 16-byte load per row), a key group walks the chunk's keys kg, kg + 16, ... with its own online softmax (running max, row sum and
-// un-normalised O for both heads).  The 16 groups are then merged through LDS in group order, and the workgroup leaves un-normalised
+// un-normalised O for each head).  The 16 groups are then merged through LDS in group order, and the workgroup leaves un-normalised
 // fp32 O, the max and the row sum of its chunk; decode_merge_kernel combines a sequence's chunks in chunk order, as attn.hip's kv_split
 // merge does.  Keys outside [first, len) get -inf; a group or a chunk without a visible key carries max -inf / sum 0 and is skipped by
 // the merges, so no exponential is ever taken of -inf - -inf.
@@ -100,39 +100,43 @@ __device__ __forceinline__ void unpack8(uint4 v, float* f) {
     f[4] = bf_lo(v.z); f[5] = bf_hi(v.z); f[6] = bf_lo(v.w); f[7] = bf_hi(v.w);
 }
 
+template <int G>   // q heads per kv head: 2 or 4
 __global__ __launch_bounds__(256) void decode_attn_kernel(DecodeArgs a) {
-    constexpr int G = LM_DECODE_KEY_GROUPS;
-    __shared__ float go[G][2][128];
-    __shared__ float gm[2][G], gl[2][G];
+    constexpr int KG = LM_DECODE_KEY_GROUPS;
+    __shared__ float go[KG][G][128];
+    __shared__ float gm[G][KG], gl[G][KG];
     const int c = blockIdx.x, kvh = blockIdx.y, n = blockIdx.z;
     const int tid = threadIdx.x, kg = tid >> 4, dc = tid & 15;
     const int first = a.first[n];
     const int k_lo = c * a.chunk, k_hi = min(a.len, k_lo + a.chunk);
-    const int Hq = 2 * a.Hkv;
-    const long pbase = ((long)n * Hq + 2 * kvh) * LM_MAX_SPLITS + c;   // head 2 kvh; head 2 kvh + 1 is LM_MAX_SPLITS further on
+    const int Hq = G * a.Hkv;
+    const long pbase = ((long)n * Hq + G * kvh) * LM_MAX_SPLITS + c;   // head G kvh; head G kvh + h is h LM_MAX_SPLITS further on
 
-    float q[2][8];
+    float q[G][8];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) unpack8(ldg16(a.qkv + (long)n * a.ld + (2 * kvh + h) * 128 + dc * 8), q[h]);
-    float m[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f}, o[2][8];
+    for (int h = 0; h < G; ++h) unpack8(ldg16(a.qkv + (long)n * a.ld + (G * kvh + h) * 128 + dc * 8), q[h]);
+    float m[G], l[G], o[G][8];
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+    for (int h = 0; h < G; ++h) {
+        m[h] = -INFINITY;
+        l[h] = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[h][e] = 0.f;
+    }
 
     const bf16_t* kb = a.kc + n * a.seq_stride + (long)kvh * a.max_pos * 128 + dc * 8;
     const bf16_t* vb = a.vc + n * a.seq_stride + (long)kvh * a.max_pos * 128 + dc * 8;
     // rounds of 16 keys that hold a visible one (uniform over the workgroup; a skipped round would have changed nothing)
-    const int r_lo = first > k_lo ? (first - k_lo) / G : 0, r_hi = (k_hi - k_lo + G - 1) / G;
+    const int r_lo = first > k_lo ? (first - k_lo) / KG : 0, r_hi = (k_hi - k_lo + KG - 1) / KG;
     for (int r = r_lo; r < r_hi; ++r) {
-        const int key = k_lo + r * G + kg;
+        const int key = k_lo + r * KG + kg;
         const long row = (long)min(key, a.len - 1) * 128;   // (rows < len are written; a clamped key is masked)
         float kf[8], vf[8];
         unpack8(ldg16(kb + row), kf);
         unpack8(ldg16(vb + row), vf);
-        float s[2];
+        float s[G];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
+        for (int h = 0; h < G; ++h) {
             float d = 0.f;
 #pragma unroll
             for (int e = 0; e < 8; ++e) d += q[h][e] * kf[e];
@@ -142,7 +146,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DecodeArgs a) {
         }
         const bool visible = key >= first && key < k_hi;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
+        for (int h = 0; h < G; ++h) {
             const float sv = visible ? s[h] : -INFINITY;
             const float m_new = fmaxf(m[h], sv);
             const bool any = m_new > -INFINITY;
@@ -155,29 +159,33 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DecodeArgs a) {
         }
     }
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < G; ++h) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) go[kg][h][dc * 8 + e] = o[h][e];
         if (dc == 0) { gm[h][kg] = m[h]; gl[h][kg] = l[h]; }
     }
     __syncthreads();
-    // thread -> (head, dim): the 16 groups in group order
-    const int h = tid >> 7, d = tid & 127;
-    float M = -INFINITY;
+    // thread -> (head of a pair, dim); one pass per head pair, the 16 groups in group order
+    const int d = tid & 127;
 #pragma unroll
-    for (int g = 0; g < G; ++g) M = fmaxf(M, gm[h][g]);
-    float acc = 0.f, L = 0.f;
-    if (M > -INFINITY) {
+    for (int hp = 0; hp < G / 2; ++hp) {
+        const int h = 2 * hp + (tid >> 7);
+        float M = -INFINITY;
 #pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const float w = gm[h][g] > -INFINITY ? __builtin_amdgcn_exp2f(gm[h][g] - M) : 0.f;
-            acc += w * go[g][h][d];
-            L += w * gl[h][g];
+        for (int g = 0; g < KG; ++g) M = fmaxf(M, gm[h][g]);
+        float acc = 0.f, L = 0.f;
+        if (M > -INFINITY) {
+#pragma unroll
+            for (int g = 0; g < KG; ++g) {
+                const float w = gm[h][g] > -INFINITY ? __builtin_amdgcn_exp2f(gm[h][g] - M) : 0.f;
+                acc += w * go[g][h][d];
+                L += w * gl[h][g];
+            }
         }
+        const long p = pbase + (long)h * LM_MAX_SPLITS;
+        a.part_o[p * 128 + d] = acc;
+        if (d == 0) { a.part_ml[p * 2] = M; a.part_ml[p * 2 + 1] = L; }
     }
-    const long p = pbase + (long)h * LM_MAX_SPLITS;
-    a.part_o[p * 128 + d] = acc;
-    if (d == 0) { a.part_ml[p * 2] = M; a.part_ml[p * 2 + 1] = L; }
 }
 
 // out[n][hq][2t, 2t + 1] from the chunks' partials, in chunk order.  (Every sequence has a visible key - first < P <= len - so L > 0;
@@ -259,20 +267,22 @@ int ace355::launch_kv_store(const bf16_t* qkv, int ld, int k_col0, int v_col0, c
     return 0;
 }
 
-int ace355::launch_decode_attention(const bf16_t* qkv, int ld, const KvCache& c, int layer, int len, bf16_t* out, int N, int Hkv, float scale,
-                                    hipStream_t s) {
+int ace355::launch_decode_attention(const bf16_t* qkv, int ld, const KvCache& c, int layer, int len, bf16_t* out, int N, int Hq, int Hkv,
+                                    float scale, hipStream_t s) {
     ACE_CHECK(c.kv && c.first_dev && c.part_o && c.part_ml && N > 0 && N <= c.max_seqs && Hkv > 0 && len > 0 && len <= c.max_pos &&
                   layer >= 0, "decode attention: cache bounds");
     ACE_CHECK(ld % 8 == 0, "decode attention: 16-byte rows");
+    ACE_CHECK(Hq == 2 * Hkv || Hq == 4 * Hkv, "decode attention: 2 or 4 q heads per kv head");
     const LmDecodePlan p = plan_lm_decode(len);
     ACE_CHECK(p.splits >= 1 && p.splits <= LM_MAX_SPLITS && p.chunk % LM_DECODE_KEY_GROUPS == 0, "decode attention: plan");
     const long slab = c.slab(Hkv);
     const bf16_t* kc = c.kv + (long)layer * 2 * slab;
     DecodeArgs a{qkv, ld, kc, kc + slab, (long)Hkv * c.max_pos * 128, c.max_pos, c.first_dev, len, p.chunk, Hkv,
                  scale * 1.4426950408889634f, c.part_o, c.part_ml};
-    hipLaunchKernelGGL(decode_attn_kernel, dim3(p.splits, Hkv, N), dim3(256), 0, s, a);
+    if (Hq == 2 * Hkv) hipLaunchKernelGGL(decode_attn_kernel<2>, dim3(p.splits, Hkv, N), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(decode_attn_kernel<4>, dim3(p.splits, Hkv, N), dim3(256), 0, s, a);
     ACE_LAUNCH_CHECK();
-    hipLaunchKernelGGL(decode_merge_kernel, dim3(2 * Hkv, N), dim3(64), 0, s, c.part_o, c.part_ml, p.splits, out, 2 * Hkv * 128);
+    hipLaunchKernelGGL(decode_merge_kernel, dim3(Hq, N), dim3(64), 0, s, c.part_o, c.part_ml, p.splits, out, Hq * 128);
     ACE_LAUNCH_CHECK();
     return 0;
 }
@@ -453,10 +463,16 @@ int lm_step(ace355_lm* h, int rc, float* logits_dev, hipStream_t s) {
 
 extern "C" {
 
-int ace355_lm_create(const ace355_lm_config* cfg, ace355_lm** out) {
+int ace355_lm_create(const ace355_lm_config* cfg, ace355_lm** out) { return ace355_lm_create_ex(cfg, 0, out); }
+
+int ace355_lm_create_ex(const ace355_lm_config* cfg, uint32_t flags, ace355_lm** out) {
     ACE_CHECK(cfg && out, "lm_create: null argument");
-    if (cfg->head_dim != 128 || cfg->num_kv_heads <= 0 || cfg->num_heads != 2 * cfg->num_kv_heads) {
-        set_error("lm_create: only head_dim 128 with num_heads == 2 * num_kv_heads is supported");
+    ACE_CHECK((flags & ~(uint32_t)ACE355_LM_ALLOW_GQA4) == 0, "lm_create: unknown flag");
+    const bool gqa4 = (flags & ACE355_LM_ALLOW_GQA4) != 0;
+    if (cfg->head_dim != 128 || cfg->num_kv_heads <= 0 ||
+        !(cfg->num_heads == 2 * cfg->num_kv_heads || (gqa4 && cfg->num_heads == 4 * cfg->num_kv_heads))) {
+        set_error(gqa4 ? "lm_create: only head_dim 128 with num_heads == 2 * or 4 * num_kv_heads is supported"
+                       : "lm_create: only head_dim 128 with num_heads == 2 * num_kv_heads is supported");
         return ACE355_ERR_UNSUPPORTED;
     }
     ACE_CHECK(cfg->hidden_size > 0 && cfg->hidden_size % 256 == 0 && cfg->intermediate_size > 0 && cfg->intermediate_size % 64 == 0,

@@ -20,12 +20,15 @@ using namespace ace355;
 namespace {
 
 // ------------------------------------------------------------------------------------------------ causal GQA attention
-// out[n][s][hq*128 + d] = softmax_{j <= s}(scale q[n][s][hq] . k[n][j][hq/2]) v[n][j][hq/2], Hq = 2 Hkv, head dim 128.
+// out[n][s][hq*128 + d] = softmax_{j <= s}(scale q[n][s][hq] . k[n][j][hq/G]) v[n][j][hq/G], Hq = G Hkv with G = 2 (the text encoder, the
+// 0.6B / 1.7B LMs) or 4 (the 4B LM), head dim 128.
 // q / k / v are columns of the QKV GEMM's output rows (q and k in the head-pair dim order of PACK_ROWS_HEADPAIR - the dot product does
 // not see a common permutation of the head dims -, v in natural order, so `out` is in natural order).
 //
-// One workgroup = 64 query rows of ONE kv head and BOTH of its q heads (8 waves: wave w takes q head 2 kvh + (w >> 2), rows 16 (w & 3) ..
-// + 15), so a K / V tile of 64 keys is staged in LDS once for 128 query rows.  Key tiles wholly above the diagonal are never visited
+// One workgroup = 64 query rows of ONE q head pair hp (8 waves: wave w takes q head 2 hp + (w >> 2), rows 16 (w & 3) .. + 15) and the kv
+// head hp >> pair_shift both heads read, so a K / V tile of 64 keys is staged in LDS once for 128 query rows.  With G = 2 a pair is a kv
+// head (pair_shift 0); with G = 4 the two pairs of a kv head each stage its tiles: the kernel is bound by its MFMAs, not by K / V.
+// Key tiles wholly above the diagonal are never visited
 // (the query block and the key tile are both 64 wide: tiles 0 .. blockIdx.x); the per-element causal predicate runs on the diagonal tile
 // only, where masked scores are -inf, so their probabilities are exactly 0.  Reads past the sequence end are clamped to row S - 1 (real,
 // finite data whose probability is 0 for every stored row), rows >= S are not stored.  Everything else is fixed-order: bit-reproducible.
@@ -50,7 +53,7 @@ struct CausalArgs {
     int ld, k_col0, v_col0;
     bf16_t* out;        // rows n * S + s, row stride o_ld
     int o_ld;
-    int S, Hkv;
+    int S, pair_shift;  // kv head of q head pair hp = hp >> pair_shift
     float scale_log2;   // softmax scale * log2(e)
     const int* k_first; // FIRST only: [N]
 };
@@ -63,10 +66,10 @@ template <bool FIRST>
 __global__ __launch_bounds__(CA_THREADS) void causal_gqa_attn_kernel(CausalArgs a) {
     __shared__ __attribute__((aligned(16))) bf16_t Ks[CA_KB * CA_LDK];
     __shared__ __attribute__((aligned(16))) bf16_t Vt[128 * CA_LDV];
-    const int qb = blockIdx.x, kvh = blockIdx.y, n = blockIdx.z;
+    const int qb = blockIdx.x, kvh = (int)blockIdx.y >> a.pair_shift, n = blockIdx.z;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, c = l & 15, g = l >> 4;
     const int S = a.S;
-    const int hq = 2 * kvh + (w >> 2);
+    const int hq = 2 * blockIdx.y + (w >> 2);
     const int q_abs = qb * CA_QB + (w & 3) * 16 + c;   // this lane's query column
     const long row0 = (long)n * S;
 
@@ -190,12 +193,14 @@ __global__ __launch_bounds__(128) void embed_rows_kernel(const bf16_t* __restric
 
 }  // namespace
 
-int ace355::launch_causal_attention(const bf16_t* qkv, int ld, int k_col0, int v_col0, bf16_t* out, int o_ld, int N, int S, int Hkv, float scale,
-                                    hipStream_t s, const int* k_first_dev) {
+int ace355::launch_causal_attention(const bf16_t* qkv, int ld, int k_col0, int v_col0, bf16_t* out, int o_ld, int N, int S, int Hq, int Hkv,
+                                    float scale, hipStream_t s, const int* k_first_dev) {
     ACE_CHECK(N > 0 && S > 0 && Hkv > 0 && N <= 65535 && Hkv <= 65535, "causal attention: sizes");
+    ACE_CHECK(Hq == 2 * Hkv || Hq == 4 * Hkv, "causal attention: 2 or 4 q heads per kv head");
+    ACE_CHECK(Hq / 2 <= 65535, "causal attention: sizes");
     ACE_CHECK(ld % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0 && o_ld % 4 == 0, "causal attention: 16-byte rows");
-    CausalArgs a{qkv, ld, k_col0, v_col0, out, o_ld, S, Hkv, scale * 1.4426950408889634f, k_first_dev};
-    const dim3 grid((S + CA_QB - 1) / CA_QB, Hkv, N);
+    CausalArgs a{qkv, ld, k_col0, v_col0, out, o_ld, S, Hq == 4 * Hkv ? 1 : 0, scale * 1.4426950408889634f, k_first_dev};
+    const dim3 grid((S + CA_QB - 1) / CA_QB, Hq / 2, N);
     if (k_first_dev) hipLaunchKernelGGL(causal_gqa_attn_kernel<true>, grid, dim3(CA_THREADS), 0, s, a);
     else hipLaunchKernelGGL(causal_gqa_attn_kernel<false>, grid, dim3(CA_THREADS), 0, s, a);
     ACE_LAUNCH_CHECK();

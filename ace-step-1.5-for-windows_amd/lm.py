@@ -1,6 +1,6 @@
 """NativeCausalLM: Python owner of an ``ace355_lm`` handle - the forward of the reference's 5 Hz LM on the GPU.
 
-The LM is transformers' ``Qwen3ForCausalLM`` (0.6B / 1.7B).  The reference's CFG loop (``_generate_with_cfg_custom``,
+The LM is transformers' ``Qwen3ForCausalLM`` (0.6B / 1.7B; the 4B's 32 / 8 head layout with ``allow_gqa4=True``).  The reference's CFG loop (``_generate_with_cfg_custom``,
 llm_inference.py:2414-2533) calls it through ``LLMHandler._forward_pass`` (llm_inference.py:416-438) in two ways:
 
 * step 0: ``model(input_ids=ids[N, P], attention_mask=mask[N, P], use_cache=True)`` with left-padded rows (``0...0 1...1``);
@@ -74,7 +74,9 @@ class NativeCausalLM(native.Owner):
     _destroy = "ace355_lm_destroy"
 
     def __init__(self, cfg: LmConfig, device: Union[str, torch.device] = "cuda:0", max_positions: int = 8192,
-                 max_seqs: int = native.LM_MAX_SEQS, out_dtype: torch.dtype = torch.float32):
+                 max_seqs: int = native.LM_MAX_SEQS, out_dtype: torch.dtype = torch.float32, allow_gqa4: bool = False):
+        """``allow_gqa4``: also take four q heads per kv head (Qwen3-4B's 32 / 8 layout) - ``ace355_lm_create_ex`` with
+        ``ACE355_LM_ALLOW_GQA4``.  Without it the handle is created as ever and such a layout is ``NotImplementedError``."""
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -91,7 +93,10 @@ class NativeCausalLM(native.Owner):
                              1 if cfg.tie_word_embeddings else 0, self.max_seqs, self.max_positions)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            rc = self._lib.ace355_lm_create(C.byref(c), C.byref(h))
+            if allow_gqa4:
+                rc = self._lib.ace355_lm_create_ex(C.byref(c), native.LM_ALLOW_GQA4, C.byref(h))
+            else:
+                rc = self._lib.ace355_lm_create(C.byref(c), C.byref(h))
         if rc == 4:   # ACE355_ERR_UNSUPPORTED
             raise NotImplementedError(f"ace355: {native.last_error()}")
         native.check(rc, "lm_create")
@@ -99,11 +104,13 @@ class NativeCausalLM(native.Owner):
 
     @classmethod
     def from_reference(cls, module, device: Union[str, torch.device], out_dtype: torch.dtype = None,
-                       max_positions: int = 8192) -> "NativeCausalLM":
-        """Build from the loaded ``Qwen3ForCausalLM`` (``LLMHandler.llm``): its config and its state_dict.  Logits dtype: the module's."""
+                       max_positions: int = 8192, allow_gqa4: bool = False) -> "NativeCausalLM":
+        """Build from the loaded ``Qwen3ForCausalLM`` (``LLMHandler.llm``): its config and its state_dict.  Logits dtype: the module's.
+        ``allow_gqa4``: as in the constructor."""
         if out_dtype is None:
             out_dtype = next(module.parameters()).dtype
-        self = cls(LmConfig.from_reference(module.config), device, max_positions=max_positions, out_dtype=out_dtype)
+        self = cls(LmConfig.from_reference(module.config, allow_gqa4=allow_gqa4), device, max_positions=max_positions, out_dtype=out_dtype,
+                   allow_gqa4=allow_gqa4)
         self.load_state_dict(module.state_dict())
         return self
 

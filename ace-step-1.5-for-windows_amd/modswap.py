@@ -157,14 +157,15 @@ class NativeCausalLMSwap(NativeModuleSwap):
             return self._reference(input_ids=input_ids, attention_mask=attention_mask, **kwargs)
 
 
-def swap_in_lm(parent, device, attr: str = "llm", max_positions: int = 8192) -> NativeCausalLMSwap:
+def swap_in_lm(parent, device, attr: str = "llm", max_positions: int = 8192, allow_gqa4: bool = False) -> NativeCausalLMSwap:
     """``parent.<attr> = NativeCausalLMSwap(NativeCausalLM.from_reference(parent.<attr>), parent.<attr>)``; logits in the module's own
-    dtype.  Raises whatever ``from_reference`` raises (the caller logs and keeps the PyTorch module)."""
+    dtype.  ``allow_gqa4``: also take Qwen3-4B's 32 / 8 head layout (``NativeCausalLM``).  Raises whatever ``from_reference`` raises
+    (the caller logs and keeps the PyTorch module)."""
     from .lm import NativeCausalLM
     ref = getattr(parent, attr)
     if isinstance(ref, NativeModuleSwap):  # re-entry
         ref = ref._reference
-    wrapper = NativeCausalLMSwap(NativeCausalLM.from_reference(ref, device, max_positions=max_positions), ref, attr)
+    wrapper = NativeCausalLMSwap(NativeCausalLM.from_reference(ref, device, max_positions=max_positions, allow_gqa4=allow_gqa4), ref, attr)
     setattr(parent, attr, wrapper)
     return wrapper
 

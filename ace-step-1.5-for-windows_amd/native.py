@@ -83,6 +83,7 @@ class LmShapeParamsC(C.Structure):
                 ("temperature", C.c_float), ("penalty", C.c_float), ("mask", C.c_void_p), ("seen", C.c_void_p)]
 
 
+LM_ALLOW_GQA4 = 1   # ACE355_LM_ALLOW_GQA4: ace355_lm_create_ex takes num_heads == 4 * num_kv_heads too
 LM_EOS_NONE, LM_EOS_BLOCK, LM_EOS_FORCE = 0, 1, 2   # ace355_lm_shape_params.eos_mode
 
 
@@ -208,7 +209,8 @@ ENC_STEPS = ("rmsnorm", "gemm", "kv_store", "causal_attn", "decode_attn", "trans
 ENC_PROJS = ("qkv", "o", "gate_up", "down")
 ENC_NORMS = ("input", "post_attention", "final")
 ENC_BUFS = {-1: None, 0: "h", 1: "xn", 2: "qkv", 3: "ao", 4: "act", 5: "vt", 6: "vmean", 7: "cache", 8: "out"}
-# the fields of a step that each kind's launcher takes
+# the fields of a step that each kind's launcher takes.  (The two causal launchers also take the step's Hq, 2 or 4 x Hkv; it is the
+# request's num_heads and is left out here so that the recorded plan tables keep their hashes.)
 ENC_STEP_FIELDS = {
     "rmsnorm": ("M", "N", "norm", "rows_per_seq"),
     "gemm": ("M", "N", "K", "proj", "lda", "ldw", "ldc", "mode", "rows_per_seq", "hn_q_cols", "hn_qk_cols", "rope_row0", "sk_cnt", "flops"),
@@ -387,6 +389,7 @@ SIGNATURES = {
     "ace355_textenc_encode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ace355_textenc_embed": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64, C.c_void_p, C.c_void_p]),
     "ace355_lm_create": (C.c_int, [C.POINTER(LmConfigC), C.POINTER(C.c_void_p)]),
+    "ace355_lm_create_ex": (C.c_int, [C.POINTER(LmConfigC), C.c_uint32, C.POINTER(C.c_void_p)]),
     "ace355_lm_destroy": (None, [C.c_void_p]),
     "ace355_lm_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int64, C.c_int]),
     "ace355_lm_finalize": (C.c_int, [C.c_void_p]),

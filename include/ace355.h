@@ -821,8 +821,15 @@ typedef struct ace355_lm_config {
     int32_t max_positions;      /* 1 .. ACE355_LM_MAX_POSITIONS: prompt + generated tokens */
 } ace355_lm_config;
 
-/* ACE355_ERR_UNSUPPORTED for head_dim != 128 or num_heads != 2 * num_kv_heads (Qwen3-4B, 32 / 8 heads, stays on PyTorch). */
+/* ACE355_ERR_UNSUPPORTED for head_dim != 128 or num_heads != 2 * num_kv_heads (Qwen3-4B, 32 / 8 heads, needs ace355_lm_create_ex).
+ * The same as ace355_lm_create_ex(cfg, 0, out). */
 int ace355_lm_create(const ace355_lm_config* cfg, ace355_lm** out);
+/* The config struct is frozen, so what a caller opts into travels beside it.  ACE355_LM_ALLOW_GQA4: num_heads == 4 * num_kv_heads is
+ * accepted next to 2 * (Qwen3-4B: hidden 2560, intermediate 9728, 36 layers, 32 / 8 heads of 128).  Every call on such a handle is
+ * the one documented below; the 2 : 1 kernels' operations and their order are unchanged.  ACE355_ERR_UNSUPPORTED for every other
+ * ratio and for head_dim != 128, ACE355_ERR_INVALID for an unknown flag bit. */
+#define ACE355_LM_ALLOW_GQA4 1u
+int ace355_lm_create_ex(const ace355_lm_config* cfg, uint32_t flags, ace355_lm** out);
 void ace355_lm_destroy(ace355_lm* h);
 /* name = a key of Qwen3ForCausalLM.state_dict(): "model.embed_tokens.weight", "model.layers.<i>.*", "model.norm.weight",
  * "lm_head.weight".  Same contract as ace355_dit_load_tensor. */

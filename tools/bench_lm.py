@@ -12,7 +12,11 @@ covers lengths length .. length + runs.  No hipGraph on either side.
 The byte floor of a decode step is what it must read once: every layer's weights and the head (bf16), plus the K / V rows of the
 cache, N x kv heads x length x 128 x 2 x 2 bytes per layer, over the chip's measured HBM copy bandwidth (6.3 TB/s; 8.0 TB/s on paper).
 
-Usage:  python tools/bench_lm.py [--runs 20] [--out profiles/lm_step_bench.txt]
+--model 4b: the Qwen3-4B shape (36 layers, hidden 2560, intermediate 9728, 32 / 8 heads, tied head, the same vocabulary) on a handle
+created with ``allow_gqa4=True`` -> profiles/lm_gqa4_bench.txt.  The PyTorch side is then built on the GPU in bf16 (an fp32 host copy
+of 4 B parameters beside the weights' own would be 32 GB).
+
+Usage:  python tools/bench_lm.py [--model {0.6b,4b}] [--runs 20] [--out profiles/lm_step_bench.txt]
 """
 from __future__ import annotations
 
@@ -27,13 +31,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import ace355  # noqa: E402,F401
-from ace355 import weightgen  # noqa: E402
+from ace355 import native, weightgen  # noqa: E402
 from ace355.config import LmConfig  # noqa: E402
 from ace355.lm import NativeCausalLM  # noqa: E402
 
 SHAPES = [(2, 512), (2, 2048), (16, 512), (16, 2048)]
 HBM_BYTES_PER_S = 6.3e12
 PADS = 64
+VOCAB = 151669 + 65536
+MODELS = {"0.6b": dict(name="Qwen3-0.6B", cfg=dict(), out="lm_step_bench.txt"),
+          "4b": dict(name="Qwen3-4B", cfg=dict(hidden_size=2560, intermediate_size=9728, num_hidden_layers=36, num_attention_heads=32,
+                                               num_key_value_heads=8), out="lm_gqa4_bench.txt")}
 
 
 def timed(fn):
@@ -45,7 +53,7 @@ def timed(fn):
     return a.elapsed_time(b)
 
 
-def hf_model(cfg, w, dev):
+def hf_model(cfg, w, dev, on_device=False):
     try:
         import transformers
         from transformers import Qwen3Config, Qwen3ForCausalLM
@@ -56,7 +64,16 @@ def hf_model(cfg, w, dev):
                     num_key_value_heads=cfg.num_key_value_heads, head_dim=cfg.head_dim, rms_norm_eps=cfg.rms_norm_eps,
                     rope_theta=cfg.rope_theta, max_position_embeddings=32768, use_sliding_window=False,
                     tie_word_embeddings=cfg.tie_word_embeddings)
-    m = Qwen3ForCausalLM(c)
+    if on_device:
+        dtype = torch.get_default_dtype()
+        torch.set_default_dtype(torch.bfloat16)
+        try:
+            with torch.device(dev):
+                m = Qwen3ForCausalLM(c)
+        finally:
+            torch.set_default_dtype(dtype)
+    else:
+        m = Qwen3ForCausalLM(c)
     m.load_state_dict(w, strict=False)
     if cfg.tie_word_embeddings:
         m.tie_weights()
@@ -68,6 +85,14 @@ def step_floor_bytes(cfg, N, length):
     layer_w = 2 * ((QD + 2 * KVD) * D + D * QD + 2 * F * D + D * F)
     kv = N * cfg.num_key_value_heads * length * 128 * 2 * 2
     return cfg.num_hidden_layers * (layer_w + kv) + 2 * cfg.vocab_size * D
+
+
+def step_launches(cfg, N, length):
+    """Kernel launches of one native decode step: the pass plan's calls (the decode attention is two kernels, the cut and its merge),
+    the embedding gather ahead of the stack and the LM head behind it."""
+    p = native.encoder_pass_plan(cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_key_value_heads,
+                                 cfg.num_hidden_layers, N, 1, causal=1, has_cache=1, pos0=length - 1, max_pos=length, max_seqs=N, has_first=1)
+    return sum(p["calls"].values()) + p["calls"]["decode_attn"] + 2
 
 
 def stats(xs):
@@ -84,21 +109,31 @@ def main():
     ap.add_argument("--runs", type=int, default=20, help="decode steps timed per side and shape")
     ap.add_argument("--prefill-runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lm_step_bench.txt"))
+    ap.add_argument("--model", choices=sorted(MODELS), default="0.6b")
+    ap.add_argument("--out", default=None, help="default: profiles/lm_step_bench.txt (0.6b), profiles/lm_gqa4_bench.txt (4b)")
+    ap.add_argument("--no-pytorch", action="store_true", help="time the native side alone")
     args = ap.parse_args()
+    model = MODELS[args.model]
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", model["out"])
     dev = torch.device("cuda:0")
-    cfg = LmConfig(vocab_size=151669 + 65536, tie_word_embeddings=True)
+    cfg = LmConfig(vocab_size=VOCAB, tie_word_embeddings=True, **model["cfg"])
+    gqa4 = cfg.num_attention_heads == 4 * cfg.num_key_value_heads
     w = weightgen.make_dit_weights(cfg.weight_shapes(), cfg.hidden_size, seed=0, mode="test")
-    nat = NativeCausalLM(cfg, dev, max_positions=max(L for _n, L in SHAPES) + args.runs + args.warmup + 8, out_dtype=torch.bfloat16)
+    opt_in = {"allow_gqa4": True} if gqa4 else {}
+    nat = NativeCausalLM(cfg, dev, max_positions=max(L for _n, L in SHAPES) + args.runs + args.warmup + 8, out_dtype=torch.bfloat16, **opt_in)
     nat.load_state_dict(w)
-    ref, note = hf_model(cfg, w, dev)
+    ref, note = (None, "PyTorch side not run (--no-pytorch)") if args.no_pytorch else hf_model(cfg, w, dev, on_device=gqa4)
     del w
     g = torch.Generator().manual_seed(0)
-    lines = [f"# native LM forward vs PyTorch, Qwen3-0.6B shape ({cfg.num_hidden_layers} layers, hidden {cfg.hidden_size}, vocabulary "
+    lines = [f"# native LM forward vs PyTorch, {model['name']} shape ({cfg.num_hidden_layers} layers, hidden {cfg.hidden_size}, vocabulary "
              f"{cfg.vocab_size}, tied head), {torch.cuda.get_device_name(dev)}", f"# {note}",
              f"# {args.warmup} warm-up calls per side, then interleaved runs ({args.prefill_runs} prefills, {args.runs} decode steps); "
              "ms per call: median [min - max]",
              f"# byte floor of a decode step: layer weights + head + K / V rows read once, over {HBM_BYTES_PER_S / 1e12:.1f} TB/s",
+             *([f"# {cfg.num_attention_heads} / {cfg.num_key_value_heads} heads: 4 q heads per kv head (allow_gqa4); kernel launches per "
+                f"native decode step: {step_launches(cfg, 16, 2048)} (per layer 2 norms, 4 GEMMs, K / V store, decode attention + merge; "
+                "embedding gather, final norm, LM head)"] if gqa4 else []),
              f"{'call':<26} {'native ms':>26} {'pytorch ms':>26} {'pytorch / native':>17} {'floor ms':>9} {'floor MB':>9}"]
     slower = []
     with torch.inference_mode():
