@@ -38,6 +38,7 @@ _ALIGN_POST_ENV = os.environ.get("ACE355_ALIGN_POST", "") == "1"   # read once: 
 _LM_SAMPLER_ENV = os.environ.get("ACE355_LM_SAMPLER", "") == "1"   # read once: the default of NativeLmMixin.use_native_lm_sampler
 _LM_LOOP_ENV = os.environ.get("ACE355_LM_LOOP", "") == "1"         # read once: the default of NativeLmMixin.use_native_lm_loop
 _LM_BATCH_ENV = os.environ.get("ACE355_LM_BATCH", "") == "1"       # read once: the default of NativeLmMixin.use_native_lm_batch
+_LM_NOCFG_ENV = os.environ.get("ACE355_LM_NOCFG", "") == "1"       # read once: the default of NativeLmMixin.use_native_lm_nocfg
 _LM_SCORE_ENV = os.environ.get("ACE355_LM_SCORE", "") == "1"       # read once: the default of NativeLmMixin.use_native_lm_score
 _LM_GQA4_ENV = os.environ.get("ACE355_LM_GQA4", "") == "1"         # read once: the default of NativeLmMixin.use_native_lm_gqa4
 _AUDIO_IN_ENV = os.environ.get("ACE355_AUDIO_IN", "") == "1"       # read once: the default of NativeAudioInMixin.use_native_audio_in
@@ -598,10 +599,11 @@ class NativeLmMixin:
             return None, None
         return self._lm_loop_accepts(batch_input_ids, batch_attention_mask, max_new_tokens)
 
-    def _lm_loop_accepts(self, batch_input_ids, batch_attention_mask, max_new_tokens):
-        """``_lm_loop_native`` whatever ``use_native_lm_loop`` says (the batched path below implies the native loop)."""
+    def _lm_loop_accepts(self, batch_input_ids, batch_attention_mask, max_new_tokens, pairs=True):
+        """``_lm_loop_native`` whatever ``use_native_lm_loop`` says (the batched path below implies the native loop).  ``pairs``
+        False: the rows are N = B >= 1 prompts of the non-CFG loop, not conditional + unconditional ones."""
         if not isinstance(batch_input_ids, torch.Tensor) or not batch_input_ids.is_cuda or batch_input_ids.dim() != 2:
-            return None, "the input ids are not a [2B, P] tensor on a CUDA device"
+            return None, f"the input ids are not a [{'2B' if pairs else 'B'}, P] tensor on a CUDA device"
         from . import lm as _lm, modswap, native
         llm = modswap.native_of(getattr(self, "llm", None))
         if not isinstance(llm, _lm.NativeCausalLM):
@@ -609,8 +611,10 @@ class NativeLmMixin:
         if batch_input_ids.device != llm.device:
             return None, f"the input ids are on {batch_input_ids.device}, the native LM on {llm.device}"
         N, P = batch_input_ids.shape
-        if N < 2 or N % 2 or P < 1:
+        if pairs and (N < 2 or N % 2 or P < 1):
             return None, f"{N} x {P} input ids are not conditional + unconditional rows"
+        if N < 1 or P < 1:
+            return None, f"{N} x {P} input ids hold no prompt"
         if N > llm.max_seqs or P + int(max_new_tokens) > llm.max_positions or N * P > native.LM_MAX_TOKENS:
             return None, (f"{N} sequences of {P} + {int(max_new_tokens)} positions exceed the native handle ({llm.max_seqs} sequences, "
                           f"{llm.max_positions} positions, {native.LM_MAX_TOKENS} prefill tokens)")
@@ -706,6 +710,22 @@ class NativeLmMixin:
                 skip_genres=skip_genres, skip_caption=skip_caption, skip_language=skip_language, generation_phase=generation_phase,
                 caption=caption, lyrics=lyrics, cot_text=cot_text, seeds=seeds)
 
+        if self.use_native_lm_nocfg and not cfg_scale > 1.0:   # (a CFG request is none of this flag's)
+            from .lmlogits import nocfg_batch_request
+            ok, why = nocfg_batch_request(formatted_prompts, cfg_scale, generation_phase, use_constrained_decoding, target_duration, seeds)
+            texts = None
+            if not ok:
+                if isinstance(formatted_prompts, list) and len(formatted_prompts) > 1:   # a single prompt is no batch: nothing to say
+                    self._lm_nocfg_skip(why, "this request runs item by item")
+            else:
+                try:
+                    texts = self._run_pt_batch_nocfg(formatted_prompts[0], len(formatted_prompts), seeds, temperature, cfg_scale, top_k,
+                                                     top_p, repetition_penalty, use_constrained_decoding, constrained_decoding_debug,
+                                                     target_duration, generation_phase)
+                except Exception as exc:
+                    logger.warning("[native-lm-nocfg] %s: %s; this request runs item by item", type(exc).__name__, exc)
+            if texts is not None:
+                return texts
         if not self.use_native_lm_batch:
             return sequential()
         from .lmlogits import batch_request
@@ -721,6 +741,78 @@ class NativeLmMixin:
             logger.warning("[native-lm-batch] %s: %s; this request runs item by item", type(exc).__name__, exc)
             texts = None
         return texts if texts is not None else sequential()
+
+    # ------------------------------------------------------------------ the loop without CFG (opt-in)
+    # The other half of ``_run_pt_single`` (llm_inference.py:929-942): with ``cfg_scale <= 1`` and constrained decoding it calls
+    # ``_generate_with_constrained_decoding`` (:2321-2412) - every "understand"-phase request (understand_audio_from_codes,
+    # create_sample_from_query, format_sample_from_input) and every codes request at lm_cfg_scale 1.0.  With ``use_native_lm_nocfg``
+    # (ACE355_LM_NOCFG=1 for every host) that method is ace355.lmlogits.generate_constrained: the loop above with B sequences and no
+    # unconditional rows, its stage in the model's dtype because that loop never upcasts (include/ace355.h, ace355_lm_shape_as).  A
+    # ``_run_pt`` batch of one prompt with B seeds and ``cfg_scale <= 1`` runs as generate_codes_batch_nocfg, up to max_seqs songs
+    # per loop.  The flag implies the native selection for these calls whatever the other flags say: the distribution is the
+    # reference's, the draw for a seed is ace355.lmsample's.  Goes to the host's own method, the reason logged once per handler
+    # (``[native-lm-nocfg] ...``): whatever ``_lm_loop_accepts`` refuses (not the native swap, ids not on the GPU, not left-padded,
+    # B > max_seqs, P + max_new_tokens > max_positions, ...), and an fp16 ``out_dtype``.  The metadata FSM stays the reference's
+    # code (run on the native forward's logits in the model's dtype), and ``llm.generate()`` without constrained decoding stays on
+    # the kept module.
+    use_native_lm_nocfg: bool = _LM_NOCFG_ENV
+    _lm_nocfg_reasons_logged = frozenset()
+
+    def _lm_nocfg_skip(self, why, then="this request runs the reference's loop"):
+        if why not in self._lm_nocfg_reasons_logged:   # once per reason and handler
+            self._lm_nocfg_reasons_logged = self._lm_nocfg_reasons_logged | {why}
+            logger.info("[native-lm-nocfg] %s; %s", why, then)
+
+    def _lm_nocfg_accepts(self, input_ids, attention_mask, max_new_tokens):
+        """``_lm_loop_accepts`` for B >= 1 rows without unconditional ones, plus the dtypes the stage runs in."""
+        llm, why = self._lm_loop_accepts(input_ids, attention_mask, max_new_tokens, pairs=False)
+        if llm is not None and llm.out_dtype not in (torch.float32, torch.bfloat16):
+            return None, f"the native LM's out_dtype {llm.out_dtype} is neither fp32 nor bf16"
+        return llm, why
+
+    def _generate_with_constrained_decoding(self, input_ids, attention_mask, max_new_tokens, temperature, top_k, top_p,
+                                            repetition_penalty, pad_token_id, streamer, constrained_processor=None):
+        llm = None
+        if self.use_native_lm_nocfg:
+            llm, why = self._lm_nocfg_accepts(input_ids, attention_mask, max_new_tokens)
+            if llm is None:
+                self._lm_nocfg_skip(why)
+        if llm is None:
+            return super()._generate_with_constrained_decoding(input_ids, attention_mask, max_new_tokens, temperature, top_k, top_p,
+                                                               repetition_penalty, pad_token_id, streamer, constrained_processor)
+        from .lmlogits import generate_constrained
+        return generate_constrained(self, llm, input_ids, attention_mask, max_new_tokens, temperature, top_k, top_p, repetition_penalty,
+                                    pad_token_id, streamer, constrained_processor)
+
+    def _run_pt_batch_nocfg(self, prompt, n_items, seeds, temperature, cfg_scale, top_k, top_p, repetition_penalty,
+                            use_constrained_decoding, constrained_decoding_debug, target_duration, generation_phase):
+        """``_run_pt_batch`` for the non-CFG branch of ``_run_pt_single``: one row, ``padding=False`` (llm_inference.py:889-894)."""
+        from .lmlogits import generate_codes_batch_nocfg, nocfg_batch_request
+        tok = self.llm_tokenizer
+        texts = []
+        with self._load_model_context():
+            max_new_tokens = self._compute_max_new_tokens(target_duration=target_duration, generation_phase=generation_phase,
+                                                          fallback_max=getattr(getattr(self.llm, "config", None), "max_new_tokens", 4096))
+            one = tok(prompt, return_tensors="pt", padding=False, truncation=True)
+            one = {k: v.to(self.device) for k, v in one.items()}
+            ids, mask = one["input_ids"], one.get("attention_mask", None)
+            llm, why = self._lm_nocfg_accepts(ids, mask, max_new_tokens)
+            ok, why = nocfg_batch_request([prompt] * n_items, cfg_scale, generation_phase, use_constrained_decoding, target_duration, seeds,
+                                          loop_refusal=why if llm is None else None)
+            if not ok:
+                self._lm_nocfg_skip(why, "this request runs item by item")
+                return None
+            group = max(llm.max_seqs, 1)
+            for i0 in range(0, n_items, group):
+                proc = self._setup_constrained_processor(
+                    use_constrained_decoding=use_constrained_decoding, constrained_decoding_debug=constrained_decoding_debug,
+                    target_duration=target_duration, user_metadata=None, stop_at_reasoning=False, skip_genres=True, skip_caption=True,
+                    skip_language=True, generation_phase=generation_phase, is_batch=False)
+                out = generate_codes_batch_nocfg(self, llm, ids, mask, list(seeds[i0:min(i0 + group, n_items)]), max_new_tokens,
+                                                 temperature, top_k, top_p, repetition_penalty, tok.pad_token_id or tok.eos_token_id, proc)
+                new = out[:, ids.shape[1]:].cpu()
+                texts += [tok.decode(row, skip_special_tokens=False) for row in new]
+        return texts
 
 
 class NativeAudioInMixin:

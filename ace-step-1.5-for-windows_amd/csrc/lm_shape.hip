@@ -9,6 +9,10 @@
 // __f*_rn intrinsics are inlined from a header that allows contraction, so the pragma does not reach them), so it carries the bits of
 // the reference's chain of separate torch kernels.  A row is cut by lm_plan.h's plan_lm_pick(V) like the selection that follows; the cut cannot change
 // a bit.  No LDS, no scratch, no floating-point atomics; ace355_lm_seen_mark's integer atomicOr commutes.
+//
+// ace355_lm_shape_as is the same launch in the model's dtype: the reference's non-CFG loop (llm_inference.py:2369-2377) never upcasts,
+// so on a bf16 model every one of its torch kernels rounds its result to bf16.  The kernel is templated on the dtype; the BF16
+// instantiation rounds where torch rounds (bf16_rne below, an integer operation on the bit pattern), the F32 one is the code as it was.
 #include <math.h>
 
 #include <string>
@@ -39,7 +43,26 @@ struct ShapeArgs {
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// round-to-nearest-even of an fp32 value to bf16, kept in fp32: +-inf and +-0 stay, subnormals round like any value, a finite value
+// past bf16's largest becomes inf, a NaN stays a (quiet) NaN
+__device__ __forceinline__ float bf16_rne(float x) {
+    uint32_t b = __float_as_uint(x);
+    if ((b & 0x7fffffffu) > 0x7f800000u) return __uint_as_float((b & 0x80000000u) | 0x7fc00000u);
+    b += 0x7fffu + ((b >> 16) & 1u);
+    return __uint_as_float(b & 0xffff0000u);
+}
+
+template <int DT>
 __device__ __forceinline__ float shape_one(const ShapeArgs& a, float c, float u, float m, uint32_t seen_word, int v) {
+    if constexpr (DT == ACE355_DTYPE_BF16) {   // no CFG below fp32 (refused on the host): c -> bf16, then every result -> bf16
+        float x = bf16_rne(c);
+        if (a.mask) x = bf16_rne(x + bf16_rne(m));
+        if (a.eos_mode == 1 && v == a.eos_id) x = -INFINITY;
+        if (a.eos_mode == 2 && v != a.eos_id) x = -INFINITY;
+        if (a.has_temperature) x = bf16_rne(x / a.temperature);
+        if (a.use_penalty && ((seen_word >> (v & 31)) & 1u)) x = x < 0.f ? bf16_rne(x * a.penalty) : bf16_rne(x / a.penalty);
+        return x;
+    }
     float x = c;
     if (a.uncond) {
         const float d = c - u;
@@ -54,13 +77,15 @@ __device__ __forceinline__ float shape_one(const ShapeArgs& a, float c, float u,
     return x;
 }
 
+template <int DT>
 __device__ __forceinline__ void shape_scalar(const ShapeArgs& a, const float* c, const float* u, float* o, const uint32_t* seen, int v) {
-    o[v] = shape_one(a, c[v], u ? u[v] : 0.f, a.mask ? a.mask[v] : 0.f, seen ? seen[v >> 5] : 0u, v);
+    o[v] = shape_one<DT>(a, c[v], u ? u[v] : 0.f, a.mask ? a.mask[v] : 0.f, seen ? seen[v >> 5] : 0u, v);
 }
 
 // grid (chunks, B).  Row b: the ids before `out`'s first 16-byte boundary (head, < 4) and those after the last whole group of four
 // (tail, < 4) go one by one; the groups in between, each owned by the chunk that holds its first id, are 16-byte stores and 16-byte
 // loads.  Every id is written exactly once, by the thread that read it, so `out` may be `cond`.
+template <int DT>
 __global__ __launch_bounds__(256) void lm_shape_kernel(ShapeArgs a) {
     const int b = blockIdx.y, V = a.V;
     const float* c = a.cond + (long)b * a.cond_stride;
@@ -71,9 +96,9 @@ __global__ __launch_bounds__(256) void lm_shape_kernel(ShapeArgs a) {
     const int groups = (V - head) >> 2;
     const int lo = blockIdx.x * a.chunk, hi = min(V, lo + a.chunk);
 
-    if (blockIdx.x == 0 && (int)threadIdx.x < head) shape_scalar(a, c, u, o, seen, threadIdx.x);
+    if (blockIdx.x == 0 && (int)threadIdx.x < head) shape_scalar<DT>(a, c, u, o, seen, threadIdx.x);
     const int tail0 = head + 4 * groups;
-    if (blockIdx.x == gridDim.x - 1 && (int)threadIdx.x < V - tail0) shape_scalar(a, c, u, o, seen, tail0 + threadIdx.x);
+    if (blockIdx.x == gridDim.x - 1 && (int)threadIdx.x < V - tail0) shape_scalar<DT>(a, c, u, o, seen, tail0 + threadIdx.x);
 
     // groups g with lo <= head + 4 g < hi
     const int g_lo = lo <= head ? 0 : (lo - head + 3) >> 2;
@@ -88,7 +113,7 @@ __global__ __launch_bounds__(256) void lm_shape_kernel(ShapeArgs a) {
         if (seen) { w0 = seen[v0 >> 5]; w1 = seen[(v0 + 3) >> 5]; }
         f32x4 r;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) r[e] = shape_one(a, cv[e], uv[e], mv[e], ((v0 + e) >> 5) == (v0 >> 5) ? w0 : w1, v0 + e);
+        for (int e = 0; e < 4; ++e) r[e] = shape_one<DT>(a, cv[e], uv[e], mv[e], ((v0 + e) >> 5) == (v0 >> 5) ? w0 : w1, v0 + e);
         *reinterpret_cast<f32x4*>(o + v0) = r;
     }
 }
@@ -108,13 +133,11 @@ int refuse(const char* who, const std::string& msg) {
     return ACE355_ERR_INVALID;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ace355_lm_shape(const float* cond_dev, int64_t cond_stride, const float* uncond_dev, int64_t uncond_stride, float* out_dev,
-                    int64_t out_stride, int B, int V, const ace355_lm_shape_params* p, void* stream) {
-    static const char* who = "lm_shape";
+// the checks and the launch behind ace355_lm_shape (dtype F32) and ace355_lm_shape_as
+int launch_shape(const char* who, const float* cond_dev, int64_t cond_stride, const float* uncond_dev, int64_t uncond_stride,
+                 float* out_dev, int64_t out_stride, int B, int V, const ace355_lm_shape_params* p, int dtype, void* stream) {
+    if (dtype != ACE355_DTYPE_F32 && dtype != ACE355_DTYPE_BF16) return refuse(who, "dtype must be ACE355_DTYPE_F32 or ACE355_DTYPE_BF16");
+    if (uncond_dev && dtype != ACE355_DTYPE_F32) return refuse(who, "uncond (the CFG combine) is taken in fp32 only");
     if (B < 1 || B > ACE355_LM_MAX_SEQS) return refuse(who, "B must be 1 .. " + std::to_string(ACE355_LM_MAX_SEQS));
     if (V < 1 || V > LM_PICK_MAX_V) return refuse(who, "V must be 1 .. " + std::to_string(LM_PICK_MAX_V));
     if (!cond_dev || !out_dev || !p) return refuse(who, "cond, out and params must not be null");
@@ -137,9 +160,26 @@ int ace355_lm_shape(const float* cond_dev, int64_t cond_stride, const float* unc
     a.eos_id = p->eos_id; a.eos_mode = p->eos_mode;
     a.has_temperature = p->has_temperature != 0;
     a.cfg_scale = p->cfg_scale; a.temperature = p->temperature; a.penalty = p->penalty;
-    hipLaunchKernelGGL(lm_shape_kernel, dim3(plan.chunks, B), dim3(256), 0, (hipStream_t)stream, a);
+    if (dtype == ACE355_DTYPE_BF16)
+        hipLaunchKernelGGL(lm_shape_kernel<ACE355_DTYPE_BF16>, dim3(plan.chunks, B), dim3(256), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(lm_shape_kernel<ACE355_DTYPE_F32>, dim3(plan.chunks, B), dim3(256), 0, (hipStream_t)stream, a);
     ACE_LAUNCH_CHECK();
     return ACE355_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ace355_lm_shape(const float* cond_dev, int64_t cond_stride, const float* uncond_dev, int64_t uncond_stride, float* out_dev,
+                    int64_t out_stride, int B, int V, const ace355_lm_shape_params* p, void* stream) {
+    return launch_shape("lm_shape", cond_dev, cond_stride, uncond_dev, uncond_stride, out_dev, out_stride, B, V, p, ACE355_DTYPE_F32, stream);
+}
+
+int ace355_lm_shape_as(const float* cond_dev, int64_t cond_stride, const float* uncond_dev, int64_t uncond_stride, float* out_dev,
+                       int64_t out_stride, int B, int V, const ace355_lm_shape_params* p, int dtype, void* stream) {
+    return launch_shape("lm_shape_as", cond_dev, cond_stride, uncond_dev, uncond_stride, out_dev, out_stride, B, V, p, dtype, stream);
 }
 
 int ace355_lm_seen_mark(const int64_t* ids_dev, int64_t row_stride, int B, int T, int V, uint32_t* seen_dev, void* stream) {

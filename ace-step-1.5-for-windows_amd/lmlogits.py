@@ -11,7 +11,10 @@ transformers' ``RepetitionPenaltyLogitsProcessor``; then ``_update_constrained_p
 * ``generate_with_cfg`` is the loop (``NativeLmMixin._generate_with_cfg_custom`` calls it when ``use_native_lm_loop`` is set);
 * ``generate_codes_batch`` is that loop for B songs that share one prompt, each with the tokens the loop gives it alone, and
   ``batch_request`` decides which ``_run_pt`` calls are such batches (``NativeLmMixin._run_pt``, ``use_native_lm_batch``);
-* ``_cfg_loop`` is the one loop behind both: each of the two builds a ``_LoopMode`` and formats what the loop returns.
+* ``_cfg_loop`` is the one loop behind both: each of the two builds a ``_LoopMode`` and formats what the loop returns;
+* ``generate_constrained`` and ``generate_codes_batch_nocfg`` are that loop without CFG (``_LoopMode.cfg`` False: the reference's
+  ``_generate_with_constrained_decoding``, stage in the model's dtype), ``nocfg_batch_request`` is ``batch_request`` for them
+  (``NativeLmMixin._generate_with_constrained_decoding`` / ``_run_pt``, ``use_native_lm_nocfg``).
 
 The native stage covers the processor's branches that are a fixed mask plus one EOS rule: no processor, a disabled one, ``COMPLETED``
 and ``CODES_GENERATION``.  Every other FSM state runs the reference's own torch code on the native forward's logits, as before.
@@ -66,10 +69,17 @@ class SeenTokens:
 
 def shape_logits(cond: torch.Tensor, uncond: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, mask: Optional[torch.Tensor] = None,
                  eos_id: Optional[int] = None, eos_mode: int = native.LM_EOS_NONE, temperature: Optional[float] = None,
-                 penalty: float = 1.0, seen: Optional[SeenTokens] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 penalty: float = 1.0, seen: Optional[SeenTokens] = None, out: Optional[torch.Tensor] = None,
+                 dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """The logits stage on ``cond`` / ``uncond`` (fp32 ``[B, V]`` on the GPU, rows may be strided, B <= 16; ``uncond=None``: no CFG):
     CFG combine, ``+ mask``, the EOS rule, ``/ temperature`` (``None``: skipped; ``<= 0``: 1e-6, as the reference), repetition penalty
-    on the ids ``seen`` holds.  One launch on the current stream.  Returns ``out`` (default: a new ``[B, V]``; may be ``cond``)."""
+    on the ids ``seen`` holds.  One launch on the current stream.  Returns ``out`` (default: a new ``[B, V]``; may be ``cond``).
+    ``dtype`` None or ``torch.float32``: every operation rounds to fp32 (``ace355_lm_shape``).  ``torch.bfloat16``: the logits and every
+    result round to bf16, as torch rounds them on a bf16 tensor (``ace355_lm_shape_as``; no ``uncond``); ``out`` is fp32 all the same."""
+    if dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError(f"ace355: the logits stage runs in torch.float32 or torch.bfloat16, not {dtype}")
+    if dtype == torch.bfloat16 and uncond is not None:
+        raise ValueError("ace355: the bf16 logits stage takes no uncond (the reference combines in fp32)")
     cond = _rows(cond, "cond")
     B, V = cond.shape
     if uncond is not None and _rows(uncond, "uncond").shape != (B, V):
@@ -89,6 +99,10 @@ def shape_logits(cond: torch.Tensor, uncond: Optional[torch.Tensor] = None, cfg_
                               mask=mask.data_ptr() if mask is not None else None,
                               seen=seen.words.data_ptr() if penalty != 1.0 else None)
     with torch.cuda.device(cond.device):
+        if dtype == torch.bfloat16:
+            native.check(native.lib().ace355_lm_shape_as(cond.data_ptr(), cond.stride(0), None, 0, out.data_ptr(), out.stride(0), B, V,
+                                                         C.byref(p), native.DTYPE_BF16, native.current_stream_ptr()), "lm_shape_as")
+            return out
         native.check(native.lib().ace355_lm_shape(cond.data_ptr(), cond.stride(0), uncond.data_ptr() if uncond is not None else None,
                                                   uncond.stride(0) if uncond is not None else 0, out.data_ptr(), out.stride(0), B, V,
                                                   C.byref(p), native.current_stream_ptr()), "lm_shape")
@@ -155,7 +169,8 @@ def step_plan(view: StepView) -> StepPlan:
 # ---------------------------------------------------------------------------------------------------------------- the loop
 def _codes_mask(processor, name: str, device) -> Optional[torch.Tensor]:
     """The processor's mask as the stage takes it.  Like the reference's ``__call__`` (``:1589-1591``, ``:1611-1612``) this moves the
-    processor's own attribute to the logits' device and dtype (fp32: the CFG result is)."""
+    processor's own attribute to the logits' device and dtype (fp32: the CFG result is, and the non-CFG stage takes its mask in
+    fp32 and rounds it itself; 0 and -inf are exact in every dtype)."""
     m = getattr(processor, name)
     if m is None:
         return None
@@ -168,19 +183,24 @@ def _codes_mask(processor, name: str, device) -> Optional[torch.Tensor]:
 class _LoopMode(NamedTuple):
     """Which loop ``_cfg_loop`` runs.  ``seeds`` None: ``generate_with_cfg``, the rows of the ids are B conditional + B unconditional
     prompts and the global generator draws.  ``seeds`` a list: ``generate_codes_batch``, the ids are one ``[2, P]`` pair for
-    ``B = len(seeds)`` songs, row i draws from a generator of its own seeded ``seeds[i]``, and there is no streamer."""
+    ``B = len(seeds)`` songs, row i draws from a generator of its own seeded ``seeds[i]``, and there is no streamer.  ``cfg`` False:
+    the non-CFG loop (``generate_constrained`` / ``generate_codes_batch_nocfg``): the ids hold no unconditional rows (B prompts, or
+    one ``[1, P]`` prompt for the songs of ``seeds``), and the stage runs in the model's dtype on the forward's fp32 logits, as the
+    reference's ``_generate_with_constrained_decoding`` does (llm_inference.py:2369-2377: no upcast)."""
     B: int                  # token rows
     seeds: Optional[list]
     streamer: Any
+    cfg: bool = True
 
 
 def _cfg_loop(handler, lm, ids: torch.Tensor, attention_mask: Optional[torch.Tensor], mode: _LoopMode, max_new_tokens: int,
               temperature: float, cfg_scale: float, top_k: Optional[int], top_p: Optional[float], repetition_penalty: float,
               pad_token_id: int, proc) -> torch.Tensor:
-    """The CFG loop behind ``generate_with_cfg`` and ``generate_codes_batch``: int64 ``[steps, B]``, row t the tokens of step t.
-    Leaves ``handler._lm_loop_stats``; raises when some step could draw no token."""
+    """The loop behind ``generate_with_cfg``, ``generate_codes_batch`` and their non-CFG counterparts (``cfg_scale`` is not read
+    there): int64 ``[steps, B]``, row t the tokens of step t.  Leaves ``handler._lm_loop_stats``; raises when some step could draw
+    no token."""
     from . import lmsample
-    B, streamer, batched = mode.B, mode.streamer, mode.seeds is not None
+    B, streamer, batched, cfg = mode.B, mode.streamer, mode.seeds is not None, mode.cfg
     dev = ids.device
     n0 = 1 if batched else B   # conditional rows of the prompt, and of step 0's logits
     V = lm.cfg.vocab_size
@@ -191,7 +211,9 @@ def _cfg_loop(handler, lm, ids: torch.Tensor, attention_mask: Optional[torch.Ten
     sample = temperature > 0
     stats = {"steps": 0, "native_steps": 0, "sync_free_steps": 0, "token_reads": 0}
     if batched:
-        stats.update(batch=B, prefill_rows=2)
+        stats.update(batch=B, prefill_rows=2 if cfg else 1)
+    if not cfg:
+        stats["cfg"] = False
     handler._lm_loop_stats = stats
     tokens = torch.empty(max(int(max_new_tokens), 1), B, dtype=torch.int64, device=dev)   # row t: the tokens of step t
     # the conditional rows, pads included; batched: every song's is the pair's
@@ -206,10 +228,10 @@ def _cfg_loop(handler, lm, ids: torch.Tensor, attention_mask: Optional[torch.Ten
     with torch.inference_mode():
         for step in range(int(max_new_tokens)):
             logits = lm.prefill(ids, attention_mask) if step == 0 else lm.decode_tokens(tokens[step - 1])
-            if lm.out_dtype != torch.float32:
+            if cfg and lm.out_dtype != torch.float32:
                 logits = logits.to(lm.out_dtype).float()   # the model's own output dtype, upcast as llm_inference.py:2482 does
             n = n0 if step == 0 else B
-            cond, uncond = logits[:n], logits[n:]
+            cond, uncond = (logits[:n], logits[n:]) if cfg else (logits, None)   # no CFG: the stage's first rounding is the .to(dtype)
             if proc is not None and proc.enabled and _state_name(proc.state) == "CODES_GENERATION" and proc.non_audio_code_mask is not None:
                 m = _codes_mask(proc, "non_audio_code_mask", dev)
                 if blocked_for is not proc.non_audio_code_mask:   # once per call: which of the loop's stop ids the mask rules out
@@ -220,22 +242,28 @@ def _cfg_loop(handler, lm, ids: torch.Tensor, attention_mask: Optional[torch.Ten
             plan = step_plan(StepView(proc, eos, pad_token_id, streamer is not None, blocked))
             if plan.native:
                 if n != B:   # one staged row per song: the penalty's bitmap and the selection have B rows
-                    cond, uncond = cond.repeat(B, 1), uncond.repeat(B, 1)
+                    cond, uncond = cond.repeat(B, 1), uncond.repeat(B, 1) if cfg else None
                 mask = None
                 if plan.mask is not None:
                     mask = _codes_mask(proc, "audio_code_mask" if _state_name(proc.state) == "COMPLETED" else "non_audio_code_mask", dev)
-                x = shape_logits(cond, uncond, cfg_scale, mask, proc.eos_token_id if plan.eos_mode else None, plan.eos_mode,
-                                 plan.temperature, penalty, seen, out=cond)
+                if cfg:
+                    x = shape_logits(cond, uncond, cfg_scale, mask, proc.eos_token_id if plan.eos_mode else None, plan.eos_mode,
+                                     plan.temperature, penalty, seen, out=cond)
+                else:
+                    x = shape_logits(cond, None, 1.0, mask, proc.eos_token_id if plan.eos_mode else None, plan.eos_mode,
+                                     plan.temperature, penalty, seen, out=cond, dtype=lm.out_dtype)
                 stats["native_steps"] += 1
             else:   # the reference's processor (THINK_TAG -> CODES_GENERATION is made in its __call__)
                 if batched and step != 0:
                     raise RuntimeError(f"ace355: the constrained processor left the codes phase at step {step} of a batched loop "
                                        f"(state {_state_name(proc.state)})")
                 cur = ids[:1] if batched else torch.cat([ids[:B], tokens[:step].t().to(ids.dtype)], dim=1)
-                x = uncond + cfg_scale * (cond - uncond)
+                x = uncond + cfg_scale * (cond - uncond) if cfg else cond.to(lm.out_dtype)
                 x = proc(cur, x)
                 for lp in handler._build_logits_processor(repetition_penalty):
                     x = lp(cur, x)
+                if not cfg:
+                    x = x.float()   # the selection reads fp32; the values stay the model dtype's
                 if batched:
                     x = x.repeat(B, 1)
             if batched:   # row i's own stream of uniforms: one torch.rand(1) per step, as the B = 1 loop draws
@@ -252,7 +280,7 @@ def _cfg_loop(handler, lm, ids: torch.Tensor, attention_mask: Optional[torch.Ten
             if seen is not None:
                 seen.mark(tokens[step])
             if batched and step == 0:
-                lm.fan_out([0] * B + [1] * B)
+                lm.fan_out([0] * B + [1] * B if cfg else [0] * B)
             if plan.native and plan.sync_free:
                 for _ in range(1 if batched else B):   # batched: once per step, codes per song
                     proc.update_state(0)   # CODES_GENERATION only counts (update_state :2153-2158): the value is not looked at
@@ -358,3 +386,76 @@ def generate_codes_batch(handler, lm, pair_ids: torch.Tensor, pair_mask: Optiona
     tokens = _cfg_loop(handler, lm, pair_ids, pair_mask, _LoopMode(B, seeds, None), max_new_tokens, temperature, cfg_scale, top_k, top_p,
                        repetition_penalty, pad_token_id, proc)
     return torch.cat([pair_ids[:1].to(torch.int64).expand(B, pair_ids.shape[1]), tokens.t()], dim=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- without CFG
+def _nocfg_dtype(lm):
+    if lm.out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"ace355: the native non-CFG LM loop runs its stage in fp32 or bf16, the LM's out_dtype is {lm.out_dtype}")
+
+
+def generate_constrained(handler, lm, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], max_new_tokens: int,
+                         temperature: float, top_k: Optional[int], top_p: Optional[float], repetition_penalty: float, pad_token_id: int,
+                         streamer, constrained_processor=None) -> torch.Tensor:
+    """``LLMHandler._generate_with_constrained_decoding`` (llm_inference.py:2321-2412) on ``lm`` (a ``NativeCausalLM``): same
+    arguments, same return (``[B, P + steps]``), same streamer calls, the processor left as the reference's loop leaves it.  The
+    third mode of ``_cfg_loop``: B sequences and no unconditional rows, the stage in ``lm.out_dtype`` (that loop never upcasts, so a
+    bf16 model's processor results round to bf16; ``shape_logits(dtype=...)``), and on an FSM state ``step_plan`` does not cover the
+    reference's processor on ``logits.to(lm.out_dtype)``.  The loop ends after the step in which any row drew the tokenizer's EOS or
+    ``pad_token_id`` (``_check_eos_token``).  The draw is the native selection's, as in ``generate_with_cfg``.  Leaves
+    ``handler._lm_loop_stats`` (plus ``"cfg": False``)."""
+    _nocfg_dtype(lm)
+    ids = input_ids
+    tokens = _cfg_loop(handler, lm, ids, attention_mask, _LoopMode(ids.shape[0], None, streamer, False), max_new_tokens, temperature, 1.0,
+                       top_k, top_p, repetition_penalty, pad_token_id, constrained_processor)
+    return torch.cat([ids, tokens.t().to(ids.dtype)], dim=1)
+
+
+def nocfg_batch_request(formatted_prompts, cfg_scale, generation_phase, use_constrained_decoding, target_duration, seeds,
+                        loop_refusal: Optional[str] = None):
+    """``batch_request`` for the non-CFG loop (``generate_codes_batch_nocfg``): the same conditions with the CFG one reversed - the
+    reference takes this branch when ``not cfg_scale > 1.0`` (llm_inference.py:929).  Pure."""
+    if not isinstance(formatted_prompts, list) or len(formatted_prompts) < 2:
+        return False, "the prompts are not a list of two or more"
+    if any(not isinstance(p, str) or p != formatted_prompts[0] for p in formatted_prompts):
+        return False, "the prompts of the batch differ"
+    if cfg_scale > 1.0:
+        return False, f"cfg_scale {cfg_scale} runs a CFG pair"
+    if generation_phase != "codes":
+        return False, f"generation phase '{generation_phase}' is not 'codes'"
+    if not use_constrained_decoding:
+        return False, "constrained decoding is off, so nothing ends every song at the same step"
+    if target_duration is None or not target_duration > 0:
+        return False, "no target duration, so nothing ends every song at the same step"
+    if (not isinstance(seeds, (list, tuple)) or len(seeds) < len(formatted_prompts)
+            or any(isinstance(s, bool) or not isinstance(s, int) for s in seeds[:len(formatted_prompts)])):
+        return False, "seeds does not hold an int for every item"
+    if loop_refusal is not None:
+        return False, loop_refusal
+    return True, None
+
+
+def generate_codes_batch_nocfg(handler, lm, prompt_ids: torch.Tensor, prompt_mask: Optional[torch.Tensor], seeds, max_new_tokens: int,
+                               temperature: float, top_k: Optional[int], top_p: Optional[float], repetition_penalty: float,
+                               pad_token_id: int, constrained_processor) -> torch.Tensor:
+    """``generate_codes_batch`` without CFG: the audio codes of ``B = len(seeds)`` songs that share the ``[1, P]`` prompt, int64
+    ``[B, P + steps]``.  One prefill of the prompt; its staged row is expanded to B rows, B tokens are selected, the cache is fanned
+    out to B sequences (``lm.fan_out([0] * B)``) and every later step decodes all B - up to ``lm.max_seqs`` songs, twice the CFG
+    path's.  Row i equals ``generate_constrained`` on the prompt called right after ``torch.manual_seed(seeds[i]);
+    torch.cuda.manual_seed_all(seeds[i])`` with a fresh processor; its uniforms come from a generator of its own, and the global
+    generators are not touched.  Needs an enabled processor with ``target_codes`` and ``eos_token_id``; a step that finds only some
+    rows stopped raises.  Leaves ``handler._lm_loop_stats`` (plus ``batch``, ``prefill_rows`` 1, ``"cfg": False``)."""
+    proc = constrained_processor
+    if proc is None or not proc.enabled or proc.target_codes is None or proc.eos_token_id is None:
+        raise RuntimeError("ace355: the batched LM loop needs an enabled constrained processor with target_codes and eos_token_id "
+                           "(nothing else ends every song at the same step)")
+    _nocfg_dtype(lm)
+    seeds = [int(s) for s in seeds]
+    B = len(seeds)
+    if prompt_ids.dim() != 2 or prompt_ids.shape[0] != 1:
+        raise ValueError("ace355: the batched non-CFG LM loop takes the [1, P] ids of the one prompt")
+    if not 1 <= B <= lm.max_seqs:
+        raise ValueError(f"ace355: {B} songs need {B} sequences, the native LM holds {lm.max_seqs}")
+    tokens = _cfg_loop(handler, lm, prompt_ids, prompt_mask, _LoopMode(B, seeds, None, False), max_new_tokens, temperature, 1.0, top_k,
+                       top_p, repetition_penalty, pad_token_id, proc)
+    return torch.cat([prompt_ids.to(torch.int64).expand(B, prompt_ids.shape[1]), tokens.t()], dim=1)

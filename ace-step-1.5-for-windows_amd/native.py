@@ -411,6 +411,8 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ace355_lm_shape": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                   C.POINTER(LmShapeParamsC), C.c_void_p]),
+    "ace355_lm_shape_as": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                     C.POINTER(LmShapeParamsC), C.c_int, C.c_void_p]),
     "ace355_lm_seen_mark": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ace355_lm_decode_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ace355_lm_bad_tokens": (C.c_int64, [C.c_void_p]),

@@ -1019,6 +1019,25 @@ typedef struct ace355_lm_shape_params {
  * cfg_scale with uncond given, has_temperature with temperature <= 0 or NaN. */
 int ace355_lm_shape(const float* cond_dev, int64_t cond_stride, const float* uncond_dev, int64_t uncond_stride, float* out_dev,
                     int64_t out_stride, int B, int V, const ace355_lm_shape_params* p, void* stream);
+/* The stage in the model's dtype: what the reference's non-CFG loop (_generate_with_constrained_decoding,
+ * llm_inference.py:2369-2377) does to outputs.logits[:, -1, :], which it never upcasts, so that on a bf16 model each of the
+ * processor's torch kernels rounds its result to bf16.  The arguments of ace355_lm_shape plus `dtype`; one launch of the same grid.
+ *   ACE355_DTYPE_F32: exactly ace355_lm_shape.
+ *   ACE355_DTYPE_BF16: r(x) is round-to-nearest-even of an fp32 value to bf16, kept in fp32 (NaN stays NaN, +-inf and +-0 stay,
+ *     subnormals round like any value, a finite value beyond bf16's largest becomes inf).  For every row b and id v:
+ *       1. x = r(cond[b][v]) (the reference's cast of the logits to the model's dtype); x = r(x + r(mask[v])) when mask is given.
+ *       2. the EOS rule of ace355_lm_shape's step 3, unchanged.
+ *       3. x = r(x / temperature) when has_temperature: the IEEE fp32 division by the fp32 temperature, then r.
+ *       4. on seen ids x = x < 0 ? r(x * penalty) : r(x / penalty), in fp32 by the fp32 penalty, then r.
+ *     out stays fp32 and holds bf16-representable values.  The rounding is an integer operation on the bit pattern.
+ *   This is torch on the CPU, bit for bit: there `x / T` on a bf16 tensor is r(fp32(x) / fp32(T)), and `x * p`, `x / p` likewise.
+ *   torch on the GPU may turn the division by a host scalar into a multiplication by its reciprocal; the stage keeps the IEEE
+ *   division of the fp32 stage and of torch on the CPU, so that one oracle serves both.  At T = 0.6 the two readings differ in
+ *   about 1 % of the bf16 results; which of them a GPU reference run produces is not pinned.
+ * ACE355_ERR_INVALID before any HIP call for a dtype other than the two, for uncond != NULL with a dtype other than
+ * ACE355_DTYPE_F32 (the reference never combines below fp32), and for everything ace355_lm_shape refuses. */
+int ace355_lm_shape_as(const float* cond_dev, int64_t cond_stride, const float* uncond_dev, int64_t uncond_stride, float* out_dev,
+                       int64_t out_stride, int B, int V, const ace355_lm_shape_params* p, int dtype, void* stream);
 /* ids dev int64, row b at ids + b * row_stride, T ids per row: sets bit v & 31 of seen[b][v >> 5] for every id v in [0, V) with an
  * integer atomic OR (commutative: the result does not depend on order); ids outside [0, V) are ignored.  Bits are only ever set:
  * the caller zeroes the bitmap (dev u32 [B, (V + 31) / 32]).  ACE355_ERR_INVALID before any HIP call for B outside
