@@ -13,7 +13,8 @@ Layout:
   lmlogits.py  shape_logits / SeenTokens / step_plan / generate_with_cfg: the LM's logits stage and its device-resident CFG loop
   lmscore.py   calculate_pmi_score_per_condition and its helpers: the reference's LM quality score on NativeCausalLM.score
   audio_out.py normalize_audio, AudioSaver: GPU normalise / PCM conversion + threaded FLAC / WAV writers
-  audio_in.py  load_stereo_48k, reference_segments: WAV / FLAC payload -> clamped 48 kHz stereo on the GPU (the producer of row N3)
+  audio_in.py  load_stereo_48k, reference_segments: WAV / FLAC payload -> clamped 48 kHz stereo on the GPU (the producer of row N3);
+               decode_flac: a FLAC file's frames decoded on the GPU, 16 to 24 bits (opt-in)
   backend.py   NativeDitMixin / NativeVaeMixin / NativeHandler: the reference's handler seam
   dist.py      one-process-per-GPU data-parallel runner (RCCL broadcast of conditioning)
   weightgen.py deterministic synthetic weights (no checkpoints exist on the boxes)

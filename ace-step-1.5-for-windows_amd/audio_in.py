@@ -9,6 +9,8 @@ payload in the container and makes the resampler's tap table; the payload goes t
 * WAV: RIFF with ``fmt `` codes 1 (PCM 8 / 16 / 24 / 32 bit), 3 (IEEE float32) and 0xFFFE (extensible, those two sub-formats); unknown
   chunks are skipped, a ``data`` chunk that claims more than the file holds is cut at the end of the file (libsndfile does the same).
 * FLAC: the package's own decoder (``audio_out.flac_decode_pcm16``: <= 16 bits, 1-2 channels), whose int16 frames are the payload.
+  With ``flac_on_gpu`` the file goes up as it is instead and its frames are decoded on the GPU (``decode_flac``, csrc/flac_in.hip:
+  16 to 24 bits, 1-2 channels); what the frame index refuses, or a frame the device rejects, goes back to the line above.
 * Anything else - RF64, ADPCM, float64, mp3, deeper FLAC, a rate whose tap table the plan refuses - raises ``NotImplementedError``: the
   seam (``backend.NativeAudioInMixin``) hands those to the host's own method.
 
@@ -95,6 +97,85 @@ def _flac_payload(data) -> Tuple[np.ndarray, PcmInfo]:
     from .audio_out import flac_decode_pcm16
     pcm, rate = flac_decode_pcm16(bytes(data))
     return pcm.reshape(-1).view(np.uint8), PcmInfo("s16", int(ch.value), int(rate), int(pcm.shape[0]), 0)
+
+
+def flac_index(data) -> Tuple["native.FlacStreamInfoC", np.ndarray]:
+    """``ace355_flac_index``: (STREAMINFO, the frame table int64 [frames, 4] = byte offset, byte length, first sample, block size) of a
+    FLAC file's bytes.  ``NotImplementedError`` with the index's text for a stream it refuses."""
+    lib = native.lib()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    info, n, cap = native.FlacStreamInfoC(), C.c_int64(0), 4096
+    for _attempt in range(2):
+        table = np.empty((cap, 4), dtype=np.int64)
+        if lib.ace355_flac_index(buf.ctypes.data, buf.size, C.byref(info), table.ctypes.data, cap, C.byref(n)) == native.OK:
+            return info, table[:n.value]
+        if n.value <= cap:
+            break
+        cap = int(n.value)
+    raise NotImplementedError(native.last_error())
+
+
+def _flac_host(data, device, report: Dict[str, object], reason: str) -> Tuple[torch.Tensor, PcmInfo, Dict[str, object]]:
+    """The fallback of ``decode_flac``: the flag-off host path (``_flac_payload``), which is the authority - what it raises surfaces, with
+    the report attached as ``flac_report``."""
+    report.update(path="host", reason=reason)
+    report.pop("words", None)
+    try:
+        payload, info = _flac_payload(data)
+    except Exception as exc:
+        exc.flac_report = report
+        raise
+    return upload(payload, device), info, report
+
+
+def _flac_status(report: Dict[str, object], words) -> Union[str, None]:
+    """Reads (first bad frame, code) out of the fetched status words into the report; the fallback's reason, or None when every frame
+    decoded."""
+    frame, code = int(words[1]), int(words[2])
+    if frame < 0:
+        return None
+    report.update(frame=frame, code=code)
+    return f"frame {frame}: {native.FLAC_STATUS[code] if 0 <= code < len(native.FLAC_STATUS) else code}"
+
+
+def decode_flac(data, device, sync: bool = True) -> Tuple[torch.Tensor, PcmInfo, Dict[str, object]]:
+    """A FLAC file's bytes -> (the uint8 device payload ``resample_payload`` takes, what is in it, a report).  The bytes are uploaded as
+    they are, indexed by frame on the host and decoded on the GPU (16 to 24 bits, 1-2 channels; int16 at 16 bits, left-justified int32
+    above); every frame's CRC-16 is checked there, the STREAMINFO MD5 is not.  ``report["path"]`` is ``"gpu"`` or ``"host"``; after a
+    fallback ``report["reason"]`` holds the index's refusal or the device status (``report["frame"]``, ``report["code"]``:
+    ``native.FLAC_STATUS``), and the payload is the host decoder's - at more than 16 bits there is none and the ``NotImplementedError``
+    of the host path is raised.  ``sync=False`` leaves the status unread in ``report["words"]`` (int32 [3] on the device: a slot for
+    the resampler's peak, then first bad frame and code) for a caller that fetches it with its own synchronisation."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise NotImplementedError("the native audio input stage runs on the GPU (no CPU fallback)")
+    report: Dict[str, object] = {"path": "gpu", "reason": None, "frame": None, "code": None}
+    lib = native.lib()
+    try:
+        info, table = flac_index(data)
+    except NotImplementedError as exc:
+        return _flac_host(data, device, report, str(exc))
+    plan = native.FlacInPlanInfoC()
+    if lib.ace355_flac_in_plan(len(table), info.channels, info.bits_per_sample, info.max_block, info.total_samples, C.byref(plan)) != native.OK:
+        return _flac_host(data, device, report, native.last_error())
+    report["frames"] = len(table)
+    file_dev = upload(np.frombuffer(data, dtype=np.uint8), device)
+    table_dev = torch.from_numpy(table).to(device)
+    scratch = torch.empty(plan.scratch_bytes, dtype=torch.uint8, device=device)
+    out = torch.empty(plan.out_bytes, dtype=torch.uint8, device=device)
+    words = torch.empty(3, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        native.check(lib.ace355_flac_in_decode(C.byref(info), native.ptr(file_dev), len(memoryview(data)), native.ptr(table_dev), len(table),
+                                               native.ptr(scratch), scratch.numel(), native.ptr(out), out.numel(), words.data_ptr() + 4,
+                                               native.current_stream_ptr()), "flac_in_decode")
+    pcm = PcmInfo(native.PCM_FORMATS[plan.out_format], int(info.channels), int(info.sample_rate), int(info.total_samples), 0)
+    if not sync:
+        report["words"] = words
+        return out, pcm, report
+    reason = _flac_status(report, words.cpu())
+    if reason is not None:
+        return _flac_host(data, device, report, reason)
+    return out, pcm, report
 
 
 def find_payload(data) -> Tuple[np.ndarray, PcmInfo]:
@@ -192,10 +273,12 @@ def upload(payload: np.ndarray, device) -> torch.Tensor:
     return buf
 
 
-def resample_payload(buf: torch.Tensor, offset: int, format: str, channels: int, frames: int, sample_rate: int) -> Tuple[torch.Tensor, torch.Tensor]:
+def resample_payload(buf: torch.Tensor, offset: int, format: str, channels: int, frames: int, sample_rate: int,
+                     peak: Union[torch.Tensor, None] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``ace355_audio_in_run``: ``buf`` uint8 on the GPU (size a multiple of 4) holding ``frames`` x ``channels`` interleaved samples of
     ``format`` from byte ``offset`` -> (fp32 [2, S] at 48 kHz clamped to [-1, 1], its peak as a fp32 [1] tensor), both on ``buf``'s device.
-    A request the plan refuses raises ``NotImplementedError`` with the plan's text."""
+    A request the plan refuses raises ``NotImplementedError`` with the plan's text.  ``peak``: a fp32 [1] tensor on that device to leave
+    the peak in (a new one otherwise)."""
     if not (buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous() and buf.numel() % 4 == 0):
         raise ValueError("resample_payload: a contiguous uint8 CUDA tensor with a multiple of 4 bytes")
     tab = device_table(sample_rate, buf.device)
@@ -205,17 +288,38 @@ def resample_payload(buf: torch.Tensor, offset: int, format: str, channels: int,
     if lib.ace355_audio_in_plan(C.byref(rq), C.byref(info)) != native.OK:
         raise NotImplementedError(native.last_error())
     out = torch.empty(2, info.out_frames, dtype=torch.float32, device=buf.device)
-    peak = torch.empty(1, dtype=torch.float32, device=buf.device)
+    if peak is None:
+        peak = torch.empty(1, dtype=torch.float32, device=buf.device)
     with torch.cuda.device(buf.device):
         native.check(lib.ace355_audio_in_run(C.byref(rq), native.ptr(buf), buf.numel(), int(offset), native.ptr(tab["first"]), native.ptr(tab["taps"]),
                                              native.ptr(out), native.ptr(peak), native.current_stream_ptr()), "audio_in_run")
     return out, peak
 
 
-def load_stereo_48k(path_or_bytes: Union[str, os.PathLike, bytes, bytearray, memoryview], device) -> Tuple[torch.Tensor, float]:
+def _load_flac_on_gpu(data, device) -> Tuple[torch.Tensor, float]:
+    """``load_stereo_48k`` of a FLAC file through ``decode_flac``: the resampler is enqueued on the decoded payload whatever the decode
+    will report, and its peak and the decode's status come back in one copy - the only synchronisation of the call.  A bad status
+    discards the result and the host decoder's payload takes the same road."""
+    buf, info, report = decode_flac(data, device, sync=False)
+    if report["path"] == "gpu":
+        words = report.pop("words")
+        wav, _peak = resample_payload(buf, 0, info.format, info.channels, info.frames, info.sample_rate, peak=words[0:1].view(torch.float32))
+        host = words.cpu()
+        reason = _flac_status(report, host)
+        if reason is None:
+            return wav, float(host[0:1].view(torch.float32).item())
+        buf, info, report = _flac_host(data, device, report, reason)
+    if info.frames < 1:
+        raise ValueError("the file holds no audio frames")
+    wav, peak = resample_payload(buf, info.offset, info.format, info.channels, info.frames, info.sample_rate)
+    return wav, float(peak.item())
+
+
+def load_stereo_48k(path_or_bytes: Union[str, os.PathLike, bytes, bytearray, memoryview], device, flac_on_gpu: bool = False) -> Tuple[torch.Tensor, float]:
     """A WAV or FLAC file (path or contents) -> (wav fp32 [2, S] at 48 kHz on ``device``, clamped to [-1, 1]; max|wav|): what
     ``torchaudio.load`` + ``_normalize_audio_to_stereo_48k`` return (io_audio.py:18-37, :78, :129).  ``OSError`` for an unreadable path,
-    ``ValueError`` for a file without frames, ``NotImplementedError`` for what this stage does not read."""
+    ``ValueError`` for a file without frames, ``NotImplementedError`` for what this stage does not read.  ``flac_on_gpu``: a FLAC file's
+    frames are decoded on the GPU (``decode_flac``) instead of by the host decoder; every other file is read as without it."""
     device = torch.device(device)
     if device.type != "cuda":
         raise NotImplementedError("the native audio input stage runs on the GPU (no CPU fallback)")
@@ -224,6 +328,8 @@ def load_stereo_48k(path_or_bytes: Union[str, os.PathLike, bytes, bytearray, mem
     else:
         with open(path_or_bytes, "rb") as f:
             data = f.read()
+    if flac_on_gpu and bytes(memoryview(data)[0:4]) == b"fLaC":
+        return _load_flac_on_gpu(data, device)
     payload, info = find_payload(data)
     if info.frames < 1:
         raise ValueError("the file holds no audio frames")

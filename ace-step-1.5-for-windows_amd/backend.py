@@ -42,6 +42,7 @@ _LM_NOCFG_ENV = os.environ.get("ACE355_LM_NOCFG", "") == "1"       # read once: 
 _LM_SCORE_ENV = os.environ.get("ACE355_LM_SCORE", "") == "1"       # read once: the default of NativeLmMixin.use_native_lm_score
 _LM_GQA4_ENV = os.environ.get("ACE355_LM_GQA4", "") == "1"         # read once: the default of NativeLmMixin.use_native_lm_gqa4
 _AUDIO_IN_ENV = os.environ.get("ACE355_AUDIO_IN", "") == "1"       # read once: the default of NativeAudioInMixin.use_native_audio_in
+_FLAC_GPU_ENV = os.environ.get("ACE355_FLAC_GPU", "") == "1"       # read once: the default of NativeAudioInMixin.native_flac_decode
 
 
 class NativeDitMixin:
@@ -819,14 +820,17 @@ class NativeAudioInMixin:
     """The three loaders of ``IoAudioMixin`` (acestep/core/generation/handler/io_audio.py:39-133) on the native input stage
     (ace355.audio_in): same signatures, same None-on-failure behaviour, but the tensor they return is already on ``self.device``, so
     ``tiled_encode`` takes it without a copy.  Required host attribute: ``device``.  Opt-in (``use_native_audio_in``, or
-    ACE355_AUDIO_IN=1 for every host): off, each call goes to the host's own method further up the MRO, untouched."""
+    ACE355_AUDIO_IN=1 for every host): off, each call goes to the host's own method further up the MRO, untouched.
+    ``native_flac_decode`` (or ACE355_FLAC_GPU=1) matters only while ``use_native_audio_in`` is on: a FLAC file's frames are then
+    decoded on the GPU, 16 to 24 bits per sample (``audio_in.decode_flac``), instead of by the host decoder, which stops at 16."""
 
     use_native_audio_in: bool = _AUDIO_IN_ENV
+    native_flac_decode: bool = _FLAC_GPU_ENV
 
     def _native_load_audio(self, audio_file):
         """(wav fp32 [2, S] at 48 kHz on ``self.device``, max|wav|) of a WAV / FLAC file."""
         from .audio_in import load_stereo_48k
-        return load_stereo_48k(audio_file, self.device)
+        return load_stereo_48k(audio_file, self.device, flac_on_gpu=self.native_flac_decode)
 
     def _native_audio_in(self, name: str, audio_file, reference: bool = False):
         parent = getattr(super(), name, None)

@@ -556,13 +556,9 @@ const char* decode_subframe(BitReader& br, int n, int bps, int32_t* s) {
     return br.bad ? "truncated subframe" : nullptr;
 }
 
-struct FlacInfo {
-    int64_t frames = 0;
-    int channels = 0, sample_rate = 0, bps = 0;
-    size_t first_frame = 0;
-    uint8_t md5[16];
-};
+}  // namespace
 
+// (FlacInfo: common.h; the frame index of the GPU decode, flac_in.hip, reads the metadata through this too)
 const char* flac_parse_header(const uint8_t* p, size_t n, FlacInfo* fi) {
     if (n < 42 || memcmp(p, "fLaC", 4) != 0) return "not a FLAC stream";
     size_t pos = 4;
@@ -577,7 +573,8 @@ const char* flac_parse_header(const uint8_t* p, size_t n, FlacInfo* fi) {
         if (type == 0) {
             if (len < 34) return "short STREAMINFO";
             BitReader br(p + pos, len);
-            br.get(16), br.get(16), br.get(24), br.get(24);
+            fi->min_block = (int)br.get(16), fi->max_block = (int)br.get(16);
+            br.get(24), br.get(24);
             fi->sample_rate = (int)br.get(20);
             fi->channels = (int)br.get(3) + 1;
             fi->bps = (int)br.get(5) + 1;
@@ -592,6 +589,8 @@ const char* flac_parse_header(const uint8_t* p, size_t n, FlacInfo* fi) {
     fi->first_frame = pos;
     return nullptr;
 }
+
+namespace {
 
 const char* flac_decode(const uint8_t* p, size_t n, const FlacInfo& fi, int16_t* out) {
     if (fi.bps > 16 || fi.channels < 1 || fi.channels > 2) return "decoder subset: <= 16 bits, 1-2 channels";

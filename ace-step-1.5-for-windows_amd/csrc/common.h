@@ -399,4 +399,15 @@ int launch_align_dtw(const float* m, int batch, int R, int S, float sign, int32_
 int launch_align_score_metrics(const float* energy, const int32_t* path, const int32_t* path_len, const int32_t* mask, int batch, int R,
                                int S, double time_weight, double overlap, double inst_weight, double* out, void* ws, hipStream_t s);
 
+
+// FLAC metadata (audio_out.hip): STREAMINFO and where the first frame starts.  Returns why not, or null.
+struct FlacInfo {
+    int64_t frames = 0;
+    int channels = 0, sample_rate = 0, bps = 0;
+    int min_block = 0, max_block = 0;
+    size_t first_frame = 0;
+    uint8_t md5[16];
+};
+const char* flac_parse_header(const uint8_t* p, size_t n, FlacInfo* fi);
+
 }  // namespace ace355

@@ -301,6 +301,20 @@ class AudioInPlanInfoC(C.Structure):
         "tile", "threads", "span", "table_in_lds", "lds_bytes", "passthrough")]
 
 
+FLAC_STATUS = ("ok", "header mismatch", "reserved code", "ran past its byte range", "sample count", "CRC-16 mismatch")   # ACE355_FLAC_*
+
+
+class FlacStreamInfoC(C.Structure):
+    _fields_ = [("total_samples", C.c_int64), ("first_frame", C.c_int64)] + [(n, C.c_int32) for n in (
+        "channels", "bits_per_sample", "sample_rate", "min_block", "max_block", "variable_blocks")]
+
+
+class FlacInPlanInfoC(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("entropy_grid", "restore_grid", "finish_grid", "desc_at", "frame_at", "scratch_bytes", "out_bytes")] + [
+        (n, C.c_int32) for n in ("launches", "entropy_threads", "entropy_lanes", "restore_threads", "restore_lanes", "finish_threads",
+                                 "finish_tiles", "status_threads", "out_format", "reserved")]
+
+
 # name -> (restype, argtypes); every symbol include/ace355.h declares
 SIGNATURES = {
     "ace355_last_error": (C.c_char_p, []),
@@ -432,6 +446,10 @@ SIGNATURES = {
     "ace355_audio_in_plan": (C.c_int, [C.POINTER(AudioInRequestC), C.POINTER(AudioInPlanInfoC)]),
     "ace355_audio_in_run": (C.c_int, [C.POINTER(AudioInRequestC), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "ace355_flac_index": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(FlacStreamInfoC), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "ace355_flac_in_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(FlacInPlanInfoC)]),
+    "ace355_flac_in_decode": (C.c_int, [C.POINTER(FlacStreamInfoC), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ace355_gemm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ace355_gemm_bf16_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -615,6 +633,17 @@ def audio_in_plan(format: str, channels: int, frames: int, o: int, n: int, K: in
     rq, out = audio_in_request(format, channels, frames, o, n, K, width), AudioInPlanInfoC()
     check(lib().ace355_audio_in_plan(C.byref(rq), C.byref(out)), "audio_in_plan")
     return {k: int(getattr(out, k)) for k, _t in AudioInPlanInfoC._fields_}
+
+
+def flac_in_plan(frames: int, channels: int, bps: int, max_block: int, total_samples: int) -> dict:
+    """`ace355_flac_in_plan` (include/ace355.h): the launches of the GPU FLAC decode for a table of ``frames`` frames - grids, workgroup
+    sizes, live lanes per wave, scratch layout and bytes, output format (by name) and bytes.  A refusal raises with the plan's text.  A
+    function of its arguments alone; no GPU."""
+    out = FlacInPlanInfoC()
+    check(lib().ace355_flac_in_plan(int(frames), int(channels), int(bps), int(max_block), int(total_samples), C.byref(out)), "flac_in_plan")
+    d = {k: int(getattr(out, k)) for k, _t in FlacInPlanInfoC._fields_ if k != "reserved"}
+    d["out_format"] = PCM_FORMATS[d["out_format"]]
+    return d
 
 
 def conv_plan(B: int, M: int, N: int, Cin: int, taps: int, **bits) -> dict:

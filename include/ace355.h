@@ -1228,6 +1228,72 @@ int ace355_audio_in_run(const ace355_audio_in_request* rq, const void* payload_d
                         const int32_t* first_dev, const float* taps_dev, float* out_dev, float* peak_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FLAC frames decoded on the GPU (csrc/flac_in.hip): the file's bytes go up as they are, the host walks the frame headers once
+ * (ace355_flac_index), and the launches of ace355_flac_in_plan decode every frame into the interleaved PCM payload
+ * ace355_audio_in_run reads.  16 to 24 bits per sample, 1 or 2 channels, every subframe form of RFC 9639 (constant, verbatim, fixed
+ * orders 0-4, LPC orders 1-32, Rice and Rice2 residuals, escaped partitions, wasted bits, the four channel assignments).  Every
+ * frame's CRC-16 is checked on the device; the STREAMINFO MD5 is not.
+ * ------------------------------------------------------------------------------------------ */
+#define ACE355_FLAC_OK 0
+#define ACE355_FLAC_HEADER_MISMATCH 1 /* no sync, CRC-8, a field that differs from the frame's table row or STREAMINFO, a range that holds more than the frame */
+#define ACE355_FLAC_RESERVED 2        /* a reserved or invalid code */
+#define ACE355_FLAC_OVERRUN 3         /* the frame ran past its byte range */
+#define ACE355_FLAC_SAMPLE_COUNT 4    /* a subframe that does not produce the block's sample count */
+#define ACE355_FLAC_CRC16 5
+
+typedef struct ace355_flac_stream_info {
+    int64_t total_samples;    /* per channel */
+    int64_t first_frame;      /* byte offset of the first frame */
+    int32_t channels;
+    int32_t bits_per_sample;
+    int32_t sample_rate;
+    int32_t min_block;
+    int32_t max_block;
+    int32_t variable_blocks;  /* the first frame's blocking-strategy bit: frame headers carry sample numbers */
+} ace355_flac_stream_info;
+
+typedef struct ace355_flac_in_plan_info {
+    int64_t entropy_grid;     /* workgroups of one wave; the first entropy_lanes lanes of each own one frame */
+    int64_t restore_grid;     /* the same over frames x channels subframes */
+    int64_t finish_grid;      /* frames x finish_tiles workgroups: one lane per sample */
+    int64_t desc_at;          /* scratch: int32 [channels][total] | subframe descriptors at desc_at | (status, assignment) per frame at frame_at */
+    int64_t frame_at;
+    int64_t scratch_bytes;
+    int64_t out_bytes;        /* a multiple of 4 */
+    int32_t launches;         /* entropy, restore, finish, status */
+    int32_t entropy_threads;
+    int32_t entropy_lanes;
+    int32_t restore_threads;
+    int32_t restore_lanes;
+    int32_t finish_threads;
+    int32_t finish_tiles;
+    int32_t status_threads;   /* one workgroup */
+    int32_t out_format;       /* ACE355_PCM_S16 at 16 bits; ACE355_PCM_S32 above, left-justified: v << (32 - bits) */
+    int32_t reserved;
+} ace355_flac_in_plan_info;
+
+/* Host, no GPU.  Parses the metadata, then walks the stream once without decoding subframes: table[f] = (byte offset, byte length,
+ * first sample, block size) of frame f, int64 [capacity][4]; *n_frames = the frames found, also when that exceeds capacity (ERR_INVALID
+ * then: call again with a larger table).  A frame ends where the next header is found: a 0xFF 0xF8/0xF9 pair whose header parses, whose
+ * CRC-8 matches, whose rate, sample size and channels agree with STREAMINFO, whose blocking bit equals the first frame's and whose coded
+ * number is the expected next one; the last frame ends with the file.  CRC-16 is left to the device, so a false sync that passes all of
+ * that splits a frame and shows up as that frame's status.  ERR_INVALID with the reason in ace355_last_error for: bits per sample outside
+ * 16 .. 24, more than 2 channels, a STREAMINFO max block outside 16 .. 16384, an unknown (0) total sample count, block sizes that do not
+ * sum to it, more than 2^24 frames.  *info is filled whenever the metadata parsed. */
+int ace355_flac_index(const uint8_t* data, int64_t size, ace355_flac_stream_info* info, int64_t* table, int64_t capacity, int64_t* n_frames);
+/* The launches ace355_flac_in_decode makes (csrc/flac_in_plan.h): a pure function of its arguments, no GPU.  ERR_INVALID for n_frames
+ * outside 1 .. 2^24, channels other than 1 / 2, bits outside 16 .. 24, max_block outside 16 .. 16384, total_samples outside 1 .. 2^32 or
+ * not within [n_frames, n_frames x max_block]. */
+int ace355_flac_in_plan(int64_t n_frames, int32_t channels, int32_t bits_per_sample, int32_t max_block, int64_t total_samples,
+                        ace355_flac_in_plan_info* out);
+/* file_dev: the whole file, 4-byte aligned and allocated up to the next multiple of 4.  table_dev: the index's table on the device.
+ * scratch_dev (16-byte aligned, plan.scratch_bytes), out_dev (plan.out_bytes): interleaved int16, or int32 left-justified above 16 bits.
+ * status_dev int32 [2]: the first frame whose status is not ACE355_FLAC_OK (-1: none) and its code; such a frame's samples are zeros.
+ * Rows that point outside the file or the stream are not acted on (HEADER_MISMATCH).  Enqueued on `stream`, no synchronisation. */
+int ace355_flac_in_decode(const ace355_flac_stream_info* info, const void* file_dev, int64_t file_bytes, const int64_t* table_dev, int64_t n_frames,
+                          void* scratch_dev, int64_t scratch_bytes, void* out_dev, int64_t out_bytes, int32_t* status_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Unit kernels (test hooks; each has an oracle twin in oracle/ used by tests/)
  * ---------------------------------------------------------------------------------------- */
 /* C = A[M,K] * W[N,K]^T, bf16 in, fp32 accumulate (MFMA).  out_dtype: ACE355_DTYPE_*; bias f32 [N] or NULL. */
