@@ -9,6 +9,9 @@ and error behaviour; the work moves as follows:
   per-item loop computes it.
 * ``AudioSaver.save_batch`` on a GPU batch interleaves and quantises on the GPU, copies the converted samples once and
   encodes all (item, block) jobs on one pool of host threads (FLAC frames are independent).
+* ``AudioSaver(flac_on_gpu=True)`` (opt-in, ``ACE355_FLAC_OUT_GPU=1``) encodes the FLAC frames on the GPU as well (csrc/flac_out.hip):
+  the compressed bytes come down instead of the PCM, the files are the host encoder's byte for byte, and the host only hashes (MD5,
+  one thread per item, optional) and writes.  ``flac_encode_device`` gives the streams without files.
 * "flac" (PCM_16), "wav" and "wav32" (IEEE float32, what the reference's torchaudio/soundfile path writes for a float32
   tensor) are native.  "mp3" / "opus" / "aac" need ffmpeg in the reference (audio_utils.py:149-157) and raise here, so a
   host integrating this keeps its own path for them.
@@ -31,6 +34,7 @@ from . import native
 FORMATS = ["flac", "wav", "mp3", "wav32", "opus", "aac"]
 _NATIVE = {"flac": 0, "wav": 1, "wav32": 1}  # ACE355_AUDIO_*
 _EXTS = [".flac", ".wav", ".mp3", ".opus", ".aac", ".m4a"]
+FLAC_OUT_GPU_DEFAULT = os.environ.get("ACE355_FLAC_OUT_GPU", "") == "1"   # read once: the default of AudioSaver(flac_on_gpu=None)
 
 
 def normalize_audio(audio_data, target_db: float = -1.0):
@@ -122,14 +126,53 @@ def float_to_pcm16(wav: torch.Tensor) -> torch.Tensor:
     return out[0] if squeeze else out
 
 
-class AudioSaver:
-    """AudioSaver of acestep/audio_utils.py:65-313 for GPU tensors and the PCM container formats."""
+def flac_encode_device(pcm: torch.Tensor, sample_rate: int, md5: bool = True) -> List[bytes]:
+    """FLAC frames encoded on the GPU (csrc/flac_out.hip): interleaved int16 ``[B, S, C]`` (or ``[S, C]``) on the device -> one stream
+    per item, the bytes ``flac_encode_pcm16`` gives for the same samples.  ``md5=False`` leaves STREAMINFO's MD5 zero ("not computed")
+    and copies no PCM down; with it the hash is the host's.  A request the plan refuses raises."""
+    assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() in (2, 3)
+    x = (pcm[None] if pcm.dim() == 2 else pcm).contiguous()
+    B, S, Cn = x.shape
+    if not 0 < int(sample_rate) < (1 << 20):
+        raise ValueError("sample rate outside STREAMINFO")
+    import hashlib
+    host = x.cpu().numpy() if md5 else None
+    digests = [hashlib.md5(host[i].astype("<i2").tobytes()).digest() if md5 else None for i in range(B)]
+    if S == 0:   # nothing to launch: the stream is its 42 header bytes
+        return [native.flac_streaminfo(0, Cn, sample_rate, 0, 0, d) for d in digests]
+    p = native.flac_out_plan(B, S, Cn)
+    with torch.cuda.device(x.device):
+        scratch = torch.empty(p["scratch_bytes"], dtype=torch.uint8, device=x.device)
+        out = torch.empty(p["out_bytes"], dtype=torch.uint8, device=x.device)
+        rec = torch.empty(B, 4, dtype=torch.int64, device=x.device)
+        native.check(native.lib().ace355_flac_out_encode(native.ptr(x), B, S, Cn, int(sample_rate), native.ptr(scratch), scratch.numel(), native.ptr(out),
+                                                         out.numel(), native.ptr(rec), native.current_stream_ptr()), "flac_out_encode")
+        r = rec.cpu().tolist()
+        streams = []
+        for i, (size, mn, mx, status) in enumerate(r):
+            if status != 0:
+                raise RuntimeError(f"ace355: item {i}: a frame did not fit its slot")
+            at = i * p["item_stride"] + 42
+            streams.append(native.flac_streaminfo(S, Cn, sample_rate, mn, mx, digests[i]) + out[at:at + size].cpu().numpy().tobytes())
+    return streams
 
-    def __init__(self, default_format: str = "flac", n_threads: int = 0):
+
+class AudioSaver:
+    """AudioSaver of acestep/audio_utils.py:65-313 for GPU tensors and the PCM container formats.
+
+    ``flac_on_gpu`` (None: ``FLAC_OUT_GPU_DEFAULT``, which ACE355_FLAC_OUT_GPU=1 turns on) encodes the FLAC frames of a device batch on
+    the GPU: the files are the host encoder's byte for byte, and the MD5 is hashed by one host thread per item; ``flac_md5=False`` leaves
+    it zero and the PCM on the GPU.  WAV ignores both.  ``last_flac_report``: the path the last FLAC call took ("gpu" / "host"), the
+    reason, and the file sizes."""
+
+    def __init__(self, default_format: str = "flac", n_threads: int = 0, flac_on_gpu: Optional[bool] = None, flac_md5: bool = True):
         self.default_format = default_format.lower()
         if self.default_format not in FORMATS:  # audio_utils.py:75-78: unknown -> flac
             self.default_format = "flac"
         self.n_threads = int(n_threads)
+        self.flac_on_gpu = FLAC_OUT_GPU_DEFAULT if flac_on_gpu is None else bool(flac_on_gpu)
+        self.flac_md5 = bool(flac_md5)
+        self.last_flac_report = None
 
     def _resolve(self, output_path, format: Optional[str]):
         fmt = (format or self.default_format).lower()
@@ -198,9 +241,25 @@ class AudioSaver:
         w = wav.detach().to(torch.float32).contiguous()
         B, Cn, S = w.shape
         arr = (C.c_char_p * B)(*[os.fsencode(str(p)) for p in paths])
+        if fmt == "flac" and self.flac_on_gpu:
+            return self._save_flac_on_gpu(w, arr, paths, sample_rate)
         with torch.cuda.device(w.device):
             native.check(native.lib().ace355_save_audio_batch(native.ptr(w), B, Cn, S, int(sample_rate), _NATIVE[fmt], arr, self.n_threads,
                                                               native.current_stream_ptr()), "save_audio_batch")
+        if fmt == "flac":
+            self.last_flac_report = {"path": "host", "reason": "flac_on_gpu is off", "sizes": None}
+
+    def _save_flac_on_gpu(self, w: torch.Tensor, arr, paths, sample_rate: int):
+        """ace355_save_audio_batch_ex with ACE355_SAVE_FLAC_GPU.  The library makes the files by the host path when the plan refuses the
+        request or a launch or copy fails, and says why; the report repeats it."""
+        B, Cn, S = w.shape
+        flags = native.SAVE_FLAC_GPU | (0 if self.flac_md5 else native.SAVE_FLAC_NO_MD5)
+        with torch.cuda.device(w.device):
+            native.check(native.lib().ace355_save_audio_batch_ex(native.ptr(w), B, Cn, S, int(sample_rate), _NATIVE["flac"], arr, self.n_threads, flags,
+                                                                 native.current_stream_ptr()), "save_audio_batch_ex")
+        reason = native.last_error()
+        self.last_flac_report = {"path": "host" if reason else "gpu", "reason": reason or ("frames on the GPU, MD5 " + ("on the host" if self.flac_md5 else "left zero")),
+                                 "sizes": [os.path.getsize(str(p)) for p in paths]}
 
     def _save(self, items, paths, sample_rate: int, fmt: str):
         # the float -> PCM_16 / interleave step is a GPU kernel: host tensors are staged through the device

@@ -11,7 +11,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libace355.so")
-SOURCES = ["gemm.hip", "attn.hip", "elementwise.hip", "conv.hip", "dit.hip", "vae.hip", "cond.hip", "audio_out.hip", "api.hip", "lora.hip", "lokr.hip", "dora.hip", "xattn_probs.hip", "textenc.hip", "encoder.hip", "align_post.hip", "lm.hip", "lm_sample.hip", "lm_shape.hip", "audio_in.hip", "lm_score.hip", "flac_in.hip"]
+SOURCES = ["gemm.hip", "attn.hip", "elementwise.hip", "conv.hip", "dit.hip", "vae.hip", "cond.hip", "audio_out.hip", "api.hip", "lora.hip", "lokr.hip", "dora.hip", "xattn_probs.hip", "textenc.hip", "encoder.hip", "align_post.hip", "lm.hip", "lm_sample.hip", "lm_shape.hip", "audio_in.hip", "lm_score.hip", "flac_in.hip", "flac_out.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 # gemm.hip: MFMA results stay in architectural VGPRs.  Left to itself the register allocator moves the 16x16x32 accumulators of the
 # one-wave-per-SIMD kernels (3-4 LDS stages: 512 registers available) to AGPRs and then ROTATES them through v_accvgpr_read/write every

@@ -8,6 +8,7 @@
 // RIFF/WAVE layout; torchaudio / libsndfile / libFLAC are absent from the reference tree and from this image, so byte
 // equality with their output is not claimed - sample equality after decoding is (FLAC is lossless).
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
@@ -18,6 +19,7 @@
 
 #include "../../include/ace355.h"
 #include "common.h"
+#include "flac_out_plan.h"
 
 namespace ace355 {
 namespace {
@@ -695,6 +697,106 @@ int write_file(const char* path, const uint8_t* a, size_t na, const uint8_t* b, 
     return (fclose(f) == 0 && ok) ? 0 : 1;
 }
 
+// ------------------------------------------------------------------------------------------------ FLAC frames on the GPU
+// ace355_save_audio_batch_ex with ACE355_SAVE_FLAC_GPU (flac_out.hip does the frames).  Returns ACE355_OK with the files written and
+// last_error empty, an error code for a file that cannot be written, or -1 with *why set: the caller makes the files by the host path.
+// The buffers are kept between calls, as the host path keeps its own; one call at a time holds them.
+struct GpuFlacBuffers {
+    std::mutex mutex;
+    void *pcm = nullptr, *scratch = nullptr, *out = nullptr, *rec = nullptr;
+    uint8_t *host_out = nullptr, *host_pcm = nullptr, *host_rec = nullptr;
+    size_t cap[7] = {0, 0, 0, 0, 0, 0, 0};
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ready = nullptr;
+};
+hipError_t grow(void** p, size_t* cap, size_t need, bool pinned) {
+    if (need <= *cap) return hipSuccess;
+    if (*p) pinned ? hipHostFree(*p) : hipFree(*p);
+    *p = nullptr, *cap = 0;
+    const hipError_t e = pinned ? hipHostMalloc(p, need, hipHostMallocDefault) : hipMalloc(p, need);
+    if (e == hipSuccess) *cap = need;
+    return e;
+}
+int save_flac_gpu(const float* wav_dev, int n_items, int channels, int64_t samples, int sample_rate, const char* const* paths, int n_threads,
+                  bool want_md5, hipStream_t stream, std::string* why) {
+    const char* cap = getenv("ACE355_FLAC_OUT_MAX_UNITS");   // a ceiling on (item, block) pairs, 17 KB of scratch each; unset: the plan's
+    const FlacOutPlan p = plan_flac_out(n_items, samples, channels, cap ? atoll(cap) : FLAC_OUT_MAX_UNITS);
+    if (p.refusal) return *why = std::string("the plan refuses the request: ") + p.refusal, -1;
+    static GpuFlacBuffers B;
+    std::lock_guard<std::mutex> lock(B.mutex);
+    auto hip_why = [&](hipError_t e, const char* what) {
+        (void)hipGetLastError();
+        *why = std::string(what) + ": " + hipGetErrorString(e);
+        if (B.copy_stream) (void)hipStreamSynchronize(B.copy_stream);
+        return -1;
+    };
+    const size_t pcm_bytes = (size_t)samples * channels * 2, total = pcm_bytes * n_items, rec_bytes = (size_t)p.records_bytes;
+    hipError_t e = hipSuccess;
+    if (!B.copy_stream) e = hipStreamCreateWithFlags(&B.copy_stream, hipStreamNonBlocking);
+    if (e == hipSuccess && !B.ready) e = hipEventCreateWithFlags(&B.ready, hipEventDisableTiming);
+    if (e == hipSuccess) e = grow(&B.pcm, &B.cap[0], total, false);
+    if (e == hipSuccess) e = grow(&B.scratch, &B.cap[1], (size_t)p.scratch_bytes, false);
+    if (e == hipSuccess) e = grow(&B.out, &B.cap[2], (size_t)p.out_bytes, false);
+    if (e == hipSuccess) e = grow(&B.rec, &B.cap[3], rec_bytes, false);
+    if (e == hipSuccess) e = grow((void**)&B.host_out, &B.cap[4], (size_t)p.out_bytes, true);
+    if (e == hipSuccess) e = grow((void**)&B.host_rec, &B.cap[5], rec_bytes, true);
+    if (e == hipSuccess && want_md5) e = grow((void**)&B.host_pcm, &B.cap[6], total, true);
+    if (e != hipSuccess) return hip_why(e, "buffers");
+    if (launch_interleave(wav_dev, n_items, channels, (long)samples, B.pcm, 1, stream) != 0) return *why = ace355_last_error(), -1;
+    if (want_md5) {   // the PCM comes down on a second stream, beside the encode
+        e = hipEventRecord(B.ready, stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(B.copy_stream, B.ready, 0);
+        if (e == hipSuccess) e = hipMemcpyAsync(B.host_pcm, B.pcm, total, hipMemcpyDeviceToHost, B.copy_stream);
+        if (e != hipSuccess) return hip_why(e, "PCM copy");
+    }
+    if (ace355_flac_out_encode(static_cast<const int16_t*>(B.pcm), n_items, samples, channels, sample_rate, B.scratch, p.scratch_bytes, B.out,
+                               p.out_bytes, static_cast<int64_t*>(B.rec), stream) != ACE355_OK) {
+        *why = ace355_last_error();
+        (void)hipStreamSynchronize(B.copy_stream);
+        return -1;
+    }
+    e = hipMemcpyAsync(B.host_rec, B.rec, rec_bytes, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hip_why(e, "records");
+    const int64_t* rec = reinterpret_cast<const int64_t*>(B.host_rec);
+    for (int i = 0; i < n_items; ++i)
+        if (rec[4 * i + 3] != 0 || rec[4 * i] < 0 || rec[4 * i] > p.item_stride - 42) {
+            (void)hipStreamSynchronize(B.copy_stream);
+            return *why = "a frame did not fit its slot", -1;
+        }
+    for (int i = 0; i < n_items && e == hipSuccess; ++i)
+        e = hipMemcpyAsync(B.host_out + (size_t)p.item_stride * i + 42, static_cast<uint8_t*>(B.out) + (size_t)p.item_stride * i + 42, (size_t)rec[4 * i],
+                           hipMemcpyDeviceToHost, stream);
+    if (e != hipSuccess) return hip_why(e, "frame copy");
+    std::vector<uint8_t> md5((size_t)n_items * 16, 0);
+    std::vector<std::thread> hashers;
+    if (want_md5) {
+        e = hipStreamSynchronize(B.copy_stream);
+        if (e != hipSuccess) return hip_why(e, "PCM copy");
+        for (int i = 0; i < n_items; ++i)   // one thread per item, while the frames come down
+            hashers.emplace_back([&, i] {
+                Md5 m;
+                m.update(B.host_pcm + pcm_bytes * i, pcm_bytes);   // little-endian host
+                m.finish(md5.data() + 16 * i);
+            });
+    }
+    e = hipStreamSynchronize(stream);
+    for (auto& h : hashers) h.join();
+    if (e != hipSuccess) return hip_why(e, "frame copy");
+    std::atomic<int> failed{-1};
+    parallel_jobs(n_items, n_threads, [&](long i) {
+        uint8_t* f = B.host_out + (size_t)p.item_stride * i;
+        flac_out_streaminfo(f, samples, channels, sample_rate, (uint32_t)rec[4 * i + 1], (uint32_t)rec[4 * i + 2], want_md5 ? md5.data() + 16 * i : nullptr);
+        if (write_file(paths[i], f, 42 + (size_t)rec[4 * i], nullptr, 0)) failed = (int)i;
+    });
+    if (failed >= 0) {
+        set_error(std::string("save_audio_batch: cannot write ") + paths[failed.load()]);
+        return ACE355_ERR_INVALID;
+    }
+    set_error("");
+    return ACE355_OK;
+}
+
 }  // namespace
 }  // namespace ace355
 
@@ -795,10 +897,22 @@ int ace355_wav_encode(const void* interleaved, int64_t frames, int channels, int
 
 int ace355_save_audio_batch(const float* wav_dev, int n_items, int channels, int64_t samples, int sample_rate, int format,
                             const char* const* paths, int n_threads, void* stream) {
+    return ace355_save_audio_batch_ex(wav_dev, n_items, channels, samples, sample_rate, format, paths, n_threads, 0u, stream);
+}
+
+int ace355_save_audio_batch_ex(const float* wav_dev, int n_items, int channels, int64_t samples, int sample_rate, int format,
+                               const char* const* paths, int n_threads, uint32_t flags, void* stream) {
     ACE_CHECK(wav_dev && paths && n_items > 0 && n_items <= 4096 && samples > 0 && (channels == 1 || channels == 2), "save_audio_batch: bad argument");
     ACE_CHECK(format >= ACE355_AUDIO_FLAC && format <= ACE355_AUDIO_WAV_PCM16, "save_audio_batch: format is FLAC (PCM_16), WAV float32 or WAV PCM_16");
     ACE_CHECK(sample_rate > 0 && sample_rate < (1 << 20), "save_audio_batch: bad sample rate");
     for (int i = 0; i < n_items; ++i) ACE_CHECK(paths[i] && paths[i][0], "save_audio_batch: empty path");
+    ACE_CHECK((flags & ~(ACE355_SAVE_FLAC_GPU | ACE355_SAVE_FLAC_NO_MD5)) == 0, "save_audio_batch_ex: unknown flag bit");
+    std::string gpu_refusal;
+    if (format == ACE355_AUDIO_FLAC && (flags & ACE355_SAVE_FLAC_GPU)) {
+        const int rc = save_flac_gpu(wav_dev, n_items, channels, samples, sample_rate, paths, n_threads, !(flags & ACE355_SAVE_FLAC_NO_MD5),
+                                     (hipStream_t)stream, &gpu_refusal);
+        if (rc >= 0) return rc;   // done (last_error empty), or a file that cannot be written
+    }
     const bool is_float = format == ACE355_AUDIO_WAV_F32;
     const size_t per_item = (size_t)samples * channels * (is_float ? 4 : 2), total = per_item * n_items;
     // conversion scratch (device) and its pinned host mirror are kept between calls: page-locking 46 MB per batch cost
@@ -847,6 +961,7 @@ int ace355_save_audio_batch(const float* wav_dev, int n_items, int channels, int
         set_error(std::string("save_audio_batch: cannot write ") + paths[failed.load()]);
         return ACE355_ERR_INVALID;
     }
+    if (!gpu_refusal.empty()) set_error("save_audio_batch_ex: FLAC frames encoded by the host: " + gpu_refusal);
     return ACE355_OK;
 }
 

@@ -315,6 +315,16 @@ class FlacInPlanInfoC(C.Structure):
                                  "finish_tiles", "status_threads", "out_format", "reserved")]
 
 
+class FlacOutPlanInfoC(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("blocks", "units", "frame_grid", "offsets_grid", "gather_grid", "item_stride", "sizes_at", "offsets_at",
+                                         "scratch_bytes", "out_bytes", "records_bytes")] + [
+        (n, C.c_int32) for n in ("launches", "frame_threads", "offsets_threads", "gather_threads", "frame_lds_bytes", "offsets_lds_bytes",
+                                 "slot_stride", "reserved")]
+
+
+SAVE_FLAC_GPU, SAVE_FLAC_NO_MD5 = 1, 2   # ACE355_SAVE_*
+
+
 # name -> (restype, argtypes); every symbol include/ace355.h declares
 SIGNATURES = {
     "ace355_last_error": (C.c_char_p, []),
@@ -450,6 +460,12 @@ SIGNATURES = {
     "ace355_flac_in_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(FlacInPlanInfoC)]),
     "ace355_flac_in_decode": (C.c_int, [C.POINTER(FlacStreamInfoC), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ace355_flac_out_plan": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(FlacOutPlanInfoC)]),
+    "ace355_flac_out_encode": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p]),
+    "ace355_flac_streaminfo": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "ace355_save_audio_batch_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_uint32,
+                                             C.c_void_p]),
     "ace355_gemm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ace355_gemm_bf16_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -644,6 +660,24 @@ def flac_in_plan(frames: int, channels: int, bps: int, max_block: int, total_sam
     d = {k: int(getattr(out, k)) for k, _t in FlacInPlanInfoC._fields_ if k != "reserved"}
     d["out_format"] = PCM_FORMATS[d["out_format"]]
     return d
+
+
+def flac_out_plan(n_items: int, frames: int, channels: int) -> dict:
+    """`ace355_flac_out_plan` (include/ace355.h): the launches of the GPU FLAC encode for ``n_items`` items of ``frames`` frames - grids,
+    workgroup sizes, LDS bytes, the slot and item strides, scratch layout and bytes, output and record bytes.  A refusal raises with the
+    plan's text.  A function of its arguments alone; no GPU."""
+    out = FlacOutPlanInfoC()
+    check(lib().ace355_flac_out_plan(int(n_items), int(frames), int(channels), C.byref(out)), "flac_out_plan")
+    return {k: int(getattr(out, k)) for k, _t in FlacOutPlanInfoC._fields_ if k != "reserved"}
+
+
+def flac_streaminfo(frames: int, channels: int, sample_rate: int, min_frame: int, max_frame: int, md5: bytes = None) -> bytes:
+    """`ace355_flac_streaminfo`: "fLaC" and the STREAMINFO block, 42 bytes; ``md5`` None leaves the 16 MD5 bytes zero."""
+    out = (C.c_uint8 * 42)()
+    assert md5 is None or len(md5) == 16
+    check(lib().ace355_flac_streaminfo(out, int(frames), int(channels), int(sample_rate), int(min_frame), int(max_frame),
+                                       C.c_char_p(md5) if md5 is not None else None), "flac_streaminfo")
+    return bytes(out)
 
 
 def conv_plan(B: int, M: int, N: int, Cin: int, taps: int, **bits) -> dict:

@@ -1294,6 +1294,61 @@ int ace355_flac_in_decode(const ace355_flac_stream_info* info, const void* file_
                           void* scratch_dev, int64_t scratch_bytes, void* out_dev, int64_t out_bytes, int32_t* status_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FLAC frames encoded on the GPU (csrc/flac_out.hip): the interleaved int16 PCM of ace355_audio_interleave goes in, every 4096-sample
+ * block becomes its frame in one workgroup, the frames are compacted per item, and what comes down is the compressed bytes.  The rules
+ * are the host encoder's (ace355_flac_encode_pcm16), decision for decision and tie for tie, so the file is that encoder's file byte for
+ * byte.  The MD5 of STREAMINFO is a serial hash and stays on the host (or is left zero, "not computed").  Opt-in.
+ * ------------------------------------------------------------------------------------------ */
+#define ACE355_SAVE_FLAC_GPU 1u      /* ace355_save_audio_batch_ex: encode FLAC frames on the GPU */
+#define ACE355_SAVE_FLAC_NO_MD5 2u   /* with ACE355_SAVE_FLAC_GPU: STREAMINFO's MD5 is 16 zero bytes and no PCM is copied down */
+
+typedef struct ace355_flac_out_plan_info {
+    int64_t blocks;           /* 4096-sample blocks per item */
+    int64_t units;            /* n_items x blocks */
+    int64_t frame_grid;       /* one workgroup per (item, block) */
+    int64_t offsets_grid;     /* one workgroup per item */
+    int64_t gather_grid;      /* one workgroup per (item, block) */
+    int64_t item_stride;      /* output: item i's file starts at i x item_stride (ace355_flac_bound up to a multiple of 16) */
+    int64_t sizes_at;         /* scratch: frame slots [units][slot_stride] | uint32 sizes [units] at sizes_at | int64 offsets [units] at offsets_at */
+    int64_t offsets_at;
+    int64_t scratch_bytes;
+    int64_t out_bytes;
+    int64_t records_bytes;    /* int64 [n_items][4]: frame bytes, smallest frame, largest frame, status (0 = fine) */
+    int32_t launches;         /* frame, offsets, gather */
+    int32_t frame_threads;
+    int32_t offsets_threads;
+    int32_t gather_threads;
+    int32_t frame_lds_bytes;
+    int32_t offsets_lds_bytes;
+    int32_t slot_stride;      /* bytes of a frame's slot: 4096 x 2 x 17 / 8 + 64 */
+    int32_t reserved;
+} ace355_flac_out_plan_info;
+
+/* The launches ace355_flac_out_encode makes (csrc/flac_out_plan.h): a pure function of its arguments, no GPU.  ERR_INVALID for n_items
+ * outside 1 .. 4096, channels other than 1 / 2, frames outside 1 .. 2^36 - 1 (an empty stream is its 42 header bytes: nothing to launch),
+ * n_items x blocks above 2^21. */
+int ace355_flac_out_plan(int32_t n_items, int64_t frames, int32_t channels, ace355_flac_out_plan_info* out);
+/* pcm_dev: interleaved int16 [n_items][frames][channels], 4-byte aligned.  scratch_dev, out_dev 16-byte aligned and at least as large as
+ * the plan says; records_dev int64 [n_items][4].  Afterwards item i's frames are the records[i][0] bytes at out_dev + i x item_stride + 42;
+ * the 42 bytes ahead of them are the caller's (ace355_flac_streaminfo with records[i][1], records[i][2]).  A non-zero records[i][3] means
+ * a frame did not fit and the item's bytes are not a stream (it cannot happen: a frame never outgrows its verbatim form).  Enqueued on
+ * `stream`, no synchronisation; the same input gives the same bytes. */
+int ace355_flac_out_encode(const int16_t* pcm_dev, int32_t n_items, int64_t frames, int32_t channels, int32_t sample_rate, void* scratch_dev,
+                           int64_t scratch_bytes, void* out_dev, int64_t out_bytes, int64_t* records_dev, void* stream);
+/* Host: "fLaC" and the STREAMINFO block of a 16-bit stream of 4096-sample blocks, 42 bytes.  md5_or_null NULL: 16 zero bytes. */
+int ace355_flac_streaminfo(uint8_t* out42, int64_t frames, int32_t channels, int32_t sample_rate, uint32_t min_frame, uint32_t max_frame,
+                           const uint8_t* md5_or_null);
+/* ace355_save_audio_batch with flags (ACE355_SAVE_*; ace355_save_audio_batch is this call with flags 0).  ACE355_SAVE_FLAC_GPU, FLAC
+ * only (the WAV formats ignore both flags): interleave, ace355_flac_out_encode, the records and then the compressed bytes copied down,
+ * STREAMINFO and the files written by the host.  The MD5 is computed by one host thread per item on a PCM copy that comes down beside the
+ * encode - the files are then the flag-off files byte for byte - unless ACE355_SAVE_FLAC_NO_MD5 leaves it zero and the PCM on the GPU.
+ * If the plan refuses the request, or a launch, copy or allocation fails, the files are made by the host path; ace355_last_error then
+ * holds the reason, and is empty after a call that took the GPU path.  ACE355_FLAC_OUT_MAX_UNITS (environment, 1 .. 2^21) lowers the
+ * plan's ceiling on n_items x blocks, each of which takes 17 KB of the scratch this call keeps.  ERR_INVALID for an unknown flag bit. */
+int ace355_save_audio_batch_ex(const float* wav_dev, int n_items, int channels, int64_t samples, int sample_rate, int format,
+                               const char* const* paths, int n_threads, uint32_t flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Unit kernels (test hooks; each has an oracle twin in oracle/ used by tests/)
  * ---------------------------------------------------------------------------------------- */
 /* C = A[M,K] * W[N,K]^T, bf16 in, fp32 accumulate (MFMA).  out_dtype: ACE355_DTYPE_*; bias f32 [N] or NULL. */
